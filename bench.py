@@ -9,12 +9,17 @@ of one micro-batch per rank (weak scaling: clips are independent across micro-ba
 no data-path collective; the only collective is ONE all-reduce of the 3-float metric vector after the timed loop's last
 step — SURVEY 8e).  Inputs are resident in HBM before the timed region.  The forward is replayed from one hipGraph.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus:
+Prints ONE JSON line (rank 0) with the driver's contract.  A plain run does only what that line needs: set-up, warm-up, the
+--steps timed steps and the line.  --full adds the measurements that take runs of their own:
   "roofline":     the kernel with the largest share of device time (measured live with events on the launch stream in an
                   eager pass of the same forward), algorithmic FLOPs or bytes (SURVEY 8d) / its summed duration vs peak;
   "kernels":      the same figures for every C-ABI kernel, incl. the two the north_star names
                   (mumpy_window_attention_fwd: MFMA; mumpy_deform_sample_fwd: HBM);
+  "alt_*":        the same workload in the split-precision and bf16-storage modes (fp32, one GPU; --no-alt skips them);
   "cpu_baseline": the oracle (CPU restatement, kind "port") timed on this box's host cores on a bounded sample.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0's micro-batch) as DIR/<name>.npy; the inputs and weights
+are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -37,6 +42,7 @@ PEAK_HBM_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E spec peak
 HBM_BOUND = {"mumpy_deform_sample_fwd", "mumpy_layernorm_fwd", "mumpy_gn_stats_nhwc_fwd", "mumpy_gn_apply_resample_nhwc_fwd", "mumpy_final_conv_fwd", "mumpy_patch_merge_ln_fwd",
              "mumpy_add_fwd"}
 GFLOP_PER_CLIP_T5 = 253.9         # whole-forward algorithmic work at T=5
+DUMP_BYTES = 64 * 10**6           # --dump-outputs: all files together (B=8, T=5 writes every output in full: 54.6 MB)
 
 
 T_START = time.perf_counter()
@@ -62,14 +68,43 @@ def parse():
     ap.add_argument("--storage", choices=["fp32", "bf16"], default="fp32",
                     help="bf16: BASELINE config 3 as written (bf16 activations / weights in HBM inside the Swin blocks, bf16 MFMA, "
                          "f32 accumulate / statistics / residual stream); never the headline configuration")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra bf16x3 measurement reported beside the fp32 headline")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the per-kernel roofline, the north-star kernels, the split-precision "
+                         "and bf16-storage alternatives and the CPU baseline (each of the last two can be skipped below)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         f"at most {DUMP_BYTES // 10**6} MB in all")
+    ap.add_argument("--no-alt", action="store_true", help="(--full) skip the extra bf16x3 measurement reported beside the fp32 headline")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--rehearse", action="store_true",
                     help="launch-path rehearsal without a GPU: ranks, rendezvous, barrier, the metric all-reduce and the JSON "
                          "line are real, the forward is replaced by a sleep (CPU tests; MUMPY_BENCH_BACKEND=gloo)")
     ap.add_argument("--cpu-sample-batch", type=int, default=8)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(path, arrays):
+    """Write each array as <path>/<name>.npy: float64 stays float64, everything else becomes float32.  Smallest first, in
+    full while the DUMP_BYTES budget lasts; an array that no longer fits is written as <name>_sample.npy, its elements at
+    flat indices drawn from a fixed seed (the same for every run with the same shapes)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES
+    for name, t in sorted(arrays.items(), key=lambda kv: kv[1].numel()):
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        if t.numel() * t.element_size() + 4096 > left:          # (4096: room for the .npy header)
+            n = max(0, left - 4096) // t.element_size()
+            idx = torch.randint(0, t.numel(), (n,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        f = os.path.join(path, name + ".npy")
+        np.save(f, t.cpu().numpy())
+        left -= os.path.getsize(f)
+        log(f"  wrote {name}.npy ({t.numel()} x {t.dtype})")
 
 
 def profile_kernels(enc, dec, x):
@@ -403,9 +438,9 @@ def main():
     log("timing")
 
     def step():                     # one forward of the micro-batch, thresholded mask included (fused in the last kernel)
-        if fwd is None:
-            return fused_forward(enc, dec, x, with_mask=True)[1]
-        return fwd(x)[1]
+        if fwd is None:             # -> (logits, uint8 mask, feats)
+            return fused_forward(enc, dec, x, with_mask=True)
+        return fwd(x)
 
     # untimed warm-up of the timed path itself: the W steps the caller asked for, and at least ~0.3 s of replays -- a GPU that
     # idled through model construction needs that long to reach its steady clock (a cold first measurement of the short bf16
@@ -426,7 +461,8 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        mask = step()
+        outs = step()
+    mask = outs[1]
     # per-image F1/IoU on device (measure.py:57-62,86-89) + the ONE collective of the path: all-reduce of the metric vector
     metric = D.all_reduce_metric(D.eval_metric_vector(mask, gt))
     barrier()
@@ -434,21 +470,10 @@ def main():
     ops.check_workspaces()          # (outside the timed region) no split GEMM launch gave up on a partial tile: the masks are complete
 
     if rank == 0:
-        log(f"timed: {1e3 * dt / args.steps:.2f} ms/step; profiling kernels")
-        kernels, eager_ms = profile_kernels(enc, dec, x)
-        dom = dict(kernels[0])
-        # HBM-side bytes per launch of the dominant entry point from the PMC passes of the same workload (FETCH_SIZE x2 +
-        # WRITE_SIZE; tools/pmc_bench.sh + tools/summarize_pmc_bench.py -> profiles/): bench.py cannot run rocprofv3 on itself
-        dom["traffic"] = None
-        try:
-            pmc = json.load(open(os.path.join(ROOT, "profiles", "r03_pmc_bench_traffic.json")))
-            if args.math == "fp32" and args.batch == 8 and args.frames == 5 and dom["kernel"] in pmc:
-                dom["traffic"] = pmc[dom["kernel"]]["hbm_bytes_per_launch"]
-                dom["traffic_unit"] = "B per launch (PMC: profiles/r03_pmc_bench_traffic.md)"
-        except OSError:
-            pass
-        dom.pop("launches", None)
-        dom.pop("ms", None)
+        log(f"timed: {1e3 * dt / args.steps:.2f} ms/step")
+        if args.dump_outputs:
+            log(f"dumping the last step's outputs to {args.dump_outputs}")
+            dump_outputs(args.dump_outputs, {"logits": outs[0], "mask": mask, "feats": outs[2], "eval_metric": metric})
         clips = args.batch * world * args.steps
         out = {
             "metric": "clips/sec fwd (B=8,T=5,224x224)", "value": round(clips / dt, 3), "unit": "clips/s",
@@ -464,16 +489,30 @@ def main():
                                    f"tubelets ({args.frames},{args.frames - 1},1)",
                        "global_batch": args.batch * world, "launch": ("eager" if fwd is None else "hipGraph replay") + ", fork/join over HIP streams (independent branches co-scheduled)",
                        "parallelism": f"batch-sharded x{world}, one metric all-reduce"},
-            "roofline": dom,
-            "north_star_kernels": north_star_kernels(args.batch, args.frames, dev),
-            "kernels": kernels,
             "forward_gflop_per_clip": GFLOP_PER_CLIP_T5 if args.frames == 5 else None,
             "whole_forward_frac_of_f32_mfma_peak": round(GFLOP_PER_CLIP_T5 * 1e9 * clips / dt / world / (PEAK_F32_MFMA_TFLOPS * 1e12), 4)
             if args.frames == 5 else None,
-            "serial_eager_forward_ms": round(eager_ms, 3),
             "eval_metric": {"f1": float(metric[0] / metric[2]), "iou": float(metric[1] / metric[2]), "clips": int(metric[2])},
         }
-        if args.math == "fp32" and world == 1 and not args.no_alt:
+        if args.full:
+            log("profiling kernels")
+            kernels, eager_ms = profile_kernels(enc, dec, x)
+            dom = dict(kernels[0])
+            # HBM-side bytes per launch of the dominant entry point from the PMC passes of the same workload (FETCH_SIZE x2 +
+            # WRITE_SIZE; tools/pmc_bench.sh + tools/summarize_pmc_bench.py -> profiles/): bench.py cannot run rocprofv3 on itself
+            dom["traffic"] = None
+            try:
+                pmc = json.load(open(os.path.join(ROOT, "profiles", "r03_pmc_bench_traffic.json")))
+                if args.math == "fp32" and args.batch == 8 and args.frames == 5 and dom["kernel"] in pmc:
+                    dom["traffic"] = pmc[dom["kernel"]]["hbm_bytes_per_launch"]
+                    dom["traffic_unit"] = "B per launch (PMC: profiles/r03_pmc_bench_traffic.md)"
+            except OSError:
+                pass
+            dom.pop("launches", None)
+            dom.pop("ms", None)
+            out.update(roofline=dom, north_star_kernels=north_star_kernels(args.batch, args.frames, dev), kernels=kernels,
+                       serial_eager_forward_ms=round(eager_ms, 3))
+        if args.full and args.math == "fp32" and world == 1 and not args.no_alt:
             # the same workload with the GEMMs / convolutions in the split-precision modes: bf16x3 (fp32-level accuracy, tests:
             # test_linear_bf16x3_math, test_full_model_bf16x3_math_t5) and bf16x2 (16-bit-mantissa operands, TF32-class:
             # test_linear_bf16x2_math) -- reported beside the headline, never as `value`
@@ -502,7 +541,7 @@ def main():
                     out["alt_" + mode] = {"error": repr(e)[:200]}
                 finally:
                     ops.set_matrix_math("fp32")
-        if args.math == "fp32" and world == 1 and not args.no_alt:
+        if args.full and args.math == "fp32" and world == 1 and not args.no_alt:
             # BASELINE config 3's per-GPU workload as written: bf16 STORAGE inside the Swin blocks (LayerNorm output, qkv,
             # attention output and the 4C MLP hidden tensor are bf16 in HBM, weights read as bf16) + bf16 matrix math for every
             # other GEMM / convolution; fp32 accumulate, statistics and residual stream (test_full_model_bf16_storage_b8_t5)
@@ -531,7 +570,7 @@ def main():
                 out["alt_bf16_storage"] = {"error": repr(e)[:200]}
             finally:
                 ops.set_storage("fp32")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             log("cpu baseline (oracle on host cores)")
             try:
                 out["cpu_baseline"] = cpu_baseline(args.frames, args.cpu_sample_batch)

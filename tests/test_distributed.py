@@ -171,7 +171,7 @@ def test_bench_rank_path_with_a_live_rccl_group_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29519", MUMPY_FORCE_DIST="1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-alt",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-alt",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -179,6 +179,37 @@ def test_bench_rank_path_with_a_live_rccl_group_on_one_gpu():
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["unit"] == "clips/s" and out["value"] > 50
     assert out["scaling"] == "weak" and out["eval_metric"]["clips"] == 8 and out["roofline"]["frac"] > 0.3
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps and prints the headline without the --full figures;
+    --dump-outputs writes what the last timed step computed: logits, the thresholded mask, the decoder features and the
+    metric vector, consistent with each other and with the line's eval_metric."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 50 and out["dtype"] == "f32"
+    assert not {"roofline", "kernels", "north_star_kernels", "cpu_baseline", "alt_bf16x3", "alt_bf16_storage"} & set(out)
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["eval_metric.npy", "feats.npy", "logits.npy", "mask.npy"], files
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 * 10**6
+    logits, mask, feats, metric = (np.load(tmp_path / f) for f in ("logits.npy", "mask.npy", "feats.npy", "eval_metric.npy"))
+    assert logits.shape == mask.shape == (8, 1, 224, 224) and feats.shape == (8, 32, 224, 224)
+    assert logits.dtype == mask.dtype == feats.dtype == np.float32 and metric.dtype == np.float64
+    assert np.isfinite(logits).all() and np.isfinite(feats).all()
+    differ = mask != (logits > 0)                     # sigmoid(l) > 0.5 (fast exp): only logits next to 0 may disagree
+    assert not differ.any() or np.abs(logits[differ]).max() < 1e-4
+    assert metric[2] == 8 and abs(metric[0] / metric[2] - out["eval_metric"]["f1"]) < 1e-12
 
 
 @pytest.mark.gpu

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Copy the outputs of tools/final_profiles.sh from gpurun_out/ (scratch) into profiles/<tag>_* (tracked).  usage: collect_profiles.py r03"""
+"""Copy the outputs of tools/final_profiles.sh from $MUMPY_PROFILE_OUT (scratch, default profile_out/) into profiles/<tag>_* (tracked).
+usage: collect_profiles.py r03"""
 import json, os, shutil, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.environ.get("MUMPY_PROFILE_OUT", os.path.join(ROOT, "profile_out")), os.path.join(ROOT, "profiles")
 pairs = {
     "bench_final.json": "final_bench.json", "bench_t9.json": "bench_t9.json", "bench_b16.json": "bench_b16.json", "bench_b1.json": "bench_b1.json",
     "stats_serial.csv": "final_serial_kernel_stats.csv", "stats_fj.csv": "final_kernel_stats.csv", "stats_s16.csv": "bf16_storage_serial_kernel_stats.csv",

@@ -1,7 +1,7 @@
 #!/bin/bash
 # The tiled kernels' split-K rule (slices >= 384 deep, at most 16 splits, K >= 768) against more aggressive ones, on the whole forward.
 export OMP_NUM_THREADS=16 MUMPY_TUNING=1
-run() { python bench.py --no-cpu-baseline --no-alt 2>/dev/null | python -c "
+run() { python bench.py --full --no-cpu-baseline --no-alt 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); k={e['kernel']:e for e in d['kernels']}
 print('$1', d['value'], d['ms_per_step'], 'conv ms', k['mumpy_conv2d_nhwc_fwd']['ms'], 'linear ms', k['mumpy_linear_wsz_fwd']['ms'])"; }
 for i in 1 2; do

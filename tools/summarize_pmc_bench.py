@@ -8,7 +8,8 @@ tag = sys.argv[1] if len(sys.argv) > 1 else "r01"
 
 
 def agg(counter):
-    f = max(glob.glob(os.path.join(ROOT, "gpurun_out", f"pmc_bench_{counter}", "*", "*counter_collection.csv")), key=os.path.getmtime)
+    out = os.environ.get("MUMPY_PROFILE_OUT", os.path.join(ROOT, "profile_out"))          # tools/pmc_bench.sh
+    f = max(glob.glob(os.path.join(out, f"pmc_bench_{counter}", "*", "*counter_collection.csv")), key=os.path.getmtime)
     d = collections.defaultdict(lambda: [0, 0.0])
     for r in csv.DictReader(open(f)):
         d[r["Kernel_Name"]][0] += 1
@@ -25,7 +26,7 @@ gemm = [r for r in rows if is_gemm(r[1]) or r[1].startswith("splitk_reduce")]
 # ABI launches of mumpy_linear_wsz_fwd + mumpy_linear_rows_fwd per forward = non-conv linear_kernel + gemm_ws_kernel dispatches
 abi_launches = sum(r[2] for r in gemm if is_gemm(r[1]))
 gemm_bytes = sum(r[3] + r[4] for r in gemm)
-out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --steps 2 --warmup 1 "
+out = {"source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE (separate passes) -- python3 bench.py --full --steps 2 --warmup 1 "
                  "--no-cpu-baseline --no-alt --no-graph, MUMPY_SERIAL=1; FETCH_SIZE x2 (gfx950 correction)",
        "forwards_in_profile": forwards,
        "mumpy_linear_wsz_fwd": {"launches": abi_launches, "hbm_bytes_per_launch": round(gemm_bytes / abi_launches),
