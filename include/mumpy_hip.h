@@ -363,6 +363,35 @@ int mumpy_adamw_hyper(float* out8_host, double lr, double beta1, double beta2, d
 int mumpy_adamw_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                          const float* hyper_dev, void* stream);
 
+/* fused SGD step over a FLAT buffer of n parameters (torch.optim.SGD single-tensor semantics, utils/utils.py:254):
+ *   d = g + wd*p;  if momentum != 0: buf = momentum*buf + d, d = nesterov ? d + momentum*buf : buf;  p -= lr*d
+ * with g = grad * grad_scale.  momentum == 0: no buffer (momentum_buf may be NULL); otherwise momentum_buf is required and
+ * a buffer that starts at zero reproduces torch's first step (buf = clone(d)) exactly.  dampening must be 0 (the only
+ * value the reference uses), nesterov requires momentum > 0; anything else is MUMPY_EINVAL.  In place on param /
+ * momentum_buf.  Each hyper-parameter is rounded from double to fp32 once, as torch does. */
+int mumpy_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, double lr, double momentum,
+                   double dampening, double weight_decay, int nesterov, double grad_scale, void* stream);
+/* the same update with its constants read from DEVICE memory (hipGraph replay, as mumpy_adamw_step_dev): mumpy_sgd_hyper
+ * fills a HOST array of 4 floats; momentum_buf NULL <=> momentum 0 (nesterov and momentum_buf are frozen at capture). */
+int mumpy_sgd_hyper(float* out4_host, double lr, double momentum, double dampening, double weight_decay, int nesterov,
+                    double grad_scale);
+int mumpy_sgd_step_dev(float* param, const float* grad, float* momentum_buf, int64_t n, const float* hyper_dev, int nesterov,
+                       void* stream);
+
+/* fused RMSprop step over a FLAT buffer of n parameters (torch.optim.RMSprop single-tensor semantics, centered=False,
+ * utils/utils.py:260):
+ *   d = g + wd*p;  sq = alpha*sq + (1-alpha)*d^2;  den = sqrt(sq) + eps;
+ *   momentum > 0: buf = momentum*buf + d/den, p -= lr*buf;  otherwise p -= lr*d/den
+ * with g = grad * grad_scale.  momentum_buf is required when momentum > 0 and may be NULL otherwise.  In place on param /
+ * square_avg / momentum_buf.  mumpy_rmsprop_hyper fills a HOST array of 8 floats for mumpy_rmsprop_step_dev (hipGraph
+ * replay; momentum_buf NULL <=> momentum 0). */
+int mumpy_rmsprop_step(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n, double lr,
+                       double alpha, double eps, double weight_decay, double momentum, double grad_scale, void* stream);
+int mumpy_rmsprop_hyper(float* out8_host, double lr, double alpha, double eps, double weight_decay, double momentum,
+                        double grad_scale);
+int mumpy_rmsprop_step_dev(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n,
+                           const float* hyper_dev, void* stream);
+
 /* ---- backward kernels of the Swin block (rows 5-7 of 8a in training) ---------------------------------
  * LayerNorm backward (swin:266,305): x, dy, dx (rows,C); gamma, dgamma, dbeta (C); C % 4 == 0, C <= 2048.
  * dx_add (rows,C) or null: added to dx -- the gradient arriving over the residual branch that bypasses the LayerNorm

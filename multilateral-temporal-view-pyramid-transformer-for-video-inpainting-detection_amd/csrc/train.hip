@@ -13,6 +13,9 @@
 //
 // AdamW: torch.optim.AdamW single-tensor semantics (utils/utils.py:258; decoupled weight decay, bias correction) over a
 // FLAT parameter buffer: one launch per parameter group instead of one per tensor.  28 B of HBM traffic per parameter.
+// SGD and RMSprop, the other two branches of get_optimizer (utils/utils.py:252-261), the same way: torch.optim.SGD (coupled
+// weight decay, momentum, dampening 0, optional Nesterov; 20 B per parameter with momentum, 12 B without) and
+// torch.optim.RMSprop (uncentered; 20 B per parameter, 28 B with momentum).
 #include <string.h>
 #include "common.h"
 using namespace mumpy;
@@ -162,6 +165,119 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
     if (i < a.n) adam_one(a.p[i], a.g[i], a.m[i], a.v[i], hy);
 }
 
+struct SgdHyper {
+    float grad_scale, weight_decay, momentum, lr;       // each rounded from a double once, as the Python floats torch uses
+};
+struct SgdArgs {
+    float* p; const float* g; float* buf;               // buf == nullptr: momentum 0, no buffer
+    int64_t n;
+    SgdHyper h;
+    const SgdHyper* hdev;                               // as AdamArgs::hdev
+    int nesterov;
+};
+
+// torch.optim.SGD, _single_tensor_sgd with dampening 0, one operation at a time and rounded as torch's kernels round
+// (`a.add(b, alpha=c)` is one fma(b, c, a); `mul_` rounds on its own), so a cancelling d = g + wd * p comes out identical:
+//   d = grad + wd * p;  buf = buf * momentum + d;  d = nesterov ? d + momentum * buf : buf;  p += -lr * d
+template <bool MOM>
+__device__ __forceinline__ void sgd_one(float& p, float g, float& b, const SgdHyper& a, bool nesterov) {
+#pragma clang fp contract(off)
+    float d = fmaf(p, a.weight_decay, g * a.grad_scale);   // grad.add(param, alpha=weight_decay)
+    if (MOM) {
+        b = b * a.momentum + d;                         // buf.mul_(momentum).add_(d_p, alpha=1 - dampening)
+        d = nesterov ? fmaf(b, a.momentum, d) : b;      // d_p.add(buf, alpha=momentum) | buf
+    }
+    p = fmaf(d, -a.lr, p);                              // param.add_(d_p, alpha=-lr)
+}
+
+template <bool MOM>
+__global__ __launch_bounds__(256) void sgd_kernel(SgdArgs a) {
+    const SgdHyper hy = a.hdev ? *a.hdev : a.h;
+    const bool nest = a.nesterov != 0;
+    const int64_t n4 = a.n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        f32x4 p = reinterpret_cast<f32x4*>(a.p)[i], b{};
+        const f32x4 g = reinterpret_cast<const f32x4*>(a.g)[i];
+        if (MOM) b = reinterpret_cast<f32x4*>(a.buf)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pe = p[e], be = b[e];
+            sgd_one<MOM>(pe, g[e], be, hy, nest);
+            p[e] = pe; b[e] = be;
+        }
+        reinterpret_cast<f32x4*>(a.p)[i] = p;
+        if (MOM) reinterpret_cast<f32x4*>(a.buf)[i] = b;
+    }
+    const int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x;       // tail (< 4 elements)
+    if (i < a.n) {
+        float be = MOM ? a.buf[i] : 0.f;
+        sgd_one<MOM>(a.p[i], a.g[i], be, hy, nest);
+        if (MOM) a.buf[i] = be;
+    }
+}
+
+struct RmsHyper {
+    float grad_scale, weight_decay, alpha, oma, eps, momentum, lr, pad;   // oma = 1 - alpha (rounded from the double)
+};
+struct RmsArgs {
+    float* p; const float* g; float* sq; float* buf;    // buf == nullptr: momentum 0
+    int64_t n;
+    RmsHyper h;
+    const RmsHyper* hdev;
+};
+
+// torch.optim.RMSprop, _single_tensor_rmsprop with centered=False, rounded op by op as torch's kernels round (as sgd_one;
+// `addcmul_` is fma(value * t1, t2, self), `addcdiv_` is self + (value * t1) / t2 without fma).  d / den is scale-free, so where d = g + wd * p cancels, one ulp of d moves
+// the update by O(1): the rounding of every step has to be torch's, not merely as accurate.
+//   d = grad + wd * p;  sq = sq * alpha + (1 - alpha) * d^2;  den = sqrt(sq) + eps;
+//   momentum > 0: buf = buf * momentum + d / den, p += -lr * buf;  else p += -lr * (d / den)
+template <bool MOM>
+__device__ __forceinline__ void rms_one(float& p, float g, float& sq, float& b, const RmsHyper& a) {
+#pragma clang fp contract(off)
+    const float d = fmaf(p, a.weight_decay, g * a.grad_scale);   // grad.add(param, alpha=weight_decay)
+    sq = fmaf(a.oma * d, d, sq * a.alpha);                      // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+    const float den = sqrtf(sq) + a.eps;                        // square_avg.sqrt().add_(eps)
+    if (MOM) {
+        b = b * a.momentum + d / den;                           // buf.mul_(momentum).addcdiv_(grad, avg)
+        p = fmaf(b, -a.lr, p);                                  // param.add_(buf, alpha=-lr)
+    } else {
+        p = p + ((-a.lr) * d) / den;                            // param.addcdiv_(grad, avg, value=-lr): self + value * t1 / t2
+    }
+}
+
+template <bool MOM>
+__global__ __launch_bounds__(256) void rmsprop_kernel(RmsArgs a) {
+    const RmsHyper hy = a.hdev ? *a.hdev : a.h;
+    const int64_t n4 = a.n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * 256;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+        f32x4 p = reinterpret_cast<f32x4*>(a.p)[i], sq = reinterpret_cast<f32x4*>(a.sq)[i], b{};
+        const f32x4 g = reinterpret_cast<const f32x4*>(a.g)[i];
+        if (MOM) b = reinterpret_cast<f32x4*>(a.buf)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float pe = p[e], se = sq[e], be = b[e];
+            rms_one<MOM>(pe, g[e], se, be, hy);
+            p[e] = pe; sq[e] = se; b[e] = be;
+        }
+        reinterpret_cast<f32x4*>(a.p)[i] = p; reinterpret_cast<f32x4*>(a.sq)[i] = sq;
+        if (MOM) reinterpret_cast<f32x4*>(a.buf)[i] = b;
+    }
+    const int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x;       // tail (< 4 elements)
+    if (i < a.n) {
+        float be = MOM ? a.buf[i] : 0.f;
+        rms_one<MOM>(a.p[i], a.g[i], a.sq[i], be, hy);
+        if (MOM) a.buf[i] = be;
+    }
+}
+
+int64_t update_grid(int64_t n) {               // grid-stride launch of the flat-buffer updates
+    int64_t grid = ((n >> 2) + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    return grid < 1 ? 1 : grid;
+}
+
 int loss_splits(int B, int64_t P) {            // enough blocks to fill the chip, chunks of >= 2048 elements
     int64_t s = (1024 + B - 1) / B;
     const int64_t cap = (P + 2047) / 2048;
@@ -214,10 +330,7 @@ static int adamw_launch(float* param, const float* grad, float* exp_avg, float* 
     a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
     a.hdev = reinterpret_cast<const AdamHyper*>(hyper_dev);
     if (host) a.h = *host; else a.h = AdamHyper{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 1.f, 0.f};
-    int64_t grid = ((n >> 2) + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)update_grid(n)), dim3(256), 0, as_stream(stream), a);
     MUMPY_CHECK_LAUNCH("adamw");
     return 0;
 }
@@ -248,4 +361,111 @@ extern "C" int mumpy_adamw_step_dev(float* param, const float* grad, float* exp_
     if (n == 0) return 0;
     MUMPY_REQUIRE(n > 0 && hyper_dev, MUMPY_EINVAL, "adamw_step_dev: bad arguments");
     return adamw_launch(param, grad, exp_avg, exp_avg_sq, n, nullptr, hyper_dev, stream);
+}
+
+// ---- SGD ----
+static int sgd_hyper(SgdHyper& h, double lr, double momentum, double dampening, double weight_decay, int nesterov,
+                     double grad_scale) {
+    MUMPY_REQUIRE(lr >= 0. && momentum >= 0. && weight_decay >= 0., MUMPY_EINVAL, "sgd: bad arguments (lr=%g momentum=%g wd=%g)",
+                  lr, momentum, weight_decay);
+    MUMPY_REQUIRE(dampening == 0., MUMPY_EINVAL, "sgd: dampening %g is not supported (only 0)", dampening);
+    MUMPY_REQUIRE(!nesterov || momentum > 0., MUMPY_EINVAL, "sgd: Nesterov momentum requires a momentum");
+    h.grad_scale = (float)grad_scale; h.weight_decay = (float)weight_decay; h.momentum = (float)momentum; h.lr = (float)lr;
+    return 0;
+}
+
+static int sgd_launch(float* param, const float* grad, float* momentum_buf, int64_t n, const SgdHyper* host,
+                      const float* hyper_dev, int nesterov, void* stream) {
+    MUMPY_REQUIRE(param && grad, MUMPY_ENULL, "sgd: null pointer");
+    MUMPY_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf), MUMPY_EALIGN, "sgd: buffers must be 16-byte aligned");
+    MUMPY_REQUIRE(!nesterov || momentum_buf, MUMPY_EINVAL, "sgd: Nesterov momentum requires a momentum buffer");
+    SgdArgs a;
+    a.p = param; a.g = grad; a.buf = momentum_buf; a.n = n; a.nesterov = nesterov;
+    a.hdev = reinterpret_cast<const SgdHyper*>(hyper_dev);
+    a.h = host ? *host : SgdHyper{0.f, 0.f, 0.f, 0.f};
+    if (momentum_buf)
+        hipLaunchKernelGGL(sgd_kernel<true>, dim3((unsigned)update_grid(n)), dim3(256), 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(sgd_kernel<false>, dim3((unsigned)update_grid(n)), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH("sgd");
+    return 0;
+}
+
+extern "C" int mumpy_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, double lr, double momentum,
+                              double dampening, double weight_decay, int nesterov, double grad_scale, void* stream) {
+    MUMPY_REQUIRE(n >= 0, MUMPY_EINVAL, "sgd: bad size n=%lld", (long long)n);
+    SgdHyper h;
+    if (int rc = sgd_hyper(h, lr, momentum, dampening, weight_decay, nesterov, grad_scale)) return rc;
+    MUMPY_REQUIRE(momentum == 0. || momentum_buf, MUMPY_ENULL, "sgd: momentum %g needs a momentum buffer", momentum);
+    if (n == 0) return 0;
+    return sgd_launch(param, grad, momentum != 0. ? momentum_buf : nullptr, n, &h, nullptr, nesterov, stream);
+}
+
+extern "C" int mumpy_sgd_hyper(float* out4_host, double lr, double momentum, double dampening, double weight_decay,
+                               int nesterov, double grad_scale) {
+    MUMPY_REQUIRE(out4_host, MUMPY_ENULL, "sgd_hyper: null pointer");
+    SgdHyper h;
+    if (int rc = sgd_hyper(h, lr, momentum, dampening, weight_decay, nesterov, grad_scale)) return rc;
+    memcpy(out4_host, &h, sizeof(h));
+    return 0;
+}
+
+extern "C" int mumpy_sgd_step_dev(float* param, const float* grad, float* momentum_buf, int64_t n, const float* hyper_dev,
+                                  int nesterov, void* stream) {
+    MUMPY_REQUIRE(n >= 0 && hyper_dev, MUMPY_EINVAL, "sgd_step_dev: bad arguments");
+    if (n == 0) return 0;
+    return sgd_launch(param, grad, momentum_buf, n, nullptr, hyper_dev, nesterov, stream);
+}
+
+// ---- RMSprop ----
+static int rmsprop_hyper(RmsHyper& h, double lr, double alpha, double eps, double weight_decay, double momentum,
+                         double grad_scale) {
+    MUMPY_REQUIRE(lr >= 0. && alpha >= 0. && eps >= 0. && weight_decay >= 0. && momentum >= 0., MUMPY_EINVAL,
+                  "rmsprop: bad arguments (lr=%g alpha=%g eps=%g wd=%g momentum=%g)", lr, alpha, eps, weight_decay, momentum);
+    h.grad_scale = (float)grad_scale; h.weight_decay = (float)weight_decay; h.alpha = (float)alpha; h.oma = (float)(1.0 - alpha);
+    h.eps = (float)eps; h.momentum = (float)momentum; h.lr = (float)lr; h.pad = 0.f;
+    return 0;
+}
+
+static int rmsprop_launch(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n,
+                          const RmsHyper* host, const float* hyper_dev, void* stream) {
+    MUMPY_REQUIRE(param && grad && square_avg, MUMPY_ENULL, "rmsprop: null pointer");
+    MUMPY_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(square_avg) && aligned16(momentum_buf), MUMPY_EALIGN,
+                  "rmsprop: buffers must be 16-byte aligned");
+    RmsArgs a;
+    a.p = param; a.g = grad; a.sq = square_avg; a.buf = momentum_buf; a.n = n;
+    a.hdev = reinterpret_cast<const RmsHyper*>(hyper_dev);
+    a.h = host ? *host : RmsHyper{0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+    if (momentum_buf)
+        hipLaunchKernelGGL(rmsprop_kernel<true>, dim3((unsigned)update_grid(n)), dim3(256), 0, as_stream(stream), a);
+    else
+        hipLaunchKernelGGL(rmsprop_kernel<false>, dim3((unsigned)update_grid(n)), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH("rmsprop");
+    return 0;
+}
+
+extern "C" int mumpy_rmsprop_step(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n, double lr,
+                                  double alpha, double eps, double weight_decay, double momentum, double grad_scale, void* stream) {
+    MUMPY_REQUIRE(n >= 0, MUMPY_EINVAL, "rmsprop: bad size n=%lld", (long long)n);
+    RmsHyper h;
+    if (int rc = rmsprop_hyper(h, lr, alpha, eps, weight_decay, momentum, grad_scale)) return rc;
+    MUMPY_REQUIRE(momentum == 0. || momentum_buf, MUMPY_ENULL, "rmsprop: momentum %g needs a momentum buffer", momentum);
+    if (n == 0) return 0;
+    return rmsprop_launch(param, grad, square_avg, momentum != 0. ? momentum_buf : nullptr, n, &h, nullptr, stream);
+}
+
+extern "C" int mumpy_rmsprop_hyper(float* out8_host, double lr, double alpha, double eps, double weight_decay, double momentum,
+                                   double grad_scale) {
+    MUMPY_REQUIRE(out8_host, MUMPY_ENULL, "rmsprop_hyper: null pointer");
+    RmsHyper h;
+    if (int rc = rmsprop_hyper(h, lr, alpha, eps, weight_decay, momentum, grad_scale)) return rc;
+    memcpy(out8_host, &h, sizeof(h));
+    return 0;
+}
+
+extern "C" int mumpy_rmsprop_step_dev(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n,
+                                      const float* hyper_dev, void* stream) {
+    MUMPY_REQUIRE(n >= 0 && hyper_dev, MUMPY_EINVAL, "rmsprop_step_dev: bad arguments");
+    if (n == 0) return 0;
+    return rmsprop_launch(param, grad, square_avg, momentum_buf, n, nullptr, hyper_dev, stream);
 }

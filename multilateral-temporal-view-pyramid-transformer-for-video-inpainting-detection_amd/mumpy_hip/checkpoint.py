@@ -2,7 +2,8 @@
 
 Format (utils/utils.py:264-276): `encoder_{epoch}.pt` / `decoder_{epoch}.pt` (or `encoder.pt` / `decoder.pt`) are plain
 `state_dict`s written with `torch.save`, `enc_opt_{epoch}.pt` / `dec_opt_{epoch}.pt` the optimizers' `state_dict`s
-(torch.optim.AdamW layout: `mumpy_hip.train.FlatAdamW.state_dict`); a model trained under `nn.DataParallel` carries a
+(the layout of torch.optim.AdamW, SGD or RMSprop, whichever the group uses: `mumpy_hip.train.FlatAdamW` / `FlatSGD` /
+`FlatRMSprop.state_dict`); a model trained under `nn.DataParallel` carries a
 `module.` prefix on every key, which `check_parallel` strips (utils/utils.py:156-176).  The reference keeps a third
 optimizer for the cross-view parameters (train.py:211-213) that its own save_checkpoint drops; here it is written too
 (`cva_opt_{epoch}.pt`) so that a resumed run continues the same trajectory.  Differences on purpose:
@@ -57,7 +58,7 @@ def save_checkpoint(directory: str, encoder: torch.nn.Module, decoder: torch.nn.
 
 def load_optimizer_states(directory: str, epoch: Optional[int] = None, map_location="cpu") -> Dict[str, dict]:
     """{"enc": state_dict, "dec": ..., "cva": ...} for the optimizer files present (weights-only load: tensors, numbers,
-    lists and dicts only).  Feed each to FlatAdamW.load_state_dict to resume (train.py:179-188 does this with torch's)."""
+    lists and dicts only).  Feed each to the matching optimizer's load_state_dict to resume (train.py:179-188 does this with torch's)."""
     out = {}
     for key in ("enc", "dec", "cva"):
         path = os.path.join(directory, _opt_name(key, epoch))

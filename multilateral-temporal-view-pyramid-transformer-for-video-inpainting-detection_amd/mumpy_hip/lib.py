@@ -94,6 +94,12 @@ SIGNATURES = {
     "mumpy_adamw_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_d, c_i, c_d],
     "mumpy_adamw_step_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f],
     "mumpy_adamw_step": [c_f, c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_d, c_i, c_d, c_f],
+    "mumpy_sgd_step": [c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_i, c_d, c_f],
+    "mumpy_sgd_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_i, c_d],
+    "mumpy_sgd_step_dev": [c_f, c_f, c_f, c_l, c_f, c_i, c_f],
+    "mumpy_rmsprop_step": [c_f, c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_d, c_d, c_f],
+    "mumpy_rmsprop_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_d, c_d],
+    "mumpy_rmsprop_step_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f],
 }
 ABI_VERSION = 2
 

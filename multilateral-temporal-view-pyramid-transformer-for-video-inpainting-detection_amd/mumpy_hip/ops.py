@@ -1138,3 +1138,71 @@ def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, hyper_dev):
     _call("mumpy_adamw_step_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(_chk(hyper_dev, "hyper")), _stream(),
           work=28.0 * n)
     return param
+
+
+def _flat_bufs(fn, n, **bufs):
+    """The contiguity / size checks of adamw_step for the in-place optimizer buffers (None = buffer not used)."""
+    for name, t in bufs.items():
+        if t is None:
+            continue
+        _chk(t, name)
+        if t.numel() != n or not t.is_contiguous():
+            raise RuntimeError(f"{fn}: {name} must be a contiguous buffer of {n} elements (in-place update)")
+
+
+def _hyper_out(fn, count, *args):
+    import ctypes
+    out = torch.empty(count, dtype=torch.float32).pin_memory()
+    rc = getattr(_lib(), fn)(ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_float)), *args)
+    if rc != 0:
+        raise RuntimeError(f"{fn} failed (rc={rc}): {_lib().mumpy_last_error().decode()}")
+    return out
+
+
+def sgd_step(param, grad, momentum_buf, lr, momentum=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0, dampening=0.0):
+    """In-place fused SGD over flat fp32 buffers (torch.optim.SGD semantics; momentum_buf None when momentum == 0; a zero
+    buffer reproduces torch's first step).  dampening must be 0."""
+    n = param.numel()
+    _flat_bufs("sgd_step", n, param=param, grad=grad, momentum_buf=momentum_buf)
+    _call("mumpy_sgd_step", _p(param), _p(grad), _p(momentum_buf), n, lr, momentum, dampening, weight_decay, int(bool(nesterov)),
+          grad_scale, _stream(), work=(20.0 if momentum_buf is not None else 12.0) * n)
+    return param
+
+
+def sgd_hyper(lr, momentum=0.0, weight_decay=0.0, nesterov=False, grad_scale=1.0, dampening=0.0):
+    """The 4 fp32 constants of one SGD step as a pinned host tensor (for sgd_step_dev under hipGraph replay)."""
+    return _hyper_out("mumpy_sgd_hyper", 4, lr, momentum, dampening, weight_decay, int(bool(nesterov)), grad_scale)
+
+
+def sgd_step_dev(param, grad, momentum_buf, hyper_dev, nesterov=False):
+    """SGD over flat buffers with the step constants in the device tensor `hyper_dev` (4 floats): capturable."""
+    n = param.numel()
+    _flat_bufs("sgd_step_dev", n, param=param, grad=grad, momentum_buf=momentum_buf)
+    _call("mumpy_sgd_step_dev", _p(param), _p(grad), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")), int(bool(nesterov)),
+          _stream(), work=(20.0 if momentum_buf is not None else 12.0) * n)
+    return param
+
+
+def rmsprop_step(param, grad, square_avg, momentum_buf, lr, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0,
+                 grad_scale=1.0):
+    """In-place fused RMSprop over flat fp32 buffers (torch.optim.RMSprop semantics, centered=False; momentum_buf None
+    when momentum == 0)."""
+    n = param.numel()
+    _flat_bufs("rmsprop_step", n, param=param, grad=grad, square_avg=square_avg, momentum_buf=momentum_buf)
+    _call("mumpy_rmsprop_step", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, lr, alpha, eps, weight_decay, momentum,
+          grad_scale, _stream(), work=(28.0 if momentum_buf is not None else 20.0) * n)
+    return param
+
+
+def rmsprop_hyper(lr, alpha=0.99, eps=1e-8, weight_decay=0.0, momentum=0.0, grad_scale=1.0):
+    """The 8 fp32 constants of one RMSprop step as a pinned host tensor (for rmsprop_step_dev under hipGraph replay)."""
+    return _hyper_out("mumpy_rmsprop_hyper", 8, lr, alpha, eps, weight_decay, momentum, grad_scale)
+
+
+def rmsprop_step_dev(param, grad, square_avg, momentum_buf, hyper_dev):
+    """RMSprop over flat buffers with the step constants in the device tensor `hyper_dev` (8 floats): capturable."""
+    n = param.numel()
+    _flat_bufs("rmsprop_step_dev", n, param=param, grad=grad, square_avg=square_avg, momentum_buf=momentum_buf)
+    _call("mumpy_rmsprop_step_dev", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")),
+          _stream(), work=(28.0 if momentum_buf is not None else 20.0) * n)
+    return param

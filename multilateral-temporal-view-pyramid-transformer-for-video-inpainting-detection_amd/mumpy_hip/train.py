@@ -1,15 +1,18 @@
-"""Training tail of config 5: parameter groups, fused AdamW on flat buffers, the polynomial LR schedule and
-the bucketed gradient all-reduce.  The model backward itself is not part of this round (forward kernels only), so these
+"""Training tail of config 5: parameter groups, fused AdamW / SGD / RMSprop on flat buffers, the polynomial LR
+schedule and the bucketed gradient all-reduce.  The model backward itself is not part of this round (forward kernels only), so these
 pieces are exercised on their own: loss + gradient wrt the logits, optimizer update, schedule, collective.
 
 Reference behaviour reproduced:
   * three optimizers: encoder parameters whose name contains "cva" / the other encoder parameters / the decoder
-    (train.py:198-213), each `torch.optim.AdamW(lr, weight_decay)` with torch defaults otherwise (utils/utils.py:258);
+    (train.py:198-213), each built by `get_optimizer` (utils/utils.py:252-261): `torch.optim.SGD(lr, weight_decay,
+    momentum=0.9)`, `torch.optim.AdamW(lr, weight_decay)` or `torch.optim.RMSprop(lr, weight_decay)`, torch defaults
+    otherwise; the decoder's from -optim, the encoder's and cva's from -optim_cnn (train.py:209-213);
   * `PolynomialLR` (utils/optimizer/scheduler.py:6-43) with power 0.9, min_lr 1e-5, step_size 1, no warm-up
     (train.py:226-262), stepped once per optimizer step;
-  * gradient accumulation: loss / accumulation_steps (train.py:115), update every accumulation_steps iterations;
+  * gradient accumulation: loss / accumulation_steps (train.py:115), update every accumulation_steps iterations (eager,
+    or replayed: GraphedTrainStep(accumulation_steps=k));
   * nn.DataParallel's gradient (grad of the mean loss over the global batch) == the mean over ranks of per-rank gradients
-    for equal shards: one sum all-reduce of the flat gradient buffer in buckets + the 1/world factor folded into AdamW.
+    for equal shards: one sum all-reduce of the flat gradient buffer in buckets + the 1/world factor folded into the update.
 """
 from typing import Dict, Iterable, List, Optional
 
@@ -45,26 +48,25 @@ def polynomial_lr(base_lr: float, current_lr: float, it: int, iter_max: int, pow
     return (base_lr - min_lr) * coef + min_lr
 
 
-class FlatAdamW:
-    """One parameter group of the reference's AdamW, held as flat fp32 buffers: the parameters are re-pointed at views
-    of `self.param`, their `.grad` at views of `self.grad`, so a step is ONE kernel over the group and the gradient
-    all-reduce runs over one contiguous buffer.  State layout (exp_avg, exp_avg_sq, step) matches torch.optim.AdamW."""
+class _FlatOptimizer:
+    """One parameter group held as flat fp32 buffers: the parameters are re-pointed at views of `self.param`, their `.grad` at
+    views of `self.grad`, so a step is ONE kernel over the group and the gradient all-reduce runs over one contiguous buffer.
+    Subclasses add their state buffers and the update (`_launch`, `_hyper`, `step_dev`) and torch's state_dict layout."""
+    KIND = ""          # the torch.optim class whose semantics and state_dict layout the subclass follows
+    HYPER = 8          # floats of step constants staged in device memory for hipGraph replay
 
-    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, weight_decay: float = 1e-2, betas=(0.9, 0.999),
-                 eps: float = 1e-8):
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float):
+        name = type(self).__name__
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
-            raise ValueError("FlatAdamW: empty parameter group")
+            raise ValueError(f"{name}: empty parameter group")
         dev = self.params[0].device      # buffers can be built anywhere; step() needs the GPU (the HIP kernel has no CPU twin)
         sizes = [(p.numel() + 3) // 4 * 4 for p in self.params]          # 16-B aligned slots
         self.offsets = [0]
         for s in sizes:
             self.offsets.append(self.offsets[-1] + s)
-        n = self.offsets[-1]
-        self.param = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.grad = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.exp_avg = torch.zeros(n, device=dev, dtype=torch.float32)
-        self.exp_avg_sq = torch.zeros(n, device=dev, dtype=torch.float32)
+        self.param = self._zeros()
+        self.grad = self._zeros()
         for p, o in zip(self.params, self.offsets):
             view = self._slot(self.param, p, o)
             view.copy_(p.data)
@@ -72,9 +74,11 @@ class FlatAdamW:
             p.grad = self._slot(self.grad, p, o)
             p._mumpy_flat_grad = p.grad           # marker: the backward kernels may accumulate into this view (autograd._grad_slot)
         self.base_lr = self.lr = lr
-        self.weight_decay, self.betas, self.eps = weight_decay, betas, eps
         self.steps = 0            # optimizer steps taken
         self.sched_it = 0         # scheduler steps taken (PolynomialLR.last_epoch)
+
+    def _zeros(self):
+        return torch.zeros(self.offsets[-1], device=self.params[0].device, dtype=torch.float32)
 
     @staticmethod
     def _slot(buf, p, o):
@@ -90,46 +94,49 @@ class FlatAdamW:
     def zero_grad(self):
         self.grad.zero_()
 
-    # ---- checkpointing: torch.optim.AdamW's state_dict layout, so a file written here reads like the reference's
+    # ---- checkpointing: torch.optim's own state_dict layout, so a file written here reads like the reference's
     # enc_opt_{e}.pt / dec_opt_{e}.pt (utils/utils.py:264-276) and vice versa; the counters torch keeps elsewhere
     # (scheduler position, base rate) ride in an extra "mumpy" entry that torch's loader ignores
-    def state_dict(self) -> dict:
-        state = {}
-        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
-            n = p.numel()
-            state[i] = {"step": torch.tensor(float(self.steps)), "exp_avg": self._slot(self.exp_avg, p, o).detach().contiguous().clone(),
-                        "exp_avg_sq": self._slot(self.exp_avg_sq, p, o).detach().contiguous().clone()}
-        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
-                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "params": list(range(len(self.params)))}
+    def _state_slot(self, buf, i):
+        return self._slot(buf, self.params[i], self.offsets[i]).detach().contiguous().clone()
+
+    def _sd(self, state: dict, group: dict) -> dict:
+        group["params"] = list(range(len(self.params)))
         return {"state": state, "param_groups": [group], "mumpy": {"steps": self.steps, "sched_it": self.sched_it, "base_lr": self.base_lr}}
 
-    def load_state_dict(self, sd: dict) -> None:
+    def _load_group(self, sd: dict) -> dict:
+        name = type(self).__name__
         groups = sd["param_groups"]
         if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
-            raise ValueError(f"FlatAdamW.load_state_dict: expected one group of {len(self.params)} parameters")
+            raise ValueError(f"{name}.load_state_dict: expected one group of {len(self.params)} parameters")
         g = groups[0]
-        self.lr, self.betas, self.eps, self.weight_decay = float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"])
-        steps = 0
-        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
-            st = sd["state"].get(i, sd["state"].get(str(i)))
-            n = p.numel()
-            if st is None:                                   # torch omits parameters that never received a gradient
-                self.exp_avg[o:o + n].zero_(); self.exp_avg_sq[o:o + n].zero_()
-                continue
-            if tuple(st["exp_avg"].shape) != tuple(p.shape):
-                raise ValueError(f"FlatAdamW.load_state_dict: parameter {i} has shape {tuple(p.shape)}, state {tuple(st['exp_avg'].shape)}")
-            self._slot(self.exp_avg, p, o).copy_(st["exp_avg"])
-            self._slot(self.exp_avg_sq, p, o).copy_(st["exp_avg_sq"])
-            steps = max(steps, int(float(st["step"])))
+        kind = "AdamW" if "betas" in g else "RMSprop" if "alpha" in g else "SGD" if "nesterov" in g else "an unknown optimizer"
+        if kind != self.KIND:
+            raise ValueError(f"{name}.load_state_dict: the state dict is from {kind}, not from {self.KIND}")
+        return g
+
+    def _load_counters(self, sd: dict, g: dict, steps: int) -> None:
         extra = sd.get("mumpy", {})
         self.steps = int(extra.get("steps", steps))          # (one step count per group: every parameter steps together here)
         self.sched_it = int(extra.get("sched_it", self.steps))
         self.base_lr = float(extra.get("base_lr", g.get("initial_lr", self.lr)))
 
+    def _load_slots(self, sd: dict, key: str, buf) -> None:
+        """Copy state[i][key] into buf's slots; a parameter without that state (torch omits parameters that never received a
+        gradient, and SGD keeps no state before its first step) gets zeros."""
+        name = type(self).__name__
+        for i, (p, o) in enumerate(zip(self.params, self.offsets)):
+            st = sd["state"].get(i, sd["state"].get(str(i)))
+            if st is None or key not in st:
+                buf[o:o + p.numel()].zero_()
+                continue
+            if tuple(st[key].shape) != tuple(p.shape):
+                raise ValueError(f"{name}.load_state_dict: parameter {i} has shape {tuple(p.shape)}, state {tuple(st[key].shape)}")
+            self._slot(buf, p, o).copy_(st[key])
+
     def all_reduce_grads(self, bucket_bytes: int = 64 << 20):
         """Sum all-reduce of the flat gradient in buckets (RCCL ring over xGMI: per-link bound, so a few tens of MB per
-        call keeps the ring busy without delaying the first bucket); returns the factor AdamW must apply (1/world)."""
+        call keeps the ring busy without delaying the first bucket); returns the factor the update must apply (1/world)."""
         if not (dist.is_available() and dist.is_initialized()) or \
                 (dist.get_world_size() == 1 and os.environ.get("MUMPY_FORCE_DIST", "0") != "1"):    # (forced: one-rank RCCL rehearsal)
             return 1.0
@@ -147,26 +154,20 @@ class FlatAdamW:
 
     def step(self, grad_scale: float = 1.0):
         self.steps += 1
-        ops.adamw_step(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.steps, self.lr, self.betas, self.eps,
-                       self.weight_decay, grad_scale)
+        self._launch(grad_scale)
         bump_weights_epoch()              # weight-derived caches (models.modules.layers.Derived) must be rebuilt
 
     # ---- hipGraph replay: the launch is frozen at capture, so the step-dependent constants live in device memory ----
     def enable_device_hyper(self):
-        self.hyper_dev = torch.zeros(8, device=self.param.device, dtype=torch.float32)
+        self.hyper_dev = torch.zeros(self.HYPER, device=self.param.device, dtype=torch.float32)
 
     def stage_hyper(self, grad_scale: float = 1.0, advance: bool = True):
         """Host side of a (captured) step: advance the step count and copy this step's constants to the device buffer.
         advance=False stages the constants of the NEXT step without counting it (used while capturing: nothing executes)."""
         if advance:
             self.steps += 1
-        self._hyper_host = ops.adamw_hyper(self.steps if advance else self.steps + 1, self.lr, self.betas, self.eps,
-                                           self.weight_decay, grad_scale)
+        self._hyper_host = self._hyper(self.steps if advance else self.steps + 1, grad_scale)
         self.hyper_dev.copy_(self._hyper_host, non_blocking=True)
-
-    def step_dev(self):
-        """Device side: the update with constants from `hyper_dev` (what gets captured)."""
-        ops.adamw_step_dev(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.hyper_dev)
 
     def scheduler_step(self, iter_max: int, power: float = 0.9, min_lr: float = 1e-5):
         self.sched_it += 1
@@ -174,36 +175,202 @@ class FlatAdamW:
         return self.lr
 
 
+class FlatAdamW(_FlatOptimizer):
+    """One parameter group of the reference's AdamW (utils/utils.py:258) on flat buffers.  State layout (exp_avg,
+    exp_avg_sq, step) matches torch.optim.AdamW."""
+    KIND = "AdamW"
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, weight_decay: float = 1e-2, betas=(0.9, 0.999),
+                 eps: float = 1e-8):
+        super().__init__(params, lr)
+        self.exp_avg = self._zeros()
+        self.exp_avg_sq = self._zeros()
+        self.weight_decay, self.betas, self.eps = weight_decay, betas, eps
+
+    def state_dict(self) -> dict:
+        state = {i: {"step": torch.tensor(float(self.steps)), "exp_avg": self._state_slot(self.exp_avg, i),
+                     "exp_avg_sq": self._state_slot(self.exp_avg_sq, i)} for i in range(len(self.params))}
+        group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None}
+        return self._sd(state, group)
+
+    def load_state_dict(self, sd: dict) -> None:
+        g = self._load_group(sd)
+        self.lr, self.betas, self.eps, self.weight_decay = float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"])
+        self._load_slots(sd, "exp_avg", self.exp_avg)
+        self._load_slots(sd, "exp_avg_sq", self.exp_avg_sq)
+        steps = max([int(float(st["step"])) for st in sd["state"].values()], default=0)
+        self._load_counters(sd, g, steps)
+
+    def _launch(self, grad_scale):
+        ops.adamw_step(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.steps, self.lr, self.betas, self.eps,
+                       self.weight_decay, grad_scale)
+
+    def _hyper(self, step, grad_scale):
+        return ops.adamw_hyper(step, self.lr, self.betas, self.eps, self.weight_decay, grad_scale)
+
+    def step_dev(self):
+        """Device side: the update with constants from `hyper_dev` (what gets captured)."""
+        ops.adamw_step_dev(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.hyper_dev)
+
+
+class FlatSGD(_FlatOptimizer):
+    """One parameter group of the reference's SGD (utils/utils.py:254: momentum 0.9, coupled weight decay, dampening 0)
+    on flat buffers.  The momentum buffer exists only when momentum != 0 (4 B per parameter against AdamW's 8).  State
+    layout (momentum_buffer; no state before the first step) matches torch.optim.SGD."""
+    KIND = "SGD"
+    HYPER = 4
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, weight_decay: float = 0.0, momentum: float = 0.0,
+                 nesterov: bool = False):
+        if nesterov and momentum <= 0:
+            raise ValueError("FlatSGD: Nesterov momentum requires a momentum")
+        super().__init__(params, lr)
+        self.weight_decay, self.momentum, self.nesterov = weight_decay, momentum, bool(nesterov)
+        self.momentum_buffer = self._zeros() if momentum != 0 else None
+        self._loaded_state = False      # a torch.optim.SGD file has momentum buffers but no step count
+
+    def state_dict(self) -> dict:
+        state = {}
+        if self.momentum_buffer is not None and (self.steps > 0 or self._loaded_state):
+            state = {i: {"momentum_buffer": self._state_slot(self.momentum_buffer, i)} for i in range(len(self.params))}
+        group = {"lr": self.lr, "momentum": self.momentum, "dampening": 0, "weight_decay": self.weight_decay,
+                 "nesterov": self.nesterov, "maximize": False, "foreach": None, "differentiable": False, "fused": None}
+        return self._sd(state, group)
+
+    def load_state_dict(self, sd: dict) -> None:
+        g = self._load_group(sd)
+        if float(g.get("dampening", 0)) != 0:
+            raise ValueError("FlatSGD.load_state_dict: dampening != 0 is not supported")
+        self.lr, self.momentum, self.weight_decay = float(g["lr"]), float(g["momentum"]), float(g["weight_decay"])
+        self.nesterov = bool(g["nesterov"])
+        if self.momentum == 0:
+            self.momentum_buffer = None
+        else:
+            if self.momentum_buffer is None:
+                self.momentum_buffer = self._zeros()
+            self._load_slots(sd, "momentum_buffer", self.momentum_buffer)
+        self._loaded_state = self.momentum_buffer is not None and bool(sd["state"])
+        self._load_counters(sd, g, 0)
+
+    def _launch(self, grad_scale):
+        ops.sgd_step(self.param, self.grad, self.momentum_buffer, self.lr, self.momentum, self.weight_decay, self.nesterov,
+                     grad_scale)
+
+    def _hyper(self, step, grad_scale):
+        return ops.sgd_hyper(self.lr, self.momentum, self.weight_decay, self.nesterov, grad_scale)
+
+    def step_dev(self):
+        ops.sgd_step_dev(self.param, self.grad, self.momentum_buffer, self.hyper_dev, self.nesterov)
+
+
+class FlatRMSprop(_FlatOptimizer):
+    """One parameter group of the reference's RMSprop (utils/utils.py:260, torch defaults otherwise; not centered) on flat
+    buffers.  State layout (step, square_avg, momentum_buffer when momentum > 0) matches torch.optim.RMSprop."""
+    KIND = "RMSprop"
+
+    def __init__(self, params: Iterable[torch.nn.Parameter], lr: float, weight_decay: float = 0.0, alpha: float = 0.99,
+                 eps: float = 1e-8, momentum: float = 0.0):
+        super().__init__(params, lr)
+        self.weight_decay, self.alpha, self.eps, self.momentum = weight_decay, alpha, eps, momentum
+        self.square_avg = self._zeros()
+        self.momentum_buffer = self._zeros() if momentum > 0 else None
+
+    def state_dict(self) -> dict:
+        state = {}
+        if self.steps > 0:
+            for i in range(len(self.params)):
+                state[i] = {"step": torch.tensor(float(self.steps)), "square_avg": self._state_slot(self.square_avg, i)}
+                if self.momentum_buffer is not None:
+                    state[i]["momentum_buffer"] = self._state_slot(self.momentum_buffer, i)
+        group = {"lr": self.lr, "momentum": self.momentum, "alpha": self.alpha, "eps": self.eps, "centered": False,
+                 "weight_decay": self.weight_decay, "capturable": False, "foreach": None, "maximize": False,
+                 "differentiable": False}
+        return self._sd(state, group)
+
+    def load_state_dict(self, sd: dict) -> None:
+        g = self._load_group(sd)
+        if g.get("centered", False):
+            raise ValueError("FlatRMSprop.load_state_dict: centered RMSprop is not supported")
+        self.lr, self.alpha, self.eps = float(g["lr"]), float(g["alpha"]), float(g["eps"])
+        self.weight_decay, self.momentum = float(g["weight_decay"]), float(g["momentum"])
+        self._load_slots(sd, "square_avg", self.square_avg)
+        if self.momentum > 0:
+            if self.momentum_buffer is None:
+                self.momentum_buffer = self._zeros()
+            self._load_slots(sd, "momentum_buffer", self.momentum_buffer)
+        else:
+            self.momentum_buffer = None
+        steps = max([int(float(st["step"])) for st in sd["state"].values()], default=0)
+        self._load_counters(sd, g, steps)
+
+    def _launch(self, grad_scale):
+        ops.rmsprop_step(self.param, self.grad, self.square_avg, self.momentum_buffer, self.lr, self.alpha, self.eps,
+                         self.weight_decay, self.momentum, grad_scale)
+
+    def _hyper(self, step, grad_scale):
+        return ops.rmsprop_hyper(self.lr, self.alpha, self.eps, self.weight_decay, self.momentum, grad_scale)
+
+    def step_dev(self):
+        ops.rmsprop_step_dev(self.param, self.grad, self.square_avg, self.momentum_buffer, self.hyper_dev)
+
+
+def get_optimizer(name: str, lr: float, params: Iterable[torch.nn.Parameter], weight_decay: float = 1e-4,
+                  momentum: float = 0.9) -> _FlatOptimizer:
+    """utils/utils.py:252-261: 'sgd' -> SGD(lr, weight_decay, momentum=0.9), 'adam' -> AdamW(lr, weight_decay),
+    'rmsprop' -> RMSprop(lr, weight_decay); torch defaults otherwise.  (The reference never passes `momentum` in, so
+    its SGD always runs at 0.9; an unknown name fails there with UnboundLocalError, here with ValueError.)"""
+    if name == "sgd":
+        return FlatSGD(params, lr, weight_decay=weight_decay, momentum=momentum)
+    if name == "adam":
+        return FlatAdamW(params, lr, weight_decay=weight_decay)
+    if name == "rmsprop":
+        return FlatRMSprop(params, lr, weight_decay=weight_decay)
+    raise ValueError(f"get_optimizer: unknown optimizer {name!r} (expected 'sgd', 'adam' or 'rmsprop')")
+
+
 def build_optimizers(encoder, decoder, lr_cnn: float, lr: float, lr_cva: Optional[float] = None, weight_decay: float = 1e-2,
-                     weight_decay_cnn: float = 1e-2) -> Dict[str, FlatAdamW]:
-    """train.py:211-213: cva / encoder / decoder optimizers (cva omitted when the encoder has no such parameters)."""
+                     weight_decay_cnn: float = 1e-2, optim: str = "adam", optim_cnn: str = "adam") -> Dict[str, _FlatOptimizer]:
+    """train.py:209-213: cva / encoder / decoder optimizers (cva omitted when the encoder has no such parameters); the
+    decoder's is built with `optim` (-optim), the encoder's and cva's with `optim_cnn` (-optim_cnn)."""
     g = split_param_groups(encoder, decoder)
-    opts = {"enc": FlatAdamW(g["enc"], lr_cnn, weight_decay_cnn), "dec": FlatAdamW(g["dec"], lr, weight_decay)}
+    opts = {"enc": get_optimizer(optim_cnn, lr_cnn, g["enc"], weight_decay_cnn),
+            "dec": get_optimizer(optim, lr, g["dec"], weight_decay)}
     if g["cva"]:
-        opts["cva"] = FlatAdamW(g["cva"], lr_cva if lr_cva is not None else lr_cnn, weight_decay)
+        opts["cva"] = get_optimizer(optim_cnn, lr_cva if lr_cva is not None else lr_cnn, g["cva"], weight_decay)
     return opts
 
 
 class GraphedTrainStep:
-    """One training step (taped forward, mask loss, backward, AdamW on every group, gradient reset) captured into a hipGraph
+    """One training step (taped forward, mask loss, backward, the update of every group, gradient reset) captured into a hipGraph
     and replayed: at config 5's micro-batch the eager step is bound by ~10^4 host-side launches, not by the GPU.
     `forward_fn(x) -> logits` must be built from mumpy_hip.autograd functions (capture-safe: no host synchronisation).
     Train mode works: the stochastic-depth masks are drawn by torch's graph-safe Philox generator inside the capture, so every
-    replay draws new ones (test_hip_graphed_train_step_draws_fresh_drop_path_masks).  Learning-rate schedules keep working: the AdamW constants
-    are staged into device memory before each replay.  Call `step(x, target)` -> loss3 (device tensor [total, iou, focal])."""
+    replay draws new ones (test_hip_graphed_train_step_draws_fresh_drop_path_masks).  Learning-rate schedules keep working: the
+    optimizers' constants are staged into device memory before each update.  Call `step(x, target)` -> loss3 (device tensor
+    [total, iou, focal])."""
 
-    def __init__(self, forward_fn, optimizers, x, target, warmup: int = 3, loss_scale: float = 1.0, all_reduce: bool = False):
-        """all_reduce=True (data-parallel ranks): TWO graphs -- forward + loss + backward, and AdamW + gradient reset -- with
-        the bucketed gradient all-reduce (RCCL) issued eagerly between their replays."""
+    def __init__(self, forward_fn, optimizers, x, target, warmup: int = 3, loss_scale: float = 1.0, all_reduce: bool = False,
+                 accumulation_steps: int = 1):
+        """all_reduce=True (data-parallel ranks): TWO graphs -- forward + loss + backward, and update + gradient reset -- with
+        the bucketed gradient all-reduce (RCCL) issued eagerly between their replays.
+        accumulation_steps=k > 1 (train.py:115-120): every step() is one micro-batch whose loss gradient is scaled by
+        loss_scale / k and accumulated in the flat gradient buffers; every k-th micro-batch (counted from the first warm-up
+        one) then runs the update graph (two graphs, as with all_reduce).  The warm-up covers at least one whole cycle."""
+        if accumulation_steps < 1:
+            raise ValueError(f"GraphedTrainStep: accumulation_steps must be >= 1, got {accumulation_steps}")
         self.opts = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
         self.x, self.target = x.clone(), target.clone()
         self.all_reduce = all_reduce
+        self.accumulation_steps = k = int(accumulation_steps)
+        self.iteration = 0                # micro-batches run (warm-up included): the reference's `iteration`
+        self._updated = False
         for o in self.opts:
             o.enable_device_hyper()
 
         def fwd_bwd():
             logits = forward_fn(self.x)
-            loss3, dlogits = ops.mask_loss(logits.detach(), self.target, loss_scale=loss_scale)
+            loss3, dlogits = ops.mask_loss(logits.detach(), self.target, loss_scale=loss_scale / k)
             logits.backward(dlogits)
             return loss3
 
@@ -216,9 +383,13 @@ class GraphedTrainStep:
         side = new_distinct_stream(self.x.device, (torch.cuda.current_stream().cuda_stream,))
         main = torch.cuda.current_stream()
         side.wait_stream(main)
-        for _ in range(warmup):                          # warm-up steps are real steps (caches, allocator, lazy inits)
+        for _ in range(warmup if k == 1 else max(warmup, k)):    # warm-up micro-batches are real ones (caches, allocator, lazy inits)
             with torch.cuda.stream(side):
                 fwd_bwd()
+            self._updated = self._due()
+            self.iteration += 1
+            if not self._updated:
+                continue
             scales = [1.0] * len(self.opts)
             if all_reduce:
                 # The collectives are issued from the CALLER's stream, never from the stream that captures: ProcessGroupNCCL's
@@ -240,7 +411,7 @@ class GraphedTrainStep:
             o.stage_hyper(advance=False)                 # capture records the launches; it does not run a step
         self.graph = torch.cuda.CUDAGraph()
         self.graph_update = None
-        if all_reduce:
+        if all_reduce or k > 1:
             with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):   # (same stream as the warm-up and thread-local capture errors: see GraphedForward._capture)
                 self.loss3 = fwd_bwd()
             self.graph_update = torch.cuda.CUDAGraph()
@@ -252,19 +423,33 @@ class GraphedTrainStep:
                 update()
         bump_weights_epoch()
 
+    def _due(self) -> bool:
+        return (self.iteration + 1) % self.accumulation_steps == 0
+
+    @property
+    def updated(self) -> bool:
+        """Whether the last step() (or the last warm-up micro-batch) ran the optimizer update."""
+        return self._updated
+
     def step(self, x=None, target=None, grad_scale: float = 1.0):
+        """One micro-batch: replay forward + loss + backward; on every accumulation_steps-th call also the all-reduce (if
+        all_reduce), the staged constants and the update.  -> loss3 = [total * loss_scale / k, iou, focal]."""
         if x is not None:
             self.x.copy_(x)
         if target is not None:
             self.target.copy_(target)
+        self._updated = self._due()
+        self.iteration += 1
         if self.graph_update is None:
             for o in self.opts:
                 o.stage_hyper(grad_scale)
             self.graph.replay()
         else:
             self.graph.replay()
-            for o in self.opts:
-                o.stage_hyper(grad_scale * o.all_reduce_grads())     # the step's collectives, on the replay's stream
-            self.graph_update.replay()
-        bump_weights_epoch()
+            if self._updated:
+                for o in self.opts:
+                    o.stage_hyper(grad_scale * (o.all_reduce_grads() if self.all_reduce else 1.0))   # the step's collectives, on the replay's stream
+                self.graph_update.replay()
+        if self._updated:
+            bump_weights_epoch()
         return self.loss3

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """One training step of the full three-view model (Encoder + Decoder) on the HIP kernels: taped forward, mask loss, backward,
 fused AdamW over the cva / encoder / decoder groups (train.py:94-138).  usage: train_full_bench.py [batch] [frames] [--bf16 | --x3 | --x2] [--graph]
+[--optim adam|sgd|rmsprop]
+--optim: the update of every group, as the reference's -optim / -optim_cnn pair (utils/utils.py:252-261; default adam).
 --x3: split-precision GEMMs / convolutions (fp32 products from three bf16 pieces per operand, fp32-level accuracy).
 --bf16: bf16-operand GEMMs / convolutions (fp32 accumulate, fp32 master weights, fp32 everything else) in forward and backward,
 i.e. config 5's matrix arithmetic; prints the gradient deviation from the fp32 step as well."""
@@ -14,7 +16,15 @@ from models.encoder.encoder import Encoder
 from mumpy_hip import ops
 from mumpy_hip.autograd import decoder_train, encoder_train
 from mumpy_hip.train import build_optimizers
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
+argv = sys.argv[1:]
+OPTIM = "adam"
+if "--optim" in argv:
+    i = argv.index("--optim")
+    OPTIM = argv[i + 1] if i + 1 < len(argv) else ""
+    del argv[i:i + 2]
+if OPTIM not in ("adam", "sgd", "rmsprop"):
+    sys.exit(f"--optim must be adam, sgd or rmsprop, not {OPTIM!r}")
+args = [a for a in argv if not a.startswith("--")]
 BF16 = "--bf16" in sys.argv
 MODE = "bf16x3" if "--x3" in sys.argv else "bf16x2" if "--x2" in sys.argv else "bf16"
 B = int(args[0]) if args else 2
@@ -22,7 +32,7 @@ T = int(args[1]) if len(args) > 1 else 5
 dev = torch.device("cuda:0")
 enc = fill_module_(Encoder(num_frames=T)).eval().to(dev)
 dec = fill_module_(Decoder(input_token_temporal_dims=[1, 1, T])).eval().to(dev)
-opts = build_optimizers(enc, dec, lr_cnn=1e-6, lr=1e-5, lr_cva=1e-6, weight_decay=1e-4, weight_decay_cnn=1e-4)
+opts = build_optimizers(enc, dec, lr_cnn=1e-6, lr=1e-5, lr_cva=1e-6, weight_decay=1e-4, weight_decay_cnn=1e-4, optim=OPTIM, optim_cnn=OPTIM)
 x = seeded_randn(1, B, T, 3, 224, 224).to(dev)
 target = (torch.rand(B, 1, 224, 224, device=dev) < 0.1).float()
 def step():
@@ -79,5 +89,5 @@ with torch.no_grad():
     e1.record(); torch.cuda.synchronize()
 inf = e0.elapsed_time(e1) / n
 nparam = sum(p.numel() for p in list(enc.parameters()) + list(dec.parameters()))
-print(f"full model train step ({ops.matrix_math()} matrix math), B={B}, T={T}: {ms:.1f} ms/step = {B / ms * 1e3:.1f} clips/s ({nparam / 1e6:.1f} M parameters, groups {sorted(opts)}); "
+print(f"full model train step ({ops.matrix_math()} matrix math, {OPTIM}), B={B}, T={T}: {ms:.1f} ms/step = {B / ms * 1e3:.1f} clips/s ({nparam / 1e6:.1f} M parameters, groups {sorted(opts)}); "
       f"eager inference forward {inf:.1f} ms -> step / forward = {ms / inf:.2f}; loss over 5 steps {[round(l, 4) for l in losses]}")
