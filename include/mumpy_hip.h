@@ -213,6 +213,17 @@ int mumpy_window_attention_bf16_fwd(const void* qkv, void* out, const float* bia
                                     const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift,
                                     float scale, void* stream);
 
+/* bf16 storage AND bf16 matrix math (opt-in; ops.set_attention_math("bf16")): Q K^T and P V run on
+ * v_mfma_f32_32x32x16_bf16 with fp32 accumulation, the softmax in fp32.  `scale` is applied to the fp32 scores AFTER the
+ * product (q is not re-rounded); the operand of P V is exp(s - max) rounded to bf16, unnormalised, and the fp32 product is
+ * divided by the fp32 row sum before the output is rounded.  Same arguments, validation and error codes as
+ * mumpy_window_attention_bf16_fwd.  Error bound against an exact softmax(q k^T scale + bias + mask) v of the same bf16
+ * operands: |out - exact| <= 2^-7 * vmax per element, vmax = the largest |v| of the element's (window, head, channel) column
+ * (one bf16 rounding of P, one of the output; tests/test_window_attention_bf16mm.py). */
+int mumpy_window_attention_bf16mm_fwd(const void* qkv, void* out, const float* bias, const float* mask_tab,
+                                      const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift,
+                                      float scale, void* stream);
+
 /* ---- Deformable cross-view attention (SwinDAttention, deform:324-405) — four kernels -------------- */
 
 /* offsets: q (B, H*W, C) raster, one frame per batch entry (t=1), gathered per 7x7 window.

@@ -88,7 +88,9 @@ __device__ __forceinline__ void qk_product(f32x16 (&s)[2], const f32x4 (&kf)[2][
 // add bias (+mask) rows and run the softmax over keys for the query column this lane owns (query i = 32*it + c).
 // MASKED is a compile-time switch: the caller branches once per unit on the (wave-uniform) mask pointer, so unmasked
 // windows run branch-free and a masked window issues its 7 mask loads back to back (one wait) instead of load-wait pairs.
-template <bool MASKED, typename BIAS>
+// NORMALISE = false leaves the exponentials e_j = exp(s_j - max) in s (their fp32 sum's reciprocal goes to *inv_out): the bf16-MFMA
+// kernel rounds those to bf16 and scales the product instead.
+template <bool MASKED, bool NORMALISE = true, typename BIAS>
 __device__ __forceinline__ void bias_softmax(f32x16 (&s)[2], BIAS bias_at, const float* mask_w, int i, int h,
                                              float post_scale, float* m_out = nullptr, float* inv_out = nullptr) {
     constexpr float NEG = -1e30f;
@@ -143,13 +145,15 @@ __device__ __forceinline__ void bias_softmax(f32x16 (&s)[2], BIAS bias_at, const
         }
     sum += __shfl_xor(sum, 32);
     const float inv = 1.0f / sum;
+    if (NORMALISE) {
 #pragma unroll
-    for (int jt = 0; jt < 2; ++jt)
+        for (int jt = 0; jt < 2; ++jt)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            if (jt == 1 && r >= 9) continue;
-            s[jt][r] *= inv;
-        }
+            for (int r = 0; r < 16; ++r) {
+                if (jt == 1 && r >= 9) continue;
+                s[jt][r] *= inv;
+            }
+    }
     if (m_out) { *m_out = m; *inv_out = inv; }
 }
 
@@ -368,6 +372,180 @@ __global__ __launch_bounds__(256, (NOLDS ? 4 : 3)) void win_attn_self_kernel(Sel
     };
     if (mask_w) tiles(std::true_type{}); else tiles(std::false_type{});
     __builtin_amdgcn_wave_barrier();   // the token tables are rewritten by the next unit
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// bf16-MFMA form of the self-attention unit for bf16-stored qkv (mumpy_window_attention_bf16mm_fwd; opt-in, see
+// ops.set_attention_math): both products on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, fp32 softmax.  Same unit
+// structure as win_attn_self_kernel<.., IO16>: one (window, head) unit per wave, persistent blocks of one head x 4 windows, the
+// head's bias table staged once in LDS, token tables, one branch per unit on the mask pointer.  What differs:
+//   * S^T = K Q^T: a head row is 32 bf16 = 64 B and lane (r, h) needs channels 16s + 8h .. +7 of row r for k-step s: ONE 16-byte
+//     load is the operand fragment, nothing is widened or converted.  2 key tiles x 2 query tiles x 2 k-steps = 8 MFMAs (fp32: 64).
+//   * scale is NOT folded into q (32^-0.5 is no power of two: a second rounding of q): it multiplies the fp32 scores,
+//     s * scale + bias (+ mask) -- this entry applies `scale` AFTER the product.
+//   * P is rounded to bf16 UNNORMALISED: the operand of P V is e_j = exp(s_j - max_j s) (in (0, 1], the largest exactly 1); the row
+//     sum is taken in fp32 over the unrounded e_j and its reciprocal scales the fp32 product before the output is rounded.
+//   * O = P^T-as-A . V: the accumulator tile S^T (query on the lane, key in the 16 registers) is the A operand with no lane
+//     movement: registers 8s .. 8s+7 of key tile jt, cast pairwise to bf16, are k-step (jt, s).  The k order inside a step is
+//     permuted: element j of lane half h is key 32jt + 16s + 8(j>>2) + 4h + (j&3), and the V fragment of lane (c, h) holds channel c
+//     of exactly those keys in that order (2-byte gathers packed in pairs).  2 query tiles x 4 k-steps = 8 MFMAs (fp32: 50).
+//     Key 48 is real (jt=1, s=1, j=0, h=0), so no k-step is dropped; keys >= 49 have e_j = 0 exactly and their V slots are slot 48's
+//     value (token table clamp) or zero: finite.
+//   * 1/sum lives on the query's LANE, O has the query in its REGISTERS: it crosses through 64 floats of LDS per wave (one
+//     ds_write_b32, four ds_read_b128 per tile).
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): 134 VGPRs, 0 AGPRs, 70 SGPRs, no scratch, no spills, 16,400 B of LDS per
+// block, 3 waves per SIMD.  (A form with the mask row folded into the bias row fits 128 VGPRs = 4 waves per SIMD without spills and
+// measured the same, 42.0 vs 41.3 us on the largest masked launch: the unit is not occupancy-bound, so the simpler form stays.)
+// Measured against the fp32-flow kernel on the same bf16 input (tools/kernel_micro.py winattn16; profiles/bf16mm_window_attention.md):
+//   (B, Hs, W, C)       shift 0: fp32 flow -> bf16 MFMA      shift 3: fp32 flow -> bf16 MFMA     [us per launch, MI355X, medians of 12 x 20
+//   (8, 280, 56, 128)     59.3 -> 38.9  (1.52x, 3.3 TB/s)      59.4 -> 41.5  (1.43x)               alternating launches; every shape of the
+//   (8, 140, 28, 256)     31.9 -> 21.6  (1.48x)                34.8 -> 23.7  (1.47x)               B=8, T=5 bf16-storage forward]
+//   (8,  70, 14, 512)     23.0 -> 14.4  (1.59x)                24.5 -> 16.0  (1.54x)
+//   (8,  56, 56,  96)     15.3 -> 10.4  (1.48x)                16.3 -> 10.7  (1.53x)
+//   (8,  35,  7, 1024)    14.3 -> 10.4  (1.37x)                 --
+//   (8,  28, 28, 192)     10.5 -> 10.5                         12.0 -> 12.1   } at ~10 us a launch in an eager loop these are paced by the
+//   (8,  14, 14, 384)     10.5 -> 10.0                         10.6 -> 10.6   } launch rate, not by the kernel: equal within the spread
+//   (8,   7,  7, 768)     10.0 -> 10.2                          --            } (+-0.5 us)
+// In the forward (rocprofv3 --kernel-trace, 60 launches): 18.4 -> 12.1 us average, 1.10 -> 0.72 ms per forward.  The largest launch moves
+// 128 MB in 38.9 us = 3.3 TB/s, half of what HBM sustains: MFMA time is gone (16 MFMAs per unit) and what remains is the issue of ~100
+// narrow memory instructions per unit (25 2-byte V gathers, 50 2-byte row-strided stores).  Neither 4 waves per SIMD nor the persistent
+// block count (512 .. 2560, MUMPY_WA16_BLOCKS in the tuning build) moves it.  Next step: V and O through an LDS transpose, 16-byte accesses.
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(256, 3) void win_attn_self_bf16mm_kernel(SelfArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tok_in[4][64];    // token * (3C*2): byte offset of the token's qkv row
+    __shared__ __attribute__((aligned(16))) uint32_t tok_out[4][64];   // token * (C*2):  byte offset of the token's out row
+    __shared__ __attribute__((aligned(16))) float inv_s[4][64];        // 1 / row sum of the unit's 64 query slots
+    __shared__ __attribute__((aligned(16))) float bias_s[WT * BLD];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int head = blockIdx.x % a.nH;
+    const int slot = blockIdx.x / a.nH;
+    const int64_t nwin = (int64_t)a.B * a.nW;
+    {
+        const float* bsrc = a.bias + (int64_t)head * 4096;
+        for (int idx = threadIdx.x; idx < WT * 16; idx += 256) {
+            const int row = idx >> 4, c4 = idx & 15;
+            *reinterpret_cast<f32x4*>(&bias_s[row * BLD + 4 * c4]) = *reinterpret_cast<const f32x4*>(bsrc + row * 64 + 4 * c4);
+        }
+        __syncthreads();
+    }
+    const int64_t L = (int64_t)a.Hs * a.W;
+    const uint32_t rsb = 6u * a.C, rob = 2u * a.C;                       // row strides in bytes
+    uint32_t* ti = tok_in[wave];
+    uint32_t* to = tok_out[wave];
+    float* invw = inv_s[wave];
+    for (int64_t bw = (int64_t)slot * 4 + wave; bw < nwin; bw += (int64_t)a.groups * 4) {   // all scalar
+        const int n = (int)(bw % a.nW);
+        const int64_t b = bw / a.nW;
+        const int wy = n / a.nWx, wx = n - wy * a.nWx;
+        {
+            const uint32_t tok = (uint32_t)window_token(wy, wx, lane < WT ? lane : WT - 1, a.Hs, a.W, a.shift);   // padded slots -> slot 48
+            ti[lane] = tok * rsb;
+            to[lane] = tok * rob;
+        }
+        __builtin_amdgcn_wave_barrier();
+        const char* base = reinterpret_cast<const char*>(reinterpret_cast<const __bf16*>(a.qkv) + b * L * 3 * a.C + head * HD);
+        const char* kbase = base + 2 * a.C;
+        const char* vbase = base + 4 * a.C;
+
+        // q / k: [tile][k-step] fragments, 16 bytes each, straight from memory
+        bf16x8 qf[2][2], kf[2][2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint32_t off = ti[32 * t + c] + 16u * h;
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                qf[t][st] = *reinterpret_cast<const bf16x8*>(base + (off + 32u * st));
+                kf[t][st] = *reinterpret_cast<const bf16x8*>(kbase + (off + 32u * st));
+            }
+        }
+        // v: [key tile][k-step] fragments in the permuted key order of the P operand; element j = key 32jt + 16s + 8(j>>2) + 4h + (j&3)
+        bf16x8 vf[2][2];
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int st = 0; st < 2; ++st) {
+                u16x8 pk = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    if (jt == 1 && st == 1 && q == 1) continue;                            // keys 56..63: all padding
+                    const u32x4 t4 = *reinterpret_cast<const u32x4*>(&ti[32 * jt + 16 * st + 8 * q + 4 * h]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (jt == 1 && st == 1 && e > 0) continue;                         // keys 49..51 / 53..55: padding in both halves
+                        pk[4 * q + e] = *reinterpret_cast<const uint16_t*>(vbase + (t4[e] + 2u * c));
+                    }
+                }
+                vf[jt][st] = __builtin_bit_cast(bf16x8, pk);
+            }
+
+        const float* mask_w = nullptr;
+        if (a.mask_id) {
+            const int id = a.mask_id[bw % a.n_mask];   // scalar load
+            if (id >= 0) mask_w = a.mask_tab + (int64_t)id * 4096;
+        }
+        char* obase = reinterpret_cast<char*>(reinterpret_cast<__bf16*>(a.out) + b * L * a.C + head * HD);
+        auto tiles = [&](auto masked) {
+            constexpr bool MASKED = decltype(masked)::value;
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                f32x16 s[2];
+#pragma unroll
+                for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[jt][r] = 0.f;
+#pragma unroll
+                for (int st = 0; st < 2; ++st)
+#pragma unroll
+                    for (int jt = 0; jt < 2; ++jt) s[jt] = mfma16(kf[jt][st], qf[it][st], s[jt]);   // S^T[jt] += K[jt] Q[it]^T
+                const int qi = 32 * it + c;
+                const float* brow = &bias_s[(qi < WT ? qi : WT - 1) * BLD + 4 * h];                  // padded queries re-read row 48
+                float m, inv;
+                bias_softmax<MASKED, false>(s, [&](int jt, int g) {
+                    f32x4 bv = *reinterpret_cast<const f32x4*>(brow + 32 * jt + 8 * g);
+                    if (jt == 1 && g == 2 && h) bv.x = -1e30f;                                      // key 52 is padding (key 48 is real)
+                    return bv;
+                }, mask_w, qi, h, a.scale, &m, &inv);
+                invw[qi] = inv;                                                                      // both lane halves hold the same value
+                f32x16 o;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) o[r] = 0.f;
+#pragma unroll
+                for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+                    for (int st = 0; st < 2; ++st) {
+                        bf16x8 pf;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) pf[j] = (__bf16)s[jt][8 * st + j];
+                        o = mfma16(pf, vf[jt][st], o);
+                    }
+                __builtin_amdgcn_wave_barrier();
+                // per register group g: the 4 consecutive queries 32it + 8g + 4h .. +3 -- their out-row offsets and 1/sum, one 16-byte read each
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    if (it == 1 && g == 3) continue;                                                 // queries 56..63: padding
+                    const u32x4 to4 = *reinterpret_cast<const u32x4*>(&to[32 * it + 8 * g + 4 * h]);
+                    const f32x4 iv = *reinterpret_cast<const f32x4*>(&invw[32 * it + 8 * g + 4 * h]);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        if (it == 1 && g == 2 && e > 0) continue;                                    // statically >= 49
+                        const int i = 32 * it + 8 * g + 4 * h + e;
+                        if (i < WT) *reinterpret_cast<__bf16*>(obase + (to4[e] + 2u * c)) = (__bf16)(o[4 * g + e] * iv[e]);
+                    }
+                }
+            }
+        };
+        if (mask_w) tiles(std::true_type{}); else tiles(std::false_type{});
+        __builtin_amdgcn_wave_barrier();   // the token tables are rewritten by the next unit
     }
 }
 
@@ -979,7 +1157,16 @@ static int window_attention_launch(int kind, const float* qkv, float* out, const
     a.groups = (int)groups; a.stagger = wa_stagger;
     const int64_t grid = groups * a.nH;
     const bool io16 = kind == 1;
-    if (kind == 2) hipLaunchKernelGGL((win_attn_self_kernel<false, false, true>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+    if (kind == 3) {
+        // bf16-MFMA kernel: 4 resident blocks per CU; the quads are dealt evenly (every block walks the same number of them, +-0)
+        static const int wa16_blocks = tune_int("MUMPY_WA16_BLOCKS", 1024);
+        int64_t g16 = (wa16_blocks + a.nH - 1) / a.nH;
+        if (g16 > quads) g16 = quads;
+        const int64_t per = (quads + g16 - 1) / g16;
+        g16 = (quads + per - 1) / per;
+        a.groups = (int)g16;
+        hipLaunchKernelGGL(win_attn_self_bf16mm_kernel, dim3((unsigned)(g16 * a.nH)), dim3(256), 0, as_stream(stream), a);
+    } else if (kind == 2) hipLaunchKernelGGL((win_attn_self_kernel<false, false, true>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     else if (io16) hipLaunchKernelGGL((win_attn_self_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     else if (dbgmask) hipLaunchKernelGGL((win_attn_self_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     else hipLaunchKernelGGL((win_attn_self_kernel<false, false>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
@@ -1006,6 +1193,15 @@ extern "C" int mumpy_window_attention_bf16_fwd(const void* qkv, void* out, const
                                                const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift,
                                                float scale, void* stream) {
     return window_attention_launch(1, static_cast<const float*>(qkv), static_cast<float*>(out), bias, mask_tab, mask_id, n_mask,
+                                   B, Hs, W, C, shift, scale, stream);
+}
+
+// bf16 storage AND bf16 matrix math: Q K^T and P V on the bf16 MFMA (fp32 accumulation, fp32 softmax, P re-quantised to bf16);
+// `scale` is applied to the fp32 scores after the product.  Same arguments, validation and error codes as the entry above.
+extern "C" int mumpy_window_attention_bf16mm_fwd(const void* qkv, void* out, const float* bias, const float* mask_tab,
+                                                 const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift,
+                                                 float scale, void* stream) {
+    return window_attention_launch(3, static_cast<const float*>(qkv), static_cast<float*>(out), bias, mask_tab, mask_id, n_mask,
                                    B, Hs, W, C, shift, scale, stream);
 }
 

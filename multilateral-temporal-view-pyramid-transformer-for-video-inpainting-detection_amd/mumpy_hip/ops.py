@@ -85,14 +85,47 @@ def linear_bf16s(x16, w16, bias=None, act=ACT_NONE, residual=None, out_bf16=True
     return out
 
 
-def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None):
-    """bf16 qkv (B, hs*w, 3C) -> bf16 (B, hs*w, C)."""
+def _attn_math_from_env() -> str:
+    mode = __import__("os").environ.get("MUMPY_ATTN_MATH", "") or "fp32"
+    if mode not in ("fp32", "bf16"):
+        raise ValueError(f"MUMPY_ATTN_MATH: unknown attention math mode {mode!r}")
+    return mode
+
+
+_ATTN_MATH = _attn_math_from_env()       # read once, at import
+
+
+def set_attention_math(mode: str) -> None:
+    """Arithmetic of the Swin window attention core when qkv is STORED as bf16 (set_storage("bf16")).  "fp32" (default): the bf16
+    values are widened and the unit runs the fp32 MFMA flow (mumpy_window_attention_bf16_fwd).  "bf16": Q K^T and P V run on
+    the bf16 MFMA with fp32 accumulation and an fp32 softmax (mumpy_window_attention_bf16mm_fwd; forward only).  fp32 qkv always
+    runs the fp32 kernels, and set_storage does not touch this switch.  The initial value is the environment variable
+    MUMPY_ATTN_MATH, read when this module is imported.  Like set_storage it is read at launch time: set it BEFORE a
+    GraphedForward is captured -- a captured graph keeps the kernels it was captured with."""
+    global _ATTN_MATH
+    if mode not in ("fp32", "bf16"):
+        raise ValueError(f"unknown attention math mode {mode!r}")
+    _ATTN_MATH = mode
+
+
+def attention_math() -> str:
+    return _ATTN_MATH
+
+
+def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, math=None):
+    """bf16 qkv (B, hs*w, 3C) -> bf16 (B, hs*w, C).  math: None follows attention_math(); "fp32" / "bf16" force the fp32-flow /
+    the bf16-MFMA kernel."""
+    if math is None:
+        math = _ATTN_MATH
+    elif math not in ("fp32", "bf16"):
+        raise ValueError(f"unknown attention math mode {math!r}")
     qkv16 = _chk16(qkv16, "qkv")
     if qkv16.numel() != b * hs * w * 3 * c:
         raise RuntimeError("window_attention_bf16: qkv shape mismatch")
     out = torch.empty(b, hs * w, c, device=qkv16.device, dtype=torch.bfloat16)
     n_mask = 0 if mask_id is None else mask_id.numel()
-    _call("mumpy_window_attention_bf16_fwd", _p(qkv16), _p(out), _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
+    _call("mumpy_window_attention_bf16mm_fwd" if math == "bf16" else "mumpy_window_attention_bf16_fwd", _p(qkv16), _p(out),
+          _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
           b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
     return out
 NEG = -1e30

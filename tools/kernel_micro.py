@@ -2,7 +2,9 @@
 """Launch one kernel shape repeatedly (for rocprofv3 --pmc / timing).
   kernel_micro.py linear M N K [act]      | kernel_micro.py winattn B Hs W C shift | kernel_micro.py sample B Hs2 W C
   | kernel_micro.py winattn_bwd B Hs W C shift | kernel_micro.py ln_bwd rows C
-  | kernel_micro.py adamw N | kernel_micro.py maskloss B P | kernel_micro.py ln rows C"""
+  | kernel_micro.py adamw N | kernel_micro.py maskloss B P | kernel_micro.py ln rows C
+  | kernel_micro.py winattn16 B Hs W C shift    bf16-stored qkv: the fp32-flow kernel and the bf16-MFMA kernel on the same input,
+                                                alternating in one process (ROUNDS rounds of REPS launches each, default 12 x 20)"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "multilateral-temporal-view-pyramid-transformer-for-video-inpainting-detection_amd")]
@@ -11,6 +13,34 @@ dev = torch.device("cuda:0")
 ops.set_matrix_math(os.environ.get("MUMPY_MATH", "fp32"))      # fp32 | bf16 | bf16x3 for the linear micro
 op, a = sys.argv[1], [int(v) for v in sys.argv[2:]]
 reps = int(os.environ.get("REPS", "20"))
+if op == "winattn16":
+    b, hs, w, c, shift = a
+    from models.modules.swinTransformer import build_shift_mask, relative_position_index
+    qkv16 = torch.randn(b, hs * w, 3 * c, device=dev).to(torch.bfloat16)
+    bias = ops.expand_relpos_bias(torch.randn(169, c // 32, device=dev) * 0.2, relative_position_index(7, 7).to(dev))
+    tab = ids = None
+    if shift:
+        tab, ids = ops.compact_attn_mask(build_shift_mask(hs, w, 7, shift).to(dev))
+    rounds = int(os.environ.get("ROUNDS", "12"))
+    times = {"fp32": [], "bf16": []}
+    for math in ("fp32", "bf16"):
+        for _ in range(5):
+            ops.window_attention_bf16(qkv16, bias, b, hs, w, c, shift, 32 ** -0.5, tab, ids, math=math)
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for math in ("fp32", "bf16"):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                ops.window_attention_bf16(qkv16, bias, b, hs, w, c, shift, 32 ** -0.5, tab, ids, math=math)
+            e1.record(); torch.cuda.synchronize()
+            times[math].append(e0.elapsed_time(e1) * 1e3 / reps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    gb = 2.0 * 4 * b * hs * w * c / 1e3            # bf16 q, k, v read + out written, per us -> GB/s
+    print(f"winattn16 {a}: fp32-flow {med['fp32']:.1f} us [{min(times['fp32']):.1f}..{max(times['fp32']):.1f}], "
+          f"bf16-MFMA {med['bf16']:.1f} us [{min(times['bf16']):.1f}..{max(times['bf16']):.1f}] ({gb / med['bf16']:.0f} GB/s), "
+          f"fp32/bf16 = {med['fp32'] / med['bf16']:.2f}  (median of {rounds} rounds x {reps} launches, alternating)")
+    sys.exit(0)
 if op == "linear":
     m, n, k = a[:3]; act = a[3] if len(a) > 3 else 0
     x = torch.randn(m, k, device=dev); w = torch.randn(n, k, device=dev) / k ** 0.5; b = torch.randn(n, device=dev)
