@@ -48,7 +48,14 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
         }                                                                            \
     } while (0)
 
-// Cross-lane all-reduce building blocks.  A butterfly from the low bit up: after the steps for 1 and 2 every lane of a quad
+// Workgroups are dealt round-robin over the 8 XCDs, each with its own L2: renumber workgroup `orig` of `nwg` XCD-major, so that
+// every XCD owns a contiguous run of the new ids (bijective form, cdna guide T1).
+__device__ __forceinline__ unsigned xcd_major_id(unsigned orig, unsigned nwg) {
+    const unsigned xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+}
+
+// Cross-lane all-reduce building blocks. A butterfly from the low bit up: after the steps for 1 and 2 every lane of a quad
 // holds the quad's sum, so the "xor 4" / "xor 8" partners can be ANY lane of the other quad / other half-row -- DPP's
 // row_half_mirror and row_mirror, which (like the quad permutes) fold into the v_add itself: one VALU instruction per step
 // instead of an address computation + ds_bpermute round trip (~100 cycles) per step.  xor 16 stays inside 32 lanes: ds_swizzle

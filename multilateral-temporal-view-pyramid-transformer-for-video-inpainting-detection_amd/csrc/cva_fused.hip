@@ -43,8 +43,7 @@ __global__ __launch_bounds__(256, 2) void deform_sample_kv_kernel(const float* _
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
     // XCD-major renumbering; the N tiles of one row panel are neighbours (they sample the same windows)
-    const unsigned nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const unsigned wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const unsigned wgid = xcd_major_id(blockIdx.x, gridDim.x);
     const unsigned tm = wgid / gn, tn = wgid - tm * gn;
     const int m0 = (int)tm * BM, n0 = (int)tn * BN;
     const int ld_row = tid >> 3, ld_c4 = tid & 7;
@@ -172,8 +171,7 @@ __global__ __launch_bounds__(256, 2) void deform_out_combine_kernel(const float*
     __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * LDR];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
-    const unsigned nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const unsigned wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const unsigned wgid = xcd_major_id(blockIdx.x, gridDim.x);
     const unsigned tn = wgid / gn, tm = wgid - tn * gn;           // the channel tiles of one o row panel are neighbours
     const int c0 = (int)tm * BM, m0 = (int)tn * BN;
     const int ld_row = tid >> 3, ld_c4 = tid & 7;

@@ -41,6 +41,7 @@
 //     through torch.addmm under the same hipGraph) moved the whole forward from 24.32 to 24.07 ms: in situ -- cold weights,
 //     co-scheduled branches, bias + residual no longer fused -- the isolated-kernel advantage does not carry over.
 #include <stdlib.h>
+#include <type_traits>
 #include "common.h"
 #include "gemm_ws.h"
 #include "gemm_ws64.h"
@@ -70,6 +71,46 @@ struct ConvGeom {
 // per-lane) and again on the fragment reads (cdna guide rule 21: swizzle both sides or neither).  Out-of-image conv taps
 // are fetched from a page of zeros.
 __device__ __attribute__((aligned(128))) float g_zero_page[32];
+
+// Output tile (tm, tn) and split-K slice ks of this block.  1-D grid, XCD-aware: blocks are dealt round-robin over the 8 XCDs,
+// so the id is remapped such that each XCD owns a contiguous run of the tile order (xcd_major_id).  The tile order itself is
+// (N-group, M, N-in-group) with NG tiles per group: the blocks resident on an XCD then share a few x row-panels and ONE narrow
+// slice of W, which stay in the 4 MiB L2.  (PMC before this ordering, M=7840 N=2048 K=512: 240 MB fetched for 20 MB of operands --
+// W was re-read from the Infinity Cache for every row panel; profiles/r01_pmc_traffic.md.)
+template <int BM, int BN>
+__device__ __forceinline__ void tile_of_block(int64_t M, unsigned gn, int ksplit, unsigned& tm, unsigned& tn, int& ks) {
+    constexpr unsigned NG = (BN >= 128) ? 4 : 8;
+    unsigned wgid = xcd_major_id(blockIdx.x, gridDim.x);
+    ks = (int)(wgid % (unsigned)ksplit);                 // K slice (split-K): slices of one tile run side by side
+    wgid /= (unsigned)ksplit;
+    const unsigned gm = (unsigned)((M + BM - 1) / BM);
+    const unsigned full = (gn / NG) * NG;                // tiles in complete N-groups
+    if (wgid < gm * full) {
+        const unsigned grp = wgid / (gm * NG), rem = wgid - grp * gm * NG;
+        tm = rem / NG;
+        tn = grp * NG + rem % NG;
+    } else {                                             // the last, narrower N-group
+        const unsigned wdt = gn - full, rem = wgid - gm * full;
+        tm = rem / wdt;
+        tn = full + rem % wdt;
+    }
+}
+
+// Convolution tap of the chunk at K index k0 (wave-uniform: scalar ALU): its offset (dy, dx) from the output pixel, the element
+// offset of its channels [c0, c0 + 32) from the pixel's own row pointer, and whether a staged pixel (ayx) has it inside the image.
+// (The LDS-DMA staging of linear_kernel keeps its own copy: sharing this one changed those kernels' register allocation.)
+struct ConvTap {
+    int dy, dx, off;
+    __device__ __forceinline__ bool inside(const ConvGeom& cg, int yx) const {
+        const int yy = (yx >> 16) + dy, xx = (yx & 0xffff) + dx;
+        return (unsigned)yy < (unsigned)cg.H && (unsigned)xx < (unsigned)cg.W;
+    }
+};
+__device__ __forceinline__ ConvTap conv_tap(const ConvGeom& cg, int k0) {
+    const int tap = k0 / cg.Cin, c0 = k0 - tap * cg.Cin;
+    const int dy = tap / cg.kw - cg.ph, dx = tap % cg.kw - cg.pw;
+    return {dy, dx, (dy * cg.W + dx) * cg.Cin + c0};
+}
 
 // epilogue shared by the fp32 and bf16-math kernels.  D[row][col]: col = lane&31, row = (r&3) + 8*(r>>2) + 4*h.
 // Addresses are a wave-uniform sub-tile base (SGPRs) plus a 32-bit element offset: row * N is a scalar multiply and the
@@ -145,28 +186,9 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM * BN > 64 * 64) ? 2
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, h = lane >> 5;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    // 1-D grid, XCD-aware: blocks are dealt round-robin over the 8 XCDs, so remap the id such that each XCD owns a
-    // contiguous run of the tile order (bijective form, cdna guide T1).  The tile order itself is (N-group, M, N-in-group)
-    // with NG tiles per group: the blocks resident on an XCD then share a few x row-panels and ONE narrow slice of W, which
-    // stay in the 4 MiB L2.  (PMC before this ordering, M=7840 N=2048 K=512: 240 MB fetched for 20 MB of operands --
-    // W was re-read from the Infinity Cache for every row panel; profiles/r01_pmc_traffic.md.)
-    constexpr unsigned NG = (BN >= 128) ? 4 : 8;
-    const unsigned nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    unsigned wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-    const int ks = (int)(wgid % (unsigned)ksplit);       // K slice (split-K): slices of one tile run side by side
-    wgid /= (unsigned)ksplit;
-    const unsigned gm = (unsigned)((M + BM - 1) / BM);
-    const unsigned full = (gn / NG) * NG;                // tiles in complete N-groups
     unsigned tm, tn;
-    if (wgid < gm * full) {
-        const unsigned grp = wgid / (gm * NG), rem = wgid - grp * gm * NG;
-        tm = rem / NG;
-        tn = grp * NG + rem % NG;
-    } else {                                             // the last, narrower N-group
-        const unsigned wdt = gn - full, rem = wgid - gm * full;
-        tm = rem / wdt;
-        tn = full + rem % wdt;
-    }
+    int ks;
+    tile_of_block<BM, BN>(M, gn, ksplit, tm, tn, ks);
     const int64_t m0 = (int64_t)tm * BM;
     const int n0 = (int)tn * BN;
     const int kbeg = ks * (K / ksplit);
@@ -239,14 +261,11 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM * BN > 64 * 64) ? 2
     };
     auto gload = [&](int k0) {                                   // global -> staging registers (16 B per lane)
         if (CONV) {
-            const int tap = k0 / cg.Cin, c0 = k0 - tap * cg.Cin;     // wave-uniform: scalar ALU
-            const int dy = tap / cg.kw - cg.ph, dx = tap % cg.kw - cg.pw;
-            const int off = (dy * cg.W + dx) * cg.Cin + c0;
+            const ConvTap t = conv_tap(cg, k0);
 #pragma unroll
             for (int i = 0; i < A_LD; ++i) {
-                const int yy = (ayx[i] >> 16) + dy, xx = (ayx[i] & 0xffff) + dx;
-                const bool ok = (unsigned)yy < (unsigned)cg.H && (unsigned)xx < (unsigned)cg.W;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(arow[i] + (ok ? off : 0));   // own pixel when outside
+                const bool ok = t.inside(cg, ayx[i]);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(arow[i] + (ok ? t.off : 0));   // own pixel when outside
                 areg[i] = ok ? v : f32x4{0, 0, 0, 0};
             }
         } else {
@@ -436,21 +455,9 @@ __global__ __launch_bounds__(256, 2) void linear_bf16_kernel(const float* __rest
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, h = lane >> 5;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    constexpr unsigned NG = (BN >= 128) ? 4 : 8;
-    const unsigned nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    unsigned wgid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-    const int ks = (int)(wgid % (unsigned)ksplit);
-    wgid /= (unsigned)ksplit;
-    const unsigned gm = (unsigned)((M + BM - 1) / BM);
-    const unsigned full = (gn / NG) * NG;
     unsigned tm, tn;
-    if (wgid < gm * full) {
-        const unsigned grp = wgid / (gm * NG), rem = wgid - grp * gm * NG;
-        tm = rem / NG; tn = grp * NG + rem % NG;
-    } else {
-        const unsigned wdt = gn - full, rem = wgid - gm * full;
-        tm = rem / wdt; tn = full + rem % wdt;
-    }
+    int ks;
+    tile_of_block<BM, BN>(M, gn, ksplit, tm, tn, ks);
     const int64_t m0 = (int64_t)tm * BM;
     const int n0 = (int)tn * BN;
     const int kbeg = ks * (K / ksplit);
@@ -502,14 +509,11 @@ __global__ __launch_bounds__(256, 2) void linear_bf16_kernel(const float* __rest
             return;
         }
         if (CONV) {
-            const int tap = k0 / cg.Cin, c0 = k0 - tap * cg.Cin;
-            const int dy = tap / cg.kw - cg.ph, dx = tap % cg.kw - cg.pw;
-            const int off = (dy * cg.W + dx) * cg.Cin + c0;
+            const ConvTap t = conv_tap(cg, k0);
 #pragma unroll
             for (int i = 0; i < A_LD; ++i) {
-                const int yy = (ayx[i] >> 16) + dy, xx = (ayx[i] & 0xffff) + dx;
-                const bool ok = (unsigned)yy < (unsigned)cg.H && (unsigned)xx < (unsigned)cg.W;
-                const f32x4 v = *reinterpret_cast<const f32x4*>(arow[i] + (ok ? off : 0));
+                const bool ok = t.inside(cg, ayx[i]);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(arow[i] + (ok ? t.off : 0));
                 areg[i] = ok ? v : f32x4{0, 0, 0, 0};
             }
         } else {
@@ -659,6 +663,15 @@ struct Plan {
 // prologue/epilogue.  When even the 64-tile grid leaves CUs idle and K is deep, K is split (slices >= 384).
 constexpr int NUM_CU = 256;
 
+// Largest split <= want with K slices >= min_slice deep, at most max_ks slices, and whole 32-chunks per slice (1: no split).
+int fit_ksplit(int K, int want, int min_slice, int max_ks) {
+    int ks = want;
+    if (ks > K / min_slice) ks = K / min_slice;
+    if (ks > max_ks) ks = max_ks;
+    while (ks > 1 && (K % (32 * ks)) != 0) --ks;
+    return ks < 1 ? 1 : ks;
+}
+
 // Split-precision (bf16x3) kernels, fitted to the same sweep (gpurun tools/gemm_shapes.py with MUMPY_MATH=bf16x3 and
 // MUMPY_GEMM_FORCE): the 128x128 tile (two co-resident blocks per CU = 512 slots) wins whenever K-splitting can bring its
 // grid to ~half the slots or more; below that the 64x64 tile (LDS-bound at three planes per operand) is the lesser evil.
@@ -667,13 +680,7 @@ Plan make_plan_x3(int64_t M, int N, int K, bool allow_split) {
     const int64_t gm128 = (M + 127) / 128, gm64 = (M + 63) / 64;
     const unsigned gn128 = (N + 127) / 128, gn64 = (N + 63) / 64;
     const int64_t b128 = gm128 * gn128, b64 = gm64 * gn64;
-    auto fit = [&](int ks) {                         // largest split <= ks with slices >= 384 deep and whole chunks
-        if (!allow_split) return 1;
-        if (ks > K / 384) ks = K / 384;
-        if (ks > 16) ks = 16;
-        while (ks > 1 && (K % (32 * ks)) != 0) --ks;
-        return ks < 1 ? 1 : ks;
-    };
+    auto fit = [&](int want) { return allow_split ? fit_ksplit(K, want, 384, 16) : 1; };      // slices >= 384 deep
     const int ksw = fit((int)((448 + b128 / 2) / b128));
     if (b128 * ksw >= 240) {
         p.tile = 0; p.ksplit = ksw; p.gm = gm128; p.gn = gn128;
@@ -703,13 +710,7 @@ Plan make_plan(int64_t M, int N, int K, bool allow_split, bool x3 = false) {
     int ks = 1;
     static const int min_slice = tune_int("MUMPY_GEMM_MINSLICE", 384), max_ks = tune_int("MUMPY_GEMM_MAXKS", 16),
                      min_k = tune_int("MUMPY_GEMM_SPLIT_MINK", 768);
-    if (tile == 2 && allow_split && b64 < 2 * NUM_CU && K >= min_k) {
-        ks = (int)((3 * NUM_CU + b64 - 1) / b64);
-        if (ks > K / min_slice) ks = K / min_slice;
-        if (ks > max_ks) ks = max_ks;
-        while (ks > 1 && (K % (32 * ks)) != 0) --ks;
-        if (ks < 1) ks = 1;
-    }
+    if (tile == 2 && allow_split && b64 < 2 * NUM_CU && K >= min_k) ks = fit_ksplit(K, (int)((3 * NUM_CU + b64 - 1) / b64), min_slice, max_ks);
     if (force) {
         int ft = -1, fk = -1;
         if (sscanf(force, "%d,%d", &ft, &fk) >= 1 && ft >= 0 && ft <= 3) {
@@ -763,30 +764,96 @@ int ws_plan(int64_t M, int N, int K, bool have_ws, bool conv) {
     return how;
 }
 
-int launch_linear(const float* x, const float* W, const float* bias, const float* residual, float* y, int64_t M, int N,
-                  int K, int act, float* ws, int64_t ws_bytes, hipStream_t s, int64_t rpb = 0, int64_t bstride = 0,
-                  const ConvGeom* conv = nullptr, bool ws_clean = false, const gemm_ws::LnArgs* ln = nullptr, int kseg = 0,
-                  int kstride = 0) {
-    if (rpb <= 0) { rpb = M; bstride = 0; }
+// One forward GEMM / implicit-GEMM convolution; every extern "C" entry point sets the fields it uses.
+struct LinearArgs {
+    const float *x, *W, *bias, *residual;
+    float* y;
+    int64_t M;
+    int N, K, act;                          // act: MUMPY_ACT_* | MUMPY_MATH_*
+    hipStream_t s;
+    float* ws = nullptr;                    // split-K slabs / the persistent kernel's flags + slabs
+    int64_t ws_bytes = 0;
+    bool ws_clean = false;                  // a kept workspace: its flag page is zero on entry (mumpy_linear_wsz_fwd)
+    int64_t rpb = 0, bstride = 0;           // rows mode: rows per block, block stride in floats (rpb = 0: dense)
+    int kseg = 0, kstride = 0;              // rows mode with a segmented contraction index (ConvGeom)
+    const ConvGeom* conv = nullptr;         // implicit-GEMM convolution
+    const gemm_ws::LnArgs* ln = nullptr;    // LayerNorm folding (mumpy_linear_lnx_fwd)
+};
+
+// What every tiled kernel is launched with.
+struct TiledArgs {
+    const float *x, *W, *bias, *residual;
+    float* y;
+    int64_t M;
+    int N, K, act;
+    unsigned gn;
+    int ksplit;
+    float* slab;
+    int64_t rpb, bstride;
+    ConvGeom cg;
+    int64_t grid;
+    hipStream_t s;
+};
+
+template <class Kern>
+void launch_tiled(Kern kern, unsigned threads, const TiledArgs& t) {
+    hipLaunchKernelGGL(kern, dim3((unsigned)t.grid), dim3(threads), 0, t.s, t.x, t.W, t.bias, t.residual, t.y, t.M, t.N, t.K, t.act,
+                       t.gn, t.ksplit, t.slab, t.rpb, t.bstride, t.cg);
+}
+
+// run-time flag -> template argument: f(std::true_type) or f(std::false_type)
+template <class F>
+void with_bool(bool b, F&& f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// fp32 products: Plan::tile x convolution x staging variant (glds: MUMPY_GEMM_GLDS, tuning build)
+void launch_tiled_fp32(int tile, bool conv, bool glds, const TiledArgs& t) {
+    with_bool(conv, [&](auto cv) {
+        constexpr bool CV = decltype(cv)::value;
+        if (tile == 3) return launch_tiled(linear_kernel<128, 128, 64, 64, CV, true, false>, 256, t);
+        with_bool(glds, [&](auto gl) {
+            constexpr bool GL = decltype(gl)::value;
+            if (tile == 0) launch_tiled(linear_kernel<128, 128, 64, 32, CV, GL>, 512, t);
+            else if (tile == 1) launch_tiled(linear_kernel<64, 128, 32, 64, CV, GL>, 256, t);
+            else launch_tiled(linear_kernel<64, 64, 32, 32, CV, GL>, 256, t);
+        });
+    });
+}
+
+// bf16 products of NP pieces per operand on the 128x128 (wide; one LDS buffer when NP > 1) or the 64x64 tile.
+// flag: a convolution, or -- IN16, bf16 storage, dense rows only -- a bf16 output.
+template <int NP, bool IN16 = false>
+void launch_tiled_bf16(bool wide, bool flag, const TiledArgs& t) {
+    with_bool(wide, [&](auto wd) {
+        with_bool(flag, [&](auto fl) {
+            constexpr int T = decltype(wd)::value ? 128 : 64, NBUF = (T == 128 && NP > 1) ? 1 : 2;
+            constexpr bool FL = decltype(fl)::value;
+            launch_tiled(linear_bf16_kernel<T, T, T / 2, T / 2, !IN16 && FL, NP, NBUF, IN16, IN16 && FL>, 256, t);
+        });
+    });
+}
+
+int launch_linear(const LinearArgs& a) {
+    const int64_t M = a.M, rpb = a.rpb > 0 ? a.rpb : M, bstride = a.rpb > 0 ? a.bstride : 0;
+    const int N = a.N, K = a.K, act = a.act & 0xff;
+    const ConvGeom* conv = a.conv;
     ConvGeom cg = conv ? *conv : ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, 0};
-    cg.kseg = kseg; cg.kstride = kstride;
-    const bool math_bf16 = (act & MUMPY_MATH_BF16) != 0;
-    const bool math_x2 = (act & MUMPY_MATH_BF16X2) != 0;
-    const bool math_x3 = (act & MUMPY_MATH_BF16X3) != 0 || math_x2;      // the two-piece mode shares the three-piece planner
-    act &= 0xff;
-    // Large dense fp32 shapes: the persistent wave-specialised kernel (gemm_ws.h).  MUMPY_GEMM_WS=0 disables it, =1 forces
-    // it for every eligible shape, =3 forces its split ("stream-K") schedule wherever a workspace is given (both: tuning).
-    // Default, fitted to same-device A/B runs of tools/gemm_shapes.py over the model's shapes: take it when whole 128x128
-    // tiles fill >= 86 % of the rounds they need (K >= 128), or -- with a workspace -- when an even split of the chunk
-    // sequence gives every CU >= 24 chunks and cuts a tile into <= 3 parts; leave the deep-K shapes with two or more tiles
-    // per CU to the tiled kernels (two co-resident workgroups hide each other's prologue and epilogue there: 121 TFLOP/s).
+    cg.kseg = a.kseg; cg.kstride = a.kstride;
+    const bool math_bf16 = (a.act & MUMPY_MATH_BF16) != 0;
+    const bool math_x2 = (a.act & MUMPY_MATH_BF16X2) != 0;
+    const bool math_x3 = (a.act & MUMPY_MATH_BF16X3) != 0 || math_x2;      // the two-piece mode shares the three-piece planner
+    float* ws = a.ws;
+    int64_t ws_bytes = a.ws_bytes;
+    // Large dense fp32 shapes: the persistent wave-specialised kernel (gemm_ws.h) wherever ws_plan takes the shape.
     const gemm_ws::Conv cvd{cg.H, cg.W, cg.Cin, cg.kh, cg.kw};
-    if (ln && (rpb < M || math_bf16 || math_x3 || conv || !gemm_ws::eligible(M, N, K) ||
-               !ws_plan(M, N, K, ws && ws_bytes >= gemm_ws::workspace_bytes(device_cus()), false))) {
+    if (a.ln && (rpb < M || math_bf16 || math_x3 || conv || !gemm_ws::eligible(M, N, K) ||
+                 !ws_plan(M, N, K, ws && ws_bytes >= gemm_ws::workspace_bytes(device_cus()), false))) {
         set_error("linear: LayerNorm folding needs a shape the persistent 128x128 kernel takes (mumpy_linear_ln_tiles) in fp32 mode");
         return MUMPY_EINVAL;
     }
-    if (rpb >= M && !kseg && !math_bf16 && !math_x3 && (conv ? gemm_ws::conv_eligible(M, N, cvd) : gemm_ws::eligible(M, N, K))) {
+    if (rpb >= M && !a.kseg && !math_bf16 && !math_x3 && (conv ? gemm_ws::conv_eligible(M, N, cvd) : gemm_ws::eligible(M, N, K))) {
         const int num_cu = device_cus();
         const bool have_ws = ws && ws_bytes >= gemm_ws::workspace_bytes(num_cu);
         const int how = ws_plan(M, N, K, have_ws, conv != nullptr);           // 0: tiled kernels, 1: whole tiles, 2: split
@@ -802,14 +869,14 @@ int launch_linear(const float* x, const float* W, const float* bias, const float
             const double r64 = (double)t64 / (2.0 * num_cu);
             const bool fits = ws64_mode == 2 || (act != MUMPY_ACT_GELU && nk <= 32 && t64 >= 64 && (r64 <= 1.0 || r64 >= 2.5 || nk <= 12));
             if (fits) {
-                if (int rc = gemm_ws64::launch(x, W, bias, residual, y, M, N, K, act, num_cu, s)) return rc;
+                if (int rc = gemm_ws64::launch(a.x, a.W, a.bias, a.residual, a.y, M, N, K, act, num_cu, a.s)) return rc;
                 MUMPY_CHECK_LAUNCH("linear(ws64)");
                 return 0;
             }
         }
         if (how) {
-            if (int rc = gemm_ws::launch(x, W, bias, residual, y, M, N, K, act, num_cu, s, ws, ws_bytes, how == 2 ? 1 : 0, nullptr, ws_clean,
-                                         conv ? &cvd : nullptr, ln)) return rc;
+            if (int rc = gemm_ws::launch(a.x, a.W, a.bias, a.residual, a.y, M, N, K, act, num_cu, a.s, ws, ws_bytes, how == 2 ? 1 : 0, nullptr,
+                                         a.ws_clean, conv ? &cvd : nullptr, a.ln)) return rc;
             MUMPY_CHECK_LAUNCH("linear(ws)");
             return 0;
         }
@@ -821,69 +888,19 @@ int launch_linear(const float* x, const float* W, const float* bias, const float
     if (p.ksplit > 1 && (int64_t)p.ksplit * M * N * (int64_t)sizeof(float) > ws_bytes) p.ksplit = 1;
     const int64_t grid = p.gm * p.gn * p.ksplit;
     MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "linear: too many tiles");
-#define MUMPY_GEMM(BM_, BN_, WM_, WN_, CV_)                                                                        \
-    if (use_glds)                                                                                                  \
-        hipLaunchKernelGGL((linear_kernel<BM_, BN_, WM_, WN_, CV_, true>), dim3((unsigned)grid),                     \
-                           dim3(64 * (BM_ / WM_) * (BN_ / WN_)), 0, s, x, W, bias, residual, y, M, N, K, act, p.gn,  \
-                           p.ksplit, ws, rpb, bstride, cg);                                               \
-    else                                                                                                           \
-    hipLaunchKernelGGL((linear_kernel<BM_, BN_, WM_, WN_, CV_, false>), dim3((unsigned)grid),                        \
-                       dim3(64 * (BM_ / WM_) * (BN_ / WN_)), 0, s, x, W, bias, residual, y, M, N, K, act, p.gn, p.ksplit, \
-                       ws, rpb, bstride, cg)
     static const bool use_glds = tune_int("MUMPY_GEMM_GLDS", 0) != 0;
-    if (math_x3) {
-        const bool wide = (p.tile == 0 || p.tile == 3);
-#define MUMPY_GEMM_X3(BM_, BN_, WM_, WN_, CV_, NB_)                                                                    \
-    hipLaunchKernelGGL((linear_bf16_kernel<BM_, BN_, WM_, WN_, CV_, 3, NB_>), dim3((unsigned)grid), dim3(256), 0, s, x, W, \
-                       bias, residual, y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg)
-#define MUMPY_GEMM_X2(BM_, BN_, WM_, WN_, CV_, NB_)                                                                    \
-    hipLaunchKernelGGL((linear_bf16_kernel<BM_, BN_, WM_, WN_, CV_, 2, NB_>), dim3((unsigned)grid), dim3(256), 0, s, x, W, \
-                       bias, residual, y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg)
-        if (math_x2) {
-            if (wide && conv) MUMPY_GEMM_X2(128, 128, 64, 64, true, 1);
-            else if (wide) MUMPY_GEMM_X2(128, 128, 64, 64, false, 1);
-            else if (conv) MUMPY_GEMM_X2(64, 64, 32, 32, true, 2);
-            else MUMPY_GEMM_X2(64, 64, 32, 32, false, 2);
-        }
-        else if (wide && conv) MUMPY_GEMM_X3(128, 128, 64, 64, true, 1);
-        else if (wide) MUMPY_GEMM_X3(128, 128, 64, 64, false, 1);
-        else if (conv) MUMPY_GEMM_X3(64, 64, 32, 32, true, 2);
-        else MUMPY_GEMM_X3(64, 64, 32, 32, false, 2);
-#undef MUMPY_GEMM_X3
-#undef MUMPY_GEMM_X2
-    } else if (math_bf16) {
-        const bool wide = (p.tile == 0 || p.tile == 3);
-#define MUMPY_GEMM_H(BM_, BN_, WM_, WN_, CV_)                                                                          \
-    hipLaunchKernelGGL((linear_bf16_kernel<BM_, BN_, WM_, WN_, CV_>), dim3((unsigned)grid), dim3(256), 0, s, x, W, bias,   \
-                       residual, y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg)
-        if (wide && conv) MUMPY_GEMM_H(128, 128, 64, 64, true);
-        else if (wide) MUMPY_GEMM_H(128, 128, 64, 64, false);
-        else if (conv) MUMPY_GEMM_H(64, 64, 32, 32, true);
-        else MUMPY_GEMM_H(64, 64, 32, 32, false);
-#undef MUMPY_GEMM_H
-    } else if (p.tile == 3) {
-        if (conv)
-            hipLaunchKernelGGL((linear_kernel<128, 128, 64, 64, true, true, false>), dim3((unsigned)grid), dim3(256), 0, s, x, W,
-                               bias, residual, y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg);
-        else
-            hipLaunchKernelGGL((linear_kernel<128, 128, 64, 64, false, true, false>), dim3((unsigned)grid), dim3(256), 0, s, x, W,
-                               bias, residual, y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg);
-    } else if (conv) {
-        if (p.tile == 0) MUMPY_GEMM(128, 128, 64, 32, true);
-        else if (p.tile == 1) MUMPY_GEMM(64, 128, 32, 64, true);
-        else MUMPY_GEMM(64, 64, 32, 32, true);
-    } else {
-        if (p.tile == 0) MUMPY_GEMM(128, 128, 64, 32, false);
-        else if (p.tile == 1) MUMPY_GEMM(64, 128, 32, 64, false);
-        else MUMPY_GEMM(64, 64, 32, 32, false);
-    }
-#undef MUMPY_GEMM
+    const bool wide = (p.tile == 0 || p.tile == 3);
+    const TiledArgs t{a.x, a.W, a.bias, a.residual, a.y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg, grid, a.s};
+    if (math_x2) launch_tiled_bf16<2>(wide, conv != nullptr, t);
+    else if (math_x3) launch_tiled_bf16<3>(wide, conv != nullptr, t);
+    else if (math_bf16) launch_tiled_bf16<1>(wide, conv != nullptr, t);
+    else launch_tiled_fp32(p.tile, conv != nullptr, use_glds, t);
     MUMPY_CHECK_LAUNCH("linear");
     if (p.ksplit > 1) {
         const int64_t mn4 = M * N / 4;
         int64_t g = (mn4 + 255) / 256;
         if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, s, ws, bias, residual, y, mn4, N,
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, a.s, ws, a.bias, a.residual, a.y, mn4, N,
                            p.ksplit, act);
         MUMPY_CHECK_LAUNCH("linear(split-K reduce)");
     }
@@ -892,27 +909,37 @@ int launch_linear(const float* x, const float* W, const float* bias, const float
 
 }  // namespace
 
-static int check_linear_args(const float* x, const float* W, const float* residual, const float* y, int64_t M, int N,
+// who: the message prefix ("linear", "linear_bf16s")
+static int check_linear_args(const char* who, const void* x, const void* W, const float* residual, const void* y, int64_t M, int N,
                              int K, int act) {
-    MUMPY_REQUIRE(x && W && y, MUMPY_ENULL, "linear: null pointer");
+    MUMPY_REQUIRE(x && W && y, MUMPY_ENULL, "%s: null pointer", who);
     MUMPY_REQUIRE(aligned16(x) && aligned16(W) && aligned16(y) && aligned16(residual), MUMPY_EALIGN,
-                  "linear: pointers must be 16-byte aligned");
+                  "%s: pointers must be 16-byte aligned", who);
     MUMPY_REQUIRE(M < (1ll << 31) - 256 && (int64_t)N * 4 * 128 < (1ll << 32), MUMPY_ERANGE,
-                  "linear: M=%lld rows / N=%d columns beyond the 32-bit row index / tile byte offsets", (long long)M, N);
+                  "%s: M=%lld rows / N=%d columns beyond the 32-bit row index / tile byte offsets", who, (long long)M, N);
     MUMPY_REQUIRE(M >= 0 && N > 0 && K > 0 && K % BK == 0 && N % 32 == 0, MUMPY_EINVAL,
-                  "linear: need K %% 32 == 0 and N %% 32 == 0 (got M=%lld N=%d K=%d)", (long long)M, N, K);
-    MUMPY_REQUIRE((act & 0xff) == MUMPY_ACT_NONE || (act & 0xff) == MUMPY_ACT_GELU, MUMPY_EINVAL, "linear: unknown act %d", act);
+                  "%s: need K %% 32 == 0 and N %% 32 == 0 (got M=%lld N=%d K=%d)", who, (long long)M, N, K);
+    MUMPY_REQUIRE((act & 0xff) == MUMPY_ACT_NONE || (act & 0xff) == MUMPY_ACT_GELU, MUMPY_EINVAL, "%s: unknown act %d", who, act);
     constexpr int math_bits = MUMPY_MATH_BF16 | MUMPY_MATH_BF16X3 | MUMPY_MATH_BF16X2;
-    MUMPY_REQUIRE((act & ~(0xff | math_bits)) == 0, MUMPY_EINVAL, "linear: unknown flag bits in act 0x%x", act);
-    MUMPY_REQUIRE(((act & math_bits) & ((act & math_bits) - 1)) == 0, MUMPY_EINVAL, "linear: the MUMPY_MATH_* modes are exclusive");
+    MUMPY_REQUIRE((act & ~(0xff | math_bits)) == 0, MUMPY_EINVAL, "%s: unknown flag bits in act 0x%x", who, act);
+    MUMPY_REQUIRE(((act & math_bits) & ((act & math_bits) - 1)) == 0, MUMPY_EINVAL, "%s: the MUMPY_MATH_* modes are exclusive", who);
     return 0;
+}
+
+// the arguments shared by the fp32-storage entry points; a null workspace has no bytes
+static LinearArgs linear_args(const float* x, const float* W, const float* bias, const float* residual, float* y, int64_t M, int N,
+                              int K, int act, void* workspace, int64_t workspace_bytes, void* stream) {
+    LinearArgs a{x, W, bias, residual, y, M, N, K, act, as_stream(stream)};
+    a.ws = static_cast<float*>(workspace);
+    a.ws_bytes = workspace ? workspace_bytes : 0;
+    return a;
 }
 
 extern "C" int mumpy_linear_fwd(const float* x, const float* W, const float* bias, const float* residual, float* y,
                                 int64_t M, int N, int K, int act, void* stream) {
     if (M == 0) return 0;      // empty batch
-    if (int rc = check_linear_args(x, W, residual, y, M, N, K, act)) return rc;
-    return launch_linear(x, W, bias, residual, y, M, N, K, act, nullptr, 0, as_stream(stream));
+    if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
+    return launch_linear(linear_args(x, W, bias, residual, y, M, N, K, act, nullptr, 0, stream));
 }
 
 extern "C" int64_t mumpy_linear_workspace_bytes(int64_t M, int N, int K) {
@@ -934,65 +961,45 @@ extern "C" int mumpy_linear_ws_fwd(const float* x, const float* W, const float* 
                                    int64_t M, int N, int K, int act, void* workspace, int64_t workspace_bytes,
                                    void* stream) {
     if (M == 0) return 0;
-    if (int rc = check_linear_args(x, W, residual, y, M, N, K, act)) return rc;
+    if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
     MUMPY_REQUIRE(aligned16(workspace), MUMPY_EALIGN, "linear: workspace must be 16-byte aligned");
-    return launch_linear(x, W, bias, residual, y, M, N, K, act, static_cast<float*>(workspace),
-                         workspace ? workspace_bytes : 0, as_stream(stream));
+    return launch_linear(linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream));
 }
 
 // bf16 STORAGE (config 3 as written): x (M,K) and W (N,K) bf16, bias / residual fp32, y bf16 (out_bf16 != 0) or fp32.
 extern "C" int mumpy_linear_bf16s_fwd(const void* x, const void* W, const float* bias, const float* residual, void* y,
                                       int64_t M, int N, int K, int act, int out_bf16, void* stream) {
     if (M == 0) return 0;
-    MUMPY_REQUIRE(x && W && y, MUMPY_ENULL, "linear_bf16s: null pointer");
-    MUMPY_REQUIRE(aligned16(x) && aligned16(W) && aligned16(y) && aligned16(residual), MUMPY_EALIGN,
-                  "linear_bf16s: pointers must be 16-byte aligned");
-    MUMPY_REQUIRE(M > 0 && M < (1ll << 31) - 256 && (int64_t)N * 4 * 128 < (1ll << 32), MUMPY_ERANGE, "linear_bf16s: M=%lld / N=%d out of range", (long long)M, N);
-    MUMPY_REQUIRE(N > 0 && K > 0 && K % BK == 0 && N % 32 == 0, MUMPY_EINVAL, "linear_bf16s: need K %% 32 == 0 and N %% 32 == 0 (got N=%d K=%d)", N, K);
-    MUMPY_REQUIRE(act == MUMPY_ACT_NONE || act == MUMPY_ACT_GELU, MUMPY_EINVAL, "linear_bf16s: unknown act %d", act);
-    const float* xf = static_cast<const float*>(x);
-    const float* wf = static_cast<const float*>(W);
-    float* yf = static_cast<float*>(y);
-    const ConvGeom cg{0, 0, 0, 0, 0, 0, 0, 0, 0};
-    hipStream_t s = as_stream(stream);
+    if (int rc = check_linear_args("linear_bf16s", x, W, residual, y, M, N, K, act)) return rc;
+    MUMPY_REQUIRE((act & ~0xff) == 0, MUMPY_EINVAL, "linear_bf16s: unknown act %d", act);
     MUMPY_REQUIRE(!(out_bf16 && residual), MUMPY_EINVAL, "linear_bf16s: a bf16 output takes no residual");
+    hipStream_t s = as_stream(stream);
     // every eligible shape (K % 64 == 0, K >= 192): the persistent wave-specialised kernel with bf16 stages (gemm_ws.h).  With
     // 512 matrix-pipe cycles per chunk even a launch of 40 tiles is latency-bound, and the DMA pipeline of that kernel beats
     // the tiled kernel's load -> convert -> LDS loop everywhere (forward of config 3: 725 -> 797 clips/s against taking it
     // only for >= 0.75 of a round of tiles).  MUMPY_GEMM_WS16=0 disables it, =1 restricts it to the large shapes (A/B runs).
-    {
-        static const int ws16 = tune_int("MUMPY_GEMM_WS16", 2);
-        static int num_cu = 0;
-        if (!num_cu) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) num_cu = prop.multiProcessorCount;
-            else num_cu = NUM_CU;
-        }
-        const int64_t tiles = ((M + 127) / 128) * ((N + 127) / 128);
+    static const int ws16 = tune_int("MUMPY_GEMM_WS16", 2);
+    const int64_t gm128 = (M + 127) / 128, gm64 = (M + 63) / 64;
+    const unsigned gn128 = (N + 127) / 128, gn64 = (N + 63) / 64;
+    if (ws16 && gemm_ws::eligible16(M, N, K)) {
+        const int num_cu = device_cus();
+        const int64_t tiles = gm128 * gn128;
         const double rounds = (double)tiles / num_cu, eff = rounds / (double)((tiles + num_cu - 1) / num_cu);
-        if (ws16 && gemm_ws::eligible16(M, N, K) && (ws16 == 2 || (tiles >= (int64_t)(0.75 * num_cu) && eff >= 0.75))) {
+        if (ws16 == 2 || (tiles >= (int64_t)(0.75 * num_cu) && eff >= 0.75)) {
             if (int rc = gemm_ws::launch16(x, W, bias, residual, y, M, N, K, act, out_bf16 != 0, num_cu, s)) return rc;
             MUMPY_CHECK_LAUNCH("linear_bf16s(ws)");
             return 0;
         }
     }
-    const int64_t gm128 = (M + 127) / 128, gm64 = (M + 63) / 64;
-    const unsigned gn128 = (N + 127) / 128, gn64 = (N + 63) / 64;
     // the products take 1/16 of the fp32 MFMA time: these launches are staging-bound, so prefer the wide tile (half the
     // operand traffic per FLOP) as soon as it yields about a round of workgroups
     const bool wide = gm128 * gn128 >= 200;
     const unsigned gn = wide ? gn128 : gn64;
     const int64_t grid = (wide ? gm128 : gm64) * gn;
     MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "linear_bf16s: too many tiles");
-#define MUMPY_GEMM_S(BM_, BN_, WM_, WN_, O16_)                                                                             \
-    hipLaunchKernelGGL((linear_bf16_kernel<BM_, BN_, WM_, WN_, false, 1, 2, true, O16_>), dim3((unsigned)grid), dim3(256), 0, s, \
-                       xf, wf, bias, residual, yf, M, N, K, act, gn, 1, nullptr, M, (int64_t)0, cg)
-    if (wide && out_bf16) MUMPY_GEMM_S(128, 128, 64, 64, true);
-    else if (wide) MUMPY_GEMM_S(128, 128, 64, 64, false);
-    else if (out_bf16) MUMPY_GEMM_S(64, 64, 32, 32, true);
-    else MUMPY_GEMM_S(64, 64, 32, 32, false);
-#undef MUMPY_GEMM_S
+    const TiledArgs t{static_cast<const float*>(x), static_cast<const float*>(W), bias, residual, static_cast<float*>(y), M, N, K, act,
+                      gn, 1, nullptr, M, 0, ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, 0}, grid, s};
+    launch_tiled_bf16<1, true>(wide, out_bf16 != 0, t);
     MUMPY_CHECK_LAUNCH("linear_bf16s");
     return 0;
 }
@@ -1004,10 +1011,11 @@ extern "C" int mumpy_linear_wsz_fwd(const float* x, const float* W, const float*
                                     int64_t M, int N, int K, int act, void* workspace, int64_t workspace_bytes,
                                     void* stream) {
     if (M == 0) return 0;
-    if (int rc = check_linear_args(x, W, residual, y, M, N, K, act)) return rc;
+    if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
     MUMPY_REQUIRE(aligned16(workspace), MUMPY_EALIGN, "linear: workspace must be 16-byte aligned");
-    return launch_linear(x, W, bias, residual, y, M, N, K, act, static_cast<float*>(workspace),
-                         workspace ? workspace_bytes : 0, as_stream(stream), 0, 0, nullptr, true);
+    LinearArgs a = linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream);
+    a.ws_clean = true;
+    return launch_linear(a);
 }
 
 // Sticky status of a kept workspace (blocking: copies one word back).  0 = fine; b + 1 = the owner of a split tile gave up waiting
@@ -1035,7 +1043,7 @@ extern "C" int mumpy_linear_lnx_fwd(const float* x, const float* W, const float*
                                     int N, int K, int act, void* workspace, int64_t workspace_bytes, float* stats_out,
                                     const float* ln_stats, int ln_gn, const float* ln_colsum, float ln_eps, void* stream) {
     if (M == 0) return 0;
-    if (int rc = check_linear_args(x, W, residual, y, M, N, K, act)) return rc;
+    if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
     MUMPY_REQUIRE((act & ~0xff) == 0, MUMPY_EINVAL, "linear_lnx: fp32 matrix math only");
     MUMPY_REQUIRE(aligned16(workspace) && workspace, MUMPY_EALIGN, "linear_lnx: needs the kept (zeroed) workspace of mumpy_linear_wsz_fwd");
     MUMPY_REQUIRE((stats_out != nullptr) != (ln_stats != nullptr), MUMPY_EINVAL, "linear_lnx: exactly one of stats_out (producer) / ln_stats (consumer)");
@@ -1045,20 +1053,23 @@ extern "C" int mumpy_linear_lnx_fwd(const float* x, const float* W, const float*
     MUMPY_REQUIRE(M * (int64_t)((N + 127) / 128) * 8 < (1ll << 31) && M * (int64_t)(ln_gn > 0 ? ln_gn : 1) * 8 < (1ll << 31), MUMPY_ERANGE,
                   "linear_lnx: statistics buffer beyond 2 GiB");
     const gemm_ws::LnArgs ln{stats_out, ln_stats, ln_colsum, ln_gn, K, ln_eps};
-    return launch_linear(x, W, bias, residual, y, M, N, K, act, static_cast<float*>(workspace), workspace_bytes, as_stream(stream), 0, 0,
-                         nullptr, true, &ln);
+    LinearArgs a = linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream);
+    a.ws_clean = true;
+    a.ln = &ln;
+    return launch_linear(a);
 }
 
 extern "C" int mumpy_linear_rows_fwd(const float* x, int64_t rows_per_block, int64_t block_stride, const float* W,
                                      const float* bias, const float* residual, float* y, int64_t M, int N, int K, int act,
                                      void* workspace, int64_t workspace_bytes, void* stream) {
     if (M == 0) return 0;
-    if (int rc = check_linear_args(x, W, residual, y, M, N, K, act)) return rc;
+    if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
     MUMPY_REQUIRE(rows_per_block > 0 && M % rows_per_block == 0 && block_stride % 4 == 0, MUMPY_EINVAL,
                   "linear_rows: M=%lld must be a multiple of rows_per_block=%lld and block_stride %% 4 == 0",
                   (long long)M, (long long)rows_per_block);
-    return launch_linear(x, W, bias, residual, y, M, N, K, act, static_cast<float*>(workspace),
-                         workspace ? workspace_bytes : 0, as_stream(stream), rows_per_block, block_stride);
+    LinearArgs a = linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream);
+    a.rpb = rows_per_block; a.bstride = block_stride;
+    return launch_linear(a);
 }
 
 // Rows mode with a segmented contraction index: row (blk, r) of the A operand is the concatenation of K / kseg segments of kseg
@@ -1069,14 +1080,16 @@ extern "C" int mumpy_linear_rows_kseg_fwd(const float* x, int64_t rows_per_block
                                           const float* W, const float* bias, const float* residual, float* y, int64_t M, int N, int K,
                                           int act, void* workspace, int64_t workspace_bytes, void* stream) {
     if (M == 0) return 0;
-    if (int rc = check_linear_args(x, W, residual, y, M, N, K, act)) return rc;
+    if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
     MUMPY_REQUIRE(rows_per_block > 0 && M % rows_per_block == 0 && block_stride % 4 == 0, MUMPY_EINVAL,
                   "linear_rows_kseg: M=%lld must be a multiple of rows_per_block=%lld and block_stride %% 4 == 0",
                   (long long)M, (long long)rows_per_block);
     MUMPY_REQUIRE(kseg > 0 && kseg % 32 == 0 && K % kseg == 0 && kstride % 4 == 0 && kstride >= 0, MUMPY_EINVAL,
                   "linear_rows_kseg: need kseg %% 32 == 0, K %% kseg == 0, kstride %% 4 == 0 (got kseg=%d K=%d kstride=%d)", kseg, K, kstride);
-    return launch_linear(x, W, bias, residual, y, M, N, K, act, static_cast<float*>(workspace), workspace ? workspace_bytes : 0,
-                         as_stream(stream), rows_per_block, block_stride, nullptr, false, nullptr, kseg, kstride);
+    LinearArgs a = linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream);
+    a.rpb = rows_per_block; a.bstride = block_stride;
+    a.kseg = kseg; a.kstride = kstride;
+    return launch_linear(a);
 }
 
 extern "C" int64_t mumpy_conv2d_workspace_bytes(int B, int H, int W, int Cin, int Cout, int kh, int kw) {
@@ -1091,9 +1104,10 @@ extern "C" int mumpy_conv2d_nhwc_fwd(const float* x, const float* w_krsc, const 
     MUMPY_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0, MUMPY_EINVAL, "conv2d: Cin=%d and Cout=%d must be multiples of 32", Cin, Cout);
     const int64_t M = (int64_t)B * H * W;
     const int K = kh * kw * Cin;
-    if (int rc = check_linear_args(x, w_krsc, residual, y, M, Cout, K, act)) return rc;
+    if (int rc = check_linear_args("linear", x, w_krsc, residual, y, M, Cout, K, act)) return rc;
     MUMPY_REQUIRE(aligned16(workspace), MUMPY_EALIGN, "conv2d: workspace must be 16-byte aligned");
     const ConvGeom cg{H, W, Cin, kh, kw, kh / 2, kw / 2, 0, 0};
-    return launch_linear(x, w_krsc, bias, residual, y, M, Cout, K, act, static_cast<float*>(workspace),
-                         workspace ? workspace_bytes : 0, as_stream(stream), 0, 0, &cg);
+    LinearArgs a = linear_args(x, w_krsc, bias, residual, y, M, Cout, K, act, workspace, workspace_bytes, stream);
+    a.conv = &cg;
+    return launch_linear(a);
 }

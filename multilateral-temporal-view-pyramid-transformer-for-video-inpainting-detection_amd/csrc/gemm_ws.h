@@ -35,6 +35,7 @@
 // v_mfma_f32_32x32x16_bf16, bf16 or fp32 output): M=7840 N=512 K=2048 24.8 us [tiled bf16 kernel 65.2], N=2048 K=512 +GELU
 // 33.0 [43.4], N=512 K=512 11.6 [35.7]; with 512 matrix-pipe cycles per chunk those are bound by the epilogue waves.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 namespace mumpy {
@@ -73,28 +74,28 @@ struct Params {
     unsigned tiles;        // gm * gn
     unsigned rr_cnt, rr_G; // whole-tile schedule: tiles per workgroup (max) and grid size; 0 = split schedule (virtual id = position)
     unsigned st_w;         // super-tile width in tiles (4, 2 or 1)
-    unsigned walk;         // whole-tile schedule, 8 x 32 workgroups: an XCD walks ALONG N inside one strip of SH tile rows (see tile_coords)
+    unsigned walk = 0;     // whole-tile schedule, 8 x 32 workgroups: an XCD walks ALONG N inside one strip of SH tile rows (see tile_coords)
     unsigned units;        // tiles * nk: the workgroups split this chunk sequence evenly (split tiles: "stream-K")
-    int lmin;              // shortest allowed head part of a split tile (chunks)
+    int lmin = 0;          // shortest allowed head part of a split tile (chunks)
     // implicit-GEMM convolution (loader_role<true>): x is an NHWC image batch, row m = output pixel (img, y, x), K index =
     // (tap, channel); all zero for a plain GEMM
-    int cv_H, cv_W, cv_C, cv_kh, cv_kw, cv_cpc;             // image size, channels, taps, chunks per tap (Cin / 32)
-    unsigned cv_mhw, cv_shw, cv_mw, cv_sw;                  // magic numbers: m / (H W) and rem / W as mulhi + shift
-    unsigned* flags;       // [grid] arrival flags of the partial slabs (zeroed by the launcher), or null: whole tiles only
-    float* slabs;          // [grid][128*128] partial accumulator images of split tiles
+    int cv_H = 0, cv_W = 0, cv_C = 0, cv_kh = 0, cv_kw = 0, cv_cpc = 0;   // image size, channels, taps, chunks per tap (Cin / 32)
+    unsigned cv_mhw = 0, cv_shw = 0, cv_mw = 0, cv_sw = 0;                // magic numbers: m / (H W) and rem / W as mulhi + shift
+    unsigned* flags = nullptr;   // [grid] arrival flags of the partial slabs (zeroed by the launcher), or null: whole tiles only
+    float* slabs = nullptr;      // [grid][128*128] partial accumulator images of split tiles
     // LayerNorm folded into the GEMMs either side of it (epilogue_role<.., LN>; swin:266,305, blocks:86-88):
     //   LN = 1, producer (a residual GEMM whose output is the next LayerNorm's input): the epilogue also writes, per output row
     //           and 128-column tile, {mean_t, M2_t} of the values it stores (two-pass inside the tile: no cancellation);
     //   LN = 2, consumer (y = act(LayerNorm(x) W^T + b)): X is the RAW x, W is W diag(gamma), `bias` is W beta + b, and the
     //           epilogue finishes  rstd (acc - mean * colsum) + bias  with mean / rstd combined (Chan) from the producer's partials.
-    float* stats_out;      // LN = 1: [M][gn][2]
-    const float* ln_stats; // LN = 2: [M][ln_gn][2] from the producer (ln_gn = its column tiles, ln_C = its N = this K)
-    const float* ln_colsum;  // LN = 2: [N] sum_k W[n][k] gamma[k]
-    int ln_gn, ln_C;
-    float ln_eps;
-    unsigned* ln_guard;    // LN = 2: sticky precision-guard word of the workspace's flag page, or null
+    float* stats_out = nullptr;         // LN = 1: [M][gn][2]
+    const float* ln_stats = nullptr;    // LN = 2: [M][ln_gn][2] from the producer (ln_gn = its column tiles, ln_C = its N = this K)
+    const float* ln_colsum = nullptr;   // LN = 2: [N] sum_k W[n][k] gamma[k]
+    int ln_gn = 0, ln_C = 0;
+    float ln_eps = 0.f;
+    unsigned* ln_guard = nullptr;       // LN = 2: sticky precision-guard word of the workspace's flag page, or null
 #ifdef MUMPY_WS_STAMP
-    unsigned long long* stamps;   // diagnostics build: [block][8] cycle sums
+    unsigned long long* stamps = nullptr;   // diagnostics build: [block][8] cycle sums
 #endif
 };
 
@@ -706,8 +707,7 @@ __global__ __launch_bounds__(768, 3) void gemm_ws_kernel(Params p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     // persistent schedule: workgroup b' owns a contiguous run of the (tile, chunk) sequence; b' is the XCD-major
     // renumbering of blockIdx.x (workgroups are dealt round-robin over the 8 XCDs), so an XCD's L2 sees neighbouring tiles
-    const unsigned G = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q8 = G >> 3, r8 = G & 7;
-    const unsigned b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const unsigned G = gridDim.x, b = xcd_major_id(blockIdx.x, G);
     const bool split = p.flags != nullptr;
     unsigned u0, u1;
     if (split) {
@@ -767,33 +767,72 @@ struct LnArgs {
     float ln_eps;
 };
 
+// The shape part of Params, shared by the three launchers (this file's two and gemm_ws64.h): operands, tile grid (tile x tile
+// outputs, `chunk` elements of K per stage) and the whole-tile schedule over at most `slots` workgroups.  Everything else keeps
+// its default (no convolution, no split, no LayerNorm folding).  Returns the grid of the whole-tile schedule.
+inline unsigned base_params(Params& p, const void* x, const void* W, const float* bias, const float* residual, void* y, int64_t M,
+                            int N, int K, int act, int tile, int chunk, unsigned slots) {
+    p.X = static_cast<const float*>(x); p.W = static_cast<const float*>(W); p.bias = bias; p.residual = residual;
+    p.Y = static_cast<float*>(y);
+    p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nk = K / chunk;
+    p.gm = (unsigned)((M + tile - 1) / tile); p.gn = (unsigned)((N + tile - 1) / tile);
+    p.tiles = p.gm * p.gn;
+    p.units = p.tiles * (unsigned)p.nk;
+    p.st_w = (p.gn % 4 == 0) ? 4u : (p.gn % 2 == 0) ? 2u : 1u;
+    const unsigned grid = p.tiles < slots ? p.tiles : slots;
+    p.rr_G = grid;
+    p.rr_cnt = (p.tiles + grid - 1) / grid;
+    return grid;
+}
+
+// epilogue passes per chunk so that a tile's epilogue (`passes` passes) fits under the next tile's nk chunks: 1, 2, 4 or 8
+inline int passes_per_chunk(int passes, int nk) {
+    const int need = (passes + nk - 2) / (nk - 1);
+    return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
+}
+
+// P -> template argument: f(std::integral_constant<int, P>) for P in {1, 2, 4, 8} (PMAX = 4: {1, 2, 4})
+template <int PMAX = 8, class F>
+inline int with_passes(int P, F&& f) {
+    if (P == 1) return f(std::integral_constant<int, 1>{});
+    if (P == 2) return f(std::integral_constant<int, 2>{});
+    if (PMAX == 4 || P == 4) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, PMAX>{});
+}
+
+// One launch of a persistent kernel (768 threads); the first launch of every instantiation reserves its dynamic LDS.
+template <auto Kernel>
+inline int launch_ws(unsigned grid, int lds_bytes, int max_lds, hipStream_t s, const Params& p, const char* who = "gemm_ws") {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+        if (e != hipSuccess) { set_error("%s: cannot reserve %d B of LDS: %s", who, max_lds, hipGetErrorString(e)); return (int)e; }
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(768), lds_bytes, s, p);
+    return 0;
+}
+
 inline int launch(const float* x, const float* W, const float* bias, const float* residual, float* y, int64_t M, int N,
                   int K, int act, int num_cu, hipStream_t s, void* ws = nullptr, int64_t ws_bytes = 0, int force_split = -1,
                   void* stamps = nullptr, bool ws_clean = false, const Conv* cv = nullptr, const LnArgs* ln = nullptr) {
     Params p;
-    p.stats_out = ln ? ln->stats_out : nullptr;
-    p.ln_stats = ln ? ln->ln_stats : nullptr;
-    p.ln_colsum = ln ? ln->ln_colsum : nullptr;
-    p.ln_gn = ln ? ln->ln_gn : 0; p.ln_C = ln ? ln->ln_C : 0; p.ln_eps = ln ? ln->ln_eps : 0.f;
-    p.ln_guard = (ln && ln->ln_stats && ws && ws_bytes >= 4096) ? static_cast<unsigned*>(ws) + LN_GUARD_WORD : nullptr;
+    unsigned grid = base_params(p, x, W, bias, residual, y, M, N, K, act, BM, BK, (unsigned)num_cu);
+    if (ln) {
+        p.stats_out = ln->stats_out; p.ln_stats = ln->ln_stats; p.ln_colsum = ln->ln_colsum;
+        p.ln_gn = ln->ln_gn; p.ln_C = ln->ln_C; p.ln_eps = ln->ln_eps;
+        if (ln->ln_stats && ws && ws_bytes >= 4096) p.ln_guard = static_cast<unsigned*>(ws) + LN_GUARD_WORD;
+    }
     const int ln_mode = !ln ? 0 : (ln->stats_out ? 1 : 2);
-    p.cv_H = p.cv_W = p.cv_C = p.cv_kh = p.cv_kw = p.cv_cpc = 0;
-    p.cv_mhw = p.cv_shw = p.cv_mw = p.cv_sw = 0;
     if (cv) {
         p.cv_H = cv->H; p.cv_W = cv->W; p.cv_C = cv->C; p.cv_kh = cv->kh; p.cv_kw = cv->kw; p.cv_cpc = cv->C / BK;
         magic_div((unsigned)(cv->H * cv->W), p.cv_mhw, p.cv_shw);
         magic_div((unsigned)cv->W, p.cv_mw, p.cv_sw);
     }
-    p.X = x; p.W = W; p.bias = bias; p.residual = residual; p.Y = y;
-    p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nk = K / BK;
-    p.gm = (unsigned)((M + BM - 1) / BM); p.gn = (unsigned)((N + BN - 1) / BN);
-    p.tiles = p.gm * p.gn;
-    p.units = p.tiles * (unsigned)p.nk;
 #ifdef MUMPY_WS_STAMP
     p.stamps = static_cast<unsigned long long*>(stamps);
 #endif
-    const int need = (PASSES + p.nk - 2) / (p.nk - 1);
-    int P = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
+    int P = passes_per_chunk(PASSES, p.nk);
     // split tiles over workgroups when whole tiles would leave the last round of CUs under-used (and the caller gave a
     // workspace): every workgroup then gets the same number of chunks, at the price of one slab round trip per split tile
     const double rounds = (double)p.tiles / num_cu;
@@ -804,12 +843,7 @@ inline int launch(const float* x, const float* W, const float* bias, const float
     // short, so that the even split is not rounded away
     if (split && P < 4) P = 4;
     p.lmin = 1 + PASSES / P;
-    unsigned grid = p.tiles < (unsigned)num_cu ? p.tiles : (unsigned)num_cu;
-    p.st_w = (p.gn % 4 == 0) ? 4u : (p.gn % 2 == 0) ? 2u : 1u;
-    p.rr_G = grid;
-    p.rr_cnt = (p.tiles + grid - 1) / grid;
     p.walk = (grid == 256u && !split && tune_int("MUMPY_WS_WALK", 0)) ? 1u : 0u;
-    p.flags = nullptr; p.slabs = nullptr;
     if (split) {
         p.rr_cnt = 0;
         grid = (unsigned)num_cu;
@@ -822,46 +856,13 @@ inline int launch(const float* x, const float* W, const float* bias, const float
             if (e != hipSuccess) { set_error("gemm_ws: flag reset failed: %s", hipGetErrorString(e)); return (int)e; }
         }
     }
-#define MUMPY_WS_LAUNCH(P_)                                                                                             \
-    do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<P_>),                       \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);                  \
-            if (e != hipSuccess) { set_error("gemm_ws: cannot reserve %d B of LDS: %s", LDS_BYTES, hipGetErrorString(e)); return (int)e; } \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
-        static bool attr_set_cv = false;                                                                                \
-        if (cv && !attr_set_cv) {                                                                                       \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<P_, true>),                 \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);                  \
-            if (e != hipSuccess) { set_error("gemm_ws: cannot reserve %d B of LDS: %s", LDS_BYTES, hipGetErrorString(e)); return (int)e; } \
-            attr_set_cv = true;                                                                                         \
-        }                                                                                                               \
-        static bool attr_set_ln1 = false, attr_set_ln2 = false;                                                         \
-        if (ln_mode == 1 && !attr_set_ln1) {                                                                            \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<P_, false, 0, 1>),          \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);                  \
-            if (e != hipSuccess) { set_error("gemm_ws: cannot reserve %d B of LDS: %s", LDS_BYTES, hipGetErrorString(e)); return (int)e; } \
-            attr_set_ln1 = true;                                                                                        \
-        }                                                                                                               \
-        if (ln_mode == 2 && !attr_set_ln2) {                                                                            \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<P_, false, 0, 2>),          \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);                  \
-            if (e != hipSuccess) { set_error("gemm_ws: cannot reserve %d B of LDS: %s", LDS_BYTES, hipGetErrorString(e)); return (int)e; } \
-            attr_set_ln2 = true;                                                                                        \
-        }                                                                                                               \
-        if (cv) hipLaunchKernelGGL((gemm_ws_kernel<P_, true>), dim3(grid), dim3(768), LDS_BYTES, s, p);                 \
-        else if (ln_mode == 1) hipLaunchKernelGGL((gemm_ws_kernel<P_, false, 0, 1>), dim3(grid), dim3(768), LDS_BYTES, s, p); \
-        else if (ln_mode == 2) hipLaunchKernelGGL((gemm_ws_kernel<P_, false, 0, 2>), dim3(grid), dim3(768), LDS_BYTES, s, p); \
-        else hipLaunchKernelGGL((gemm_ws_kernel<P_, false>), dim3(grid), dim3(768), LDS_BYTES, s, p);                   \
-    } while (0)
-    if (P == 1) MUMPY_WS_LAUNCH(1);
-    else if (P == 2) MUMPY_WS_LAUNCH(2);
-    else if (P == 4) MUMPY_WS_LAUNCH(4);
-    else MUMPY_WS_LAUNCH(8);
-#undef MUMPY_WS_LAUNCH
-    return 0;
+    return with_passes(P, [&](auto pc) {
+        constexpr int PC = decltype(pc)::value;
+        if (cv) return launch_ws<gemm_ws_kernel<PC, true>>(grid, LDS_BYTES, LDS_BYTES, s, p);
+        if (ln_mode == 1) return launch_ws<gemm_ws_kernel<PC, false, 0, 1>>(grid, LDS_BYTES, LDS_BYTES, s, p);
+        if (ln_mode == 2) return launch_ws<gemm_ws_kernel<PC, false, 0, 2>>(grid, LDS_BYTES, LDS_BYTES, s, p);
+        return launch_ws<gemm_ws_kernel<PC>>(grid, LDS_BYTES, LDS_BYTES, s, p);
+    });
 }
 
 // ---- bf16 operands (config 3's storage).  x (M,K) and W (N,K) bf16 in memory, bias / residual fp32, y bf16 (no residual)
@@ -874,50 +875,14 @@ inline bool eligible16(int64_t M, int N, int K) {
 inline int launch16(const void* x16, const void* W16, const float* bias, const float* residual, void* y, int64_t M, int N, int K,
                     int act, bool out_bf16, int num_cu, hipStream_t s) {
     Params p;
-    p.cv_H = p.cv_W = p.cv_C = p.cv_kh = p.cv_kw = p.cv_cpc = 0;
-    p.cv_mhw = p.cv_shw = p.cv_mw = p.cv_sw = 0;
-    p.X = static_cast<const float*>(x16); p.W = static_cast<const float*>(W16); p.bias = bias; p.residual = residual;
-    p.Y = static_cast<float*>(y);
-    p.stats_out = nullptr; p.ln_stats = nullptr; p.ln_colsum = nullptr; p.ln_gn = p.ln_C = 0; p.ln_eps = 0.f; p.ln_guard = nullptr;
-    p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nk = K / 64;
-    p.gm = (unsigned)((M + BM - 1) / BM); p.gn = (unsigned)((N + BN - 1) / BN);
-    p.tiles = p.gm * p.gn;
-    p.units = p.tiles * (unsigned)p.nk;
-#ifdef MUMPY_WS_STAMP
-    p.stamps = nullptr;
-#endif
-    const int need = (PASSES + p.nk - 2) / (p.nk - 1);
-    const int P = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
+    const unsigned grid = base_params(p, x16, W16, bias, residual, y, M, N, K, act, BM, 64, (unsigned)num_cu);
+    const int P = passes_per_chunk(PASSES, p.nk);
     p.lmin = 1 + PASSES / P;
-    const unsigned grid = p.tiles < (unsigned)num_cu ? p.tiles : (unsigned)num_cu;
-    p.st_w = (p.gn % 4 == 0) ? 4u : (p.gn % 2 == 0) ? 2u : 1u;
-    p.rr_G = grid;
-    p.rr_cnt = (p.tiles + grid - 1) / grid;
-    p.walk = 0u;
-    p.flags = nullptr; p.slabs = nullptr;
-#define MUMPY_WS_LAUNCH16(P_, IO_)                                                                                      \
-    do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws_kernel<P_, false, IO_>),           \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);                  \
-            if (e != hipSuccess) { set_error("gemm_ws: cannot reserve %d B of LDS: %s", LDS_BYTES, hipGetErrorString(e)); return (int)e; } \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL((gemm_ws_kernel<P_, false, IO_>), dim3(grid), dim3(768), LDS_BYTES, s, p);                   \
-    } while (0)
-#define MUMPY_WS_PICK16(IO_)                                                                                            \
-    do {                                                                                                                \
-        if (P == 1) MUMPY_WS_LAUNCH16(1, IO_);                                                                          \
-        else if (P == 2) MUMPY_WS_LAUNCH16(2, IO_);                                                                     \
-        else if (P == 4) MUMPY_WS_LAUNCH16(4, IO_);                                                                     \
-        else MUMPY_WS_LAUNCH16(8, IO_);                                                                                 \
-    } while (0)
-    if (out_bf16) MUMPY_WS_PICK16(1);
-    else MUMPY_WS_PICK16(2);
-#undef MUMPY_WS_PICK16
-#undef MUMPY_WS_LAUNCH16
-    return 0;
+    return with_passes(P, [&](auto pc) {
+        constexpr int PC = decltype(pc)::value;
+        if (out_bf16) return launch_ws<gemm_ws_kernel<PC, false, 1>>(grid, LDS_BYTES, LDS_BYTES, s, p);
+        return launch_ws<gemm_ws_kernel<PC, false, 2>>(grid, LDS_BYTES, LDS_BYTES, s, p);
+    });
 }
 
 }  // namespace gemm_ws

@@ -219,8 +219,7 @@ __global__ __launch_bounds__(768, 6) void gemm_ws64_kernel(Params p) {
     extern __shared__ __attribute__((aligned(1024))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const unsigned G = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q8 = G >> 3, r8 = G & 7;
-    const unsigned b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const unsigned G = gridDim.x, b = xcd_major_id(blockIdx.x, G);
     const unsigned cnt = b < p.tiles ? (p.tiles - b + G - 1) / G : 0;     // whole tiles, dealt round-robin (gemm_ws.h)
     if (cnt == 0) return;
     const unsigned v0 = b * p.rr_cnt;
@@ -240,42 +239,12 @@ inline bool eligible(int64_t M, int N, int K) { return gemm_ws::eligible(M, N, K
 inline int launch(const float* x, const float* W, const float* bias, const float* residual, float* y, int64_t M, int N, int K,
                   int act, int num_cu, hipStream_t s, int per_cu = 2) {
     Params p;
-    p.cv_H = p.cv_W = p.cv_C = p.cv_kh = p.cv_kw = p.cv_cpc = 0;
-    p.cv_mhw = p.cv_shw = p.cv_mw = p.cv_sw = 0;
-    p.X = x; p.W = W; p.bias = bias; p.residual = residual; p.Y = y;
-    p.M = (int)M; p.N = N; p.K = K; p.act = act; p.nk = K / BK;
-    p.gm = (unsigned)((M + T - 1) / T); p.gn = (unsigned)((N + T - 1) / T);
-    p.tiles = p.gm * p.gn;
-    p.units = p.tiles * (unsigned)p.nk;
-#ifdef MUMPY_WS_STAMP
-    p.stamps = nullptr;
-#endif
-    const int need = (PASSES + p.nk - 2) / (p.nk - 1);           // passes per chunk so that a tile's epilogue fits under the next tile
-    const int P = need <= 1 ? 1 : need <= 2 ? 2 : 4;
-    p.lmin = 0;
-    const unsigned slots = (unsigned)per_cu * (unsigned)num_cu;
+    const unsigned grid = gemm_ws::base_params(p, x, W, bias, residual, y, M, N, K, act, T, BK, (unsigned)per_cu * (unsigned)num_cu);
+    const int P = gemm_ws::passes_per_chunk(PASSES, p.nk);        // (4 passes per tile: at most 4 per chunk)
     const int lds_bytes = per_cu == 1 ? 2 * LDS_BYTES + 1024 : LDS_BYTES;
-    const unsigned grid = p.tiles < slots ? p.tiles : slots;
-    p.st_w = (p.gn % 4 == 0) ? 4u : (p.gn % 2 == 0) ? 2u : 1u;
-    p.rr_G = grid;
-    p.rr_cnt = (p.tiles + grid - 1) / grid;
-    p.flags = nullptr; p.slabs = nullptr;
-#define MUMPY_WS64_LAUNCH(P_)                                                                                           \
-    do {                                                                                                                \
-        static bool attr_set = false;                                                                                   \
-        if (!attr_set) {                                                                                                \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_ws64_kernel<P_>),                     \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 2 * LDS_BYTES + 1024);       \
-            if (e != hipSuccess) { set_error("gemm_ws64: cannot reserve %d B of LDS: %s", 2 * LDS_BYTES + 1024, hipGetErrorString(e)); return (int)e; } \
-            attr_set = true;                                                                                            \
-        }                                                                                                               \
-        hipLaunchKernelGGL(gemm_ws64_kernel<P_>, dim3(grid), dim3(768), lds_bytes, s, p);                               \
-    } while (0)
-    if (P == 1) MUMPY_WS64_LAUNCH(1);
-    else if (P == 2) MUMPY_WS64_LAUNCH(2);
-    else MUMPY_WS64_LAUNCH(4);
-#undef MUMPY_WS64_LAUNCH
-    return 0;
+    return gemm_ws::with_passes<4>(P, [&](auto pc) {
+        return gemm_ws::launch_ws<gemm_ws64_kernel<decltype(pc)::value>>(grid, lds_bytes, 2 * LDS_BYTES + 1024, s, p, "gemm_ws64");
+    });
 }
 
 }  // namespace gemm_ws64

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI.  Each takes/returns torch CUDA(HIP) fp32 tensors, allocates outputs with
 torch (caching allocator => graph-capturable), and enqueues on torch's current stream.  No fallbacks."""
 import math
+import os
 from typing import Optional
 
 import torch
@@ -52,82 +53,6 @@ def storage() -> str:
     return _STORAGE
 
 
-def _chk16(t: torch.Tensor, name: str) -> torch.Tensor:
-    if not t.is_cuda or t.dtype != torch.bfloat16:
-        raise RuntimeError(f"mumpy_hip: {name} must be a bfloat16 GPU tensor, got {t.dtype} on {t.device}")
-    return t if t.is_contiguous() else t.contiguous()
-
-
-def layernorm_bf16(x, gamma, beta, eps=1e-5):
-    """LayerNorm of an fp32 tensor, written as bf16 (statistics in fp32)."""
-    x = _chk(x, "x")
-    c = x.shape[-1]
-    out = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    _call("mumpy_layernorm_bf16_fwd", _p(x), _p(_chk(gamma, "gamma")), _p(_chk(beta, "beta")), _p(out), x.numel() // c, c, eps,
-          _stream(), work=6.0 * x.numel())
-    return out
-
-
-def linear_bf16s(x16, w16, bias=None, act=ACT_NONE, residual=None, out_bf16=True):
-    """y = act(x16 @ w16.T + bias) + residual with bf16 x / W in memory, fp32 accumulate; y bf16 or fp32 (residual fp32)."""
-    x16, w16 = _chk16(x16, "x"), _chk16(w16, "weight")
-    n, k = w16.shape[0], w16.numel() // w16.shape[0]
-    if x16.shape[-1] != k:
-        raise RuntimeError(f"linear_bf16s: x has {x16.shape[-1]} features, weight expects {k}")
-    m = x16.numel() // k
-    out = torch.empty(*x16.shape[:-1], n, device=x16.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
-    if residual is not None:
-        residual = _chk(residual, "residual")
-        if residual.numel() != m * n or out_bf16:
-            raise RuntimeError("linear_bf16s: the residual is fp32 and needs an fp32 output of the same shape")
-    _call("mumpy_linear_bf16s_fwd", _p(x16), _p(w16), _p(None if bias is None else _chk(bias, "bias")), _p(residual), _p(out),
-          m, n, k, act, 1 if out_bf16 else 0, _stream(), work=2.0 * m * n * k)
-    return out
-
-
-def _attn_math_from_env() -> str:
-    mode = __import__("os").environ.get("MUMPY_ATTN_MATH", "") or "fp32"
-    if mode not in ("fp32", "bf16"):
-        raise ValueError(f"MUMPY_ATTN_MATH: unknown attention math mode {mode!r}")
-    return mode
-
-
-_ATTN_MATH = _attn_math_from_env()       # read once, at import
-
-
-def set_attention_math(mode: str) -> None:
-    """Arithmetic of the Swin window attention core when qkv is STORED as bf16 (set_storage("bf16")).  "fp32" (default): the bf16
-    values are widened and the unit runs the fp32 MFMA flow (mumpy_window_attention_bf16_fwd).  "bf16": Q K^T and P V run on
-    the bf16 MFMA with fp32 accumulation and an fp32 softmax (mumpy_window_attention_bf16mm_fwd; forward only).  fp32 qkv always
-    runs the fp32 kernels, and set_storage does not touch this switch.  The initial value is the environment variable
-    MUMPY_ATTN_MATH, read when this module is imported.  Like set_storage it is read at launch time: set it BEFORE a
-    GraphedForward is captured -- a captured graph keeps the kernels it was captured with."""
-    global _ATTN_MATH
-    if mode not in ("fp32", "bf16"):
-        raise ValueError(f"unknown attention math mode {mode!r}")
-    _ATTN_MATH = mode
-
-
-def attention_math() -> str:
-    return _ATTN_MATH
-
-
-def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, math=None):
-    """bf16 qkv (B, hs*w, 3C) -> bf16 (B, hs*w, C).  math: None follows attention_math(); "fp32" / "bf16" force the fp32-flow /
-    the bf16-MFMA kernel."""
-    if math is None:
-        math = _ATTN_MATH
-    elif math not in ("fp32", "bf16"):
-        raise ValueError(f"unknown attention math mode {math!r}")
-    qkv16 = _chk16(qkv16, "qkv")
-    if qkv16.numel() != b * hs * w * 3 * c:
-        raise RuntimeError("window_attention_bf16: qkv shape mismatch")
-    out = torch.empty(b, hs * w, c, device=qkv16.device, dtype=torch.bfloat16)
-    n_mask = 0 if mask_id is None else mask_id.numel()
-    _call("mumpy_window_attention_bf16mm_fwd" if math == "bf16" else "mumpy_window_attention_bf16_fwd", _p(qkv16), _p(out),
-          _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
-          b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
-    return out
 NEG = -1e30
 
 
@@ -170,6 +95,97 @@ def _call(name, *args, work=0.0):
         raise RuntimeError(f"{name} failed (rc={rc}): {lib.mumpy_last_error().decode()}")
 
 
+def _opt(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    """An optional fp32 operand (a bias): checked like any other when given."""
+    return None if t is None else _chk(t, name)
+
+
+def _ws_bytes(key, fn_name, *args):
+    """Workspace size of a launch (in the library a pure host function of the shape), asked once per shape."""
+    wsb = _WS_BYTES.get(key)
+    if wsb is None:
+        wsb = _WS_BYTES[key] = int(getattr(_lib(), fn_name)(*args))
+    return wsb
+
+
+def _chk16(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not t.is_cuda or t.dtype != torch.bfloat16:
+        raise RuntimeError(f"mumpy_hip: {name} must be a bfloat16 GPU tensor, got {t.dtype} on {t.device}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def layernorm_bf16(x, gamma, beta, eps=1e-5):
+    """LayerNorm of an fp32 tensor, written as bf16 (statistics in fp32)."""
+    x = _chk(x, "x")
+    c = x.shape[-1]
+    out = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
+    _call("mumpy_layernorm_bf16_fwd", _p(x), _p(_chk(gamma, "gamma")), _p(_chk(beta, "beta")), _p(out), x.numel() // c, c, eps,
+          _stream(), work=6.0 * x.numel())
+    return out
+
+
+def linear_bf16s(x16, w16, bias=None, act=ACT_NONE, residual=None, out_bf16=True):
+    """y = act(x16 @ w16.T + bias) + residual with bf16 x / W in memory, fp32 accumulate; y bf16 or fp32 (residual fp32)."""
+    x16, w16 = _chk16(x16, "x"), _chk16(w16, "weight")
+    n, k = w16.shape[0], w16.numel() // w16.shape[0]
+    if x16.shape[-1] != k:
+        raise RuntimeError(f"linear_bf16s: x has {x16.shape[-1]} features, weight expects {k}")
+    m = x16.numel() // k
+    out = torch.empty(*x16.shape[:-1], n, device=x16.device, dtype=torch.bfloat16 if out_bf16 else torch.float32)
+    if residual is not None:
+        residual = _chk(residual, "residual")
+        if residual.numel() != m * n or out_bf16:
+            raise RuntimeError("linear_bf16s: the residual is fp32 and needs an fp32 output of the same shape")
+    _call("mumpy_linear_bf16s_fwd", _p(x16), _p(w16), _p(_opt(bias, "bias")), _p(residual), _p(out),
+          m, n, k, act, 1 if out_bf16 else 0, _stream(), work=2.0 * m * n * k)
+    return out
+
+
+def _attn_math_from_env() -> str:
+    mode = os.environ.get("MUMPY_ATTN_MATH", "") or "fp32"
+    if mode not in ("fp32", "bf16"):
+        raise ValueError(f"MUMPY_ATTN_MATH: unknown attention math mode {mode!r}")
+    return mode
+
+
+_ATTN_MATH = _attn_math_from_env()       # read once, at import
+
+
+def set_attention_math(mode: str) -> None:
+    """Arithmetic of the Swin window attention core when qkv is STORED as bf16 (set_storage("bf16")).  "fp32" (default): the bf16
+    values are widened and the unit runs the fp32 MFMA flow (mumpy_window_attention_bf16_fwd).  "bf16": Q K^T and P V run on
+    the bf16 MFMA with fp32 accumulation and an fp32 softmax (mumpy_window_attention_bf16mm_fwd; forward only).  fp32 qkv always
+    runs the fp32 kernels, and set_storage does not touch this switch.  The initial value is the environment variable
+    MUMPY_ATTN_MATH, read when this module is imported.  Like set_storage it is read at launch time: set it BEFORE a
+    GraphedForward is captured -- a captured graph keeps the kernels it was captured with."""
+    global _ATTN_MATH
+    if mode not in ("fp32", "bf16"):
+        raise ValueError(f"unknown attention math mode {mode!r}")
+    _ATTN_MATH = mode
+
+
+def attention_math() -> str:
+    return _ATTN_MATH
+
+
+def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, math=None):
+    """bf16 qkv (B, hs*w, 3C) -> bf16 (B, hs*w, C).  math: None follows attention_math(); "fp32" / "bf16" force the fp32-flow /
+    the bf16-MFMA kernel."""
+    if math is None:
+        math = _ATTN_MATH
+    elif math not in ("fp32", "bf16"):
+        raise ValueError(f"unknown attention math mode {math!r}")
+    qkv16 = _chk16(qkv16, "qkv")
+    if qkv16.numel() != b * hs * w * 3 * c:
+        raise RuntimeError("window_attention_bf16: qkv shape mismatch")
+    out = torch.empty(b, hs * w, c, device=qkv16.device, dtype=torch.bfloat16)
+    n_mask = 0 if mask_id is None else mask_id.numel()
+    _call("mumpy_window_attention_bf16mm_fwd" if math == "bf16" else "mumpy_window_attention_bf16_fwd", _p(qkv16), _p(out),
+          _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
+          b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 def layernorm(x, gamma, beta, eps=1e-5, out=None):
     x = _chk(x, "x")
@@ -197,13 +213,10 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, out=None, emit_sta
         if residual.numel() != m * n:
             raise RuntimeError("linear: residual shape mismatch")
     if _in_background():
-        _call("mumpy_linear_rd_fwd", _p(x), _p(weight), _p(None if bias is None else _chk(bias, "bias")), _p(residual), _p(out), m, n, k,
+        _call("mumpy_linear_rd_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(residual), _p(out), m, n, k,
               act, _stream(), work=2.0 * m * n * k)
         return out
-    key = (m, n, k)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_linear_workspace_bytes(m, n, k))
+    wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
     if emit_stats:
         # measured (tools/ln_fold_shapes.py, profiles/r03_ln_fold_shapes.txt): the statistics epilogue costs 4-5 us on a producer with
         # >= 16 chunks per tile (K >= 512) -- less than the LayerNorm launch it saves -- but 9-21 us on the short-K producers of
@@ -212,12 +225,12 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, out=None, emit_sta
         if gn:
             stats = torch.empty(m, gn, 2, device=x.device, dtype=torch.float32)
             ws = _kept_workspace(max(wsb, 4096), x.device)
-            _call("mumpy_linear_lnx_fwd", _p(x), _p(weight), _p(None if bias is None else _chk(bias, "bias")), _p(residual), _p(out), m, n, k,
+            _call("mumpy_linear_lnx_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(residual), _p(out), m, n, k,
                   act, _p(ws), ws.numel() * 4, _p(stats), None, 0, None, 0.0, _stream(), work=2.0 * m * n * k)
             out._mumpy_ln_stats = stats
             return out
     ws = _kept_workspace(wsb, x.device) if wsb else None      # split-K slabs / the persistent kernel's flags + slabs
-    _call("mumpy_linear_wsz_fwd", _p(x), _p(weight), _p(None if bias is None else _chk(bias, "bias")), _p(residual),
+    _call("mumpy_linear_wsz_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(residual),
           _p(out), m, n, k, act | _MATH, _p(ws), 0 if ws is None else ws.numel() * 4, _stream(), work=2.0 * m * n * k)
     return out
 
@@ -227,7 +240,7 @@ _BACKGROUND = [0]
 # Measured and NOT adopted (default off; profiles/r03_coresidency_probe.txt): the LDS-free GEMM is resident-compatible with the
 # persistent kernel but two MFMA-bound kernels gain nothing from sharing a CU (together = sum on the two-stream probe), and alone
 # it is slower than the tiled kernels -- the forward went 21.5 -> 23.3 ms with it.  MUMPY_BACKGROUND=1 turns it on for A/B runs.
-BACKGROUND_ON = __import__("os").environ.get("MUMPY_BACKGROUND", "0") == "1"
+BACKGROUND_ON = os.environ.get("MUMPY_BACKGROUND", "0") == "1"
 
 
 class background:
@@ -249,7 +262,7 @@ def _in_background():
 
 
 # ---- LayerNorm folded into the GEMMs either side of it (mumpy_linear_lnx_fwd; swin:266,305 / blocks:86-88) -----------------
-LN_FOLD = __import__("os").environ.get("MUMPY_LN_FOLD", "1") != "0"      # A/B switch
+LN_FOLD = os.environ.get("MUMPY_LN_FOLD", "1") != "0"      # A/B switch
 LN_FOLD_MIN_K = 512
 _LN_TILES = {}
 
@@ -278,9 +291,7 @@ def linear_ln(x, stats, wg, colsum, bprime, eps, act=ACT_NONE):
     n, k = wg.shape
     m = x.numel() // k
     out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=torch.float32)
-    wsb = _WS_BYTES.get((m, n, k))
-    if wsb is None:
-        wsb = _WS_BYTES[(m, n, k)] = int(_lib().mumpy_linear_workspace_bytes(m, n, k))
+    wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
     ws = _kept_workspace(max(wsb, 4096), x.device)
     _call("mumpy_linear_lnx_fwd", _p(x), _p(wg), _p(_chk(bprime, "bprime")), None, _p(out), m, n, k, act, _p(ws), ws.numel() * 4, None,
           _p(_chk(stats, "stats")), stats.shape[-2], _p(_chk(colsum, "colsum")), eps, _stream(), work=2.0 * m * n * k)
@@ -368,13 +379,10 @@ def linear_rows(x_view, weight, bias=None, residual=None, out=None):
     m = nblk * rows
     if out is None:
         out = torch.empty(m, n, device=x_view.device, dtype=torch.float32)
-    key = (m, n, k)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_linear_workspace_bytes(m, n, k))
+    wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
     ws = torch.empty(wsb // 4, device=x_view.device, dtype=torch.float32) if wsb else None
     _call("mumpy_linear_rows_fwd", x_view.data_ptr(), rows, x_view.stride(0), _p(weight),
-          _p(None if bias is None else _chk(bias, "bias")), _p(residual), _p(out), m, n, k, ACT_NONE | _MATH, _p(ws), wsb, _stream(),
+          _p(_opt(bias, "bias")), _p(residual), _p(out), m, n, k, ACT_NONE | _MATH, _p(ws), wsb, _stream(),
           work=2.0 * m * n * k)
     return out
 
@@ -391,12 +399,9 @@ def linear_time_slices(x4, weight, bias=None, residual=None):
     out = torch.empty(m, nout, device=x4.device, dtype=torch.float32)
     if residual is not None:
         residual = _chk(residual, "residual")
-    key = (m, nout, k)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_linear_workspace_bytes(m, nout, k))
+    wsb = _ws_bytes((m, nout, k), "mumpy_linear_workspace_bytes", m, nout, k)
     ws = torch.empty(wsb // 4, device=x4.device, dtype=torch.float32) if wsb else None
-    _call("mumpy_linear_rows_kseg_fwd", _p(x4), n, t * n * c, c, n * c, _p(weight), _p(None if bias is None else _chk(bias, "bias")),
+    _call("mumpy_linear_rows_kseg_fwd", _p(x4), n, t * n * c, c, n * c, _p(weight), _p(_opt(bias, "bias")),
           _p(residual), _p(out), m, nout, k, ACT_NONE | _MATH, _p(ws), wsb, _stream(), work=2.0 * m * nout * k)
     return out
 
@@ -413,12 +418,9 @@ def conv2d_nhwc(x, w_krsc, bias=None, act=ACT_NONE, residual=None):
     out = empty_nhwc(b, cout, h, w, x.device)
     if residual is not None:
         residual = _nhwc(residual, "residual")
-    key = ("conv", b, h, w, cin, cout, kh, kw)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_conv2d_workspace_bytes(b, h, w, cin, cout, kh, kw))
+    wsb = _ws_bytes(("conv", b, h, w, cin, cout, kh, kw), "mumpy_conv2d_workspace_bytes", b, h, w, cin, cout, kh, kw)
     ws = torch.empty(wsb // 4, device=x.device, dtype=torch.float32) if wsb else None
-    _call("mumpy_conv2d_nhwc_fwd", _p(x), _p(w_krsc), _p(None if bias is None else _chk(bias, "bias")), _p(residual), _p(out),
+    _call("mumpy_conv2d_nhwc_fwd", _p(x), _p(w_krsc), _p(_opt(bias, "bias")), _p(residual), _p(out),
           b, h, w, cin, cout, kh, kw, act | _MATH, _p(ws), wsb, _stream(), work=2.0 * b * h * w * cout * kh * kw * cin)
     return out
 
@@ -839,10 +841,7 @@ def layernorm_bwd(x, gamma, dy, eps=1e-5, dx_add=None, dg_out=None, db_out=None)
     acc = dg_out is not None
     dg = _chk(dg_out, "dg_out") if acc else torch.empty(c, device=x.device, dtype=torch.float32)
     db = _chk(db_out, "db_out") if acc else torch.empty(c, device=x.device, dtype=torch.float32)
-    key = ("lnbwd", rows, c)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_layernorm_bwd_workspace_bytes(rows, c))
+    wsb = _ws_bytes(("lnbwd", rows, c), "mumpy_layernorm_bwd_workspace_bytes", rows, c)
     ws = _ws(wsb, x.device)
     _call("mumpy_layernorm_bwd", _p(x), _p(gamma), _p(dy), _p(dx_add), _p(dx), _p(dg), _p(db), _p(ws), wsb, rows, c, eps, int(acc),
           _stream(), work=12.0 * x.numel())
@@ -908,10 +907,7 @@ def linear_bwd(x2d, weight, dy2d, need_dx=True, dw_out=None, db_out=None, need_d
             db, acc = _chk(db_out, "db_out"), acc | 2
         else:
             db = torch.empty(n, device=dev, dtype=torch.float32)
-    key = ("lbwd", m, n, k)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_linear_bwd_workspace_bytes(m, n, k))
+    wsb = _ws_bytes(("lbwd", m, n, k), "mumpy_linear_bwd_workspace_bytes", m, n, k)
     ws = _ws(wsb, dev)
     if _MATH == MATH_BF16:
         acc |= MATH_BF16                                      # bf16 operands on the bf16 MFMA, fp32 accumulate (config 5's arithmetic)
@@ -972,10 +968,7 @@ def conv2d_wgrad(x, dy, kh, kw, dw_out=None):
     dw = _chk(dw_out, "dw_out") if acc else torch.empty(cout, kh, kw, cin, device=x.device, dtype=torch.float32)
     if dw.shape != (cout, kh, kw, cin):
         raise RuntimeError(f"conv2d_wgrad: gradient buffer {tuple(dw.shape)} != {(cout, kh, kw, cin)}")
-    key = ("cwgrad", b, h, w, cin, cout, kh, kw)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_conv2d_wgrad_workspace_bytes(b, h, w, cin, cout, kh, kw))
+    wsb = _ws_bytes(("cwgrad", b, h, w, cin, cout, kh, kw), "mumpy_conv2d_wgrad_workspace_bytes", b, h, w, cin, cout, kh, kw)
     ws = _ws(wsb, x.device) if wsb else None
     if _MATH not in (MATH_FP32, MATH_BF16):
         raise RuntimeError("conv2d_wgrad: the split-precision modes have no one-launch weight gradient")
@@ -1027,10 +1020,7 @@ def window_attention_bwd(qkv, dout, bias_pad, rel_index32, b, hs, w, c, shift, s
     dtable = _chk(dtable_out, "dtable_out") if acc else torch.empty(169, c // 32, device=qkv.device, dtype=torch.float32)
     if dtable.shape != (169, c // 32):
         raise RuntimeError(f"window_attention_bwd: table gradient buffer {tuple(dtable.shape)} != {(169, c // 32)}")
-    key = ("wabwd", b, hs, w, c)
-    wsb = _WS_BYTES.get(key)
-    if wsb is None:
-        wsb = _WS_BYTES[key] = int(_lib().mumpy_window_attention_bwd_workspace_bytes(b, hs, w, c))
+    wsb = _ws_bytes(("wabwd", b, hs, w, c), "mumpy_window_attention_bwd_workspace_bytes", b, hs, w, c)
     ws = _ws(wsb, qkv.device)
     n_mask = 0 if mask_id is None else mask_id.numel()
     if rel_csr is not None and (rel_csr.dtype != torch.int32 or rel_csr.numel() != 170 + 49 * 49 or rel_csr.device != qkv.device):

@@ -114,3 +114,18 @@ def test_shipped_library_reads_no_environment_and_the_tuning_build_exists():
     assert os.path.exists(tuning_library_path()), "run `python __graft_entry__.py` (builds both libraries)"
     t = ctypes.CDLL(tuning_library_path())
     assert t.mumpy_tuning_build() == 1 and t.mumpy_abi_version() == load_library().mumpy_abi_version()
+
+
+def test_gemm_planner_matches_the_recorded_values():
+    """mumpy_linear_workspace_bytes and mumpy_linear_ln_tiles are pure host functions of the shape (the planner of csrc/gemm.hip at
+    256 CUs: the MI355X's count, and the fall-back without a device).  Their values over an M x N x K sweep are recorded in
+    tests/golden/gemm_planner.json; a change of the launch layer must not move any of them."""
+    import json
+    from mumpy_hip.lib import load_library
+    lib = load_library()
+    with open(os.path.join(ROOT, "tests", "golden", "gemm_planner.json")) as f:
+        gold = json.load(f)
+    shapes = [(m, n, k) for m in gold["M"] for n in gold["N"] for k in gold["K"]]
+    assert len(shapes) == 640 == len(gold["workspace_bytes"]) == len(gold["ln_tiles"])
+    assert [int(lib.mumpy_linear_workspace_bytes(*s)) for s in shapes] == gold["workspace_bytes"]
+    assert [int(lib.mumpy_linear_ln_tiles(*s)) for s in shapes] == gold["ln_tiles"]

@@ -46,7 +46,8 @@ def test_layernorm_empty_and_inplace():
 
 
 @pytest.mark.parametrize("m,n,k", [(392, 96, 96), (1, 128, 32), (129, 288, 96), (1568, 384, 1536), (300, 768, 2560),
-                                   (257, 2304, 768), (1000, 512, 128), (64, 96, 384), (131, 192, 384), (50, 3072, 768), (392, 768, 3072), (1568, 384, 1536), (392, 256, 12800), (1960, 768, 3072), (7840, 512, 2048)])
+                                   (257, 2304, 768), (1000, 512, 128), (64, 96, 384), (131, 192, 384), (50, 3072, 768), (392, 768, 3072), (1568, 384, 1536), (392, 256, 12800), (1960, 768, 3072), (7840, 512, 2048),
+                                   (129, 576, 1536)])
 @pytest.mark.parametrize("act,res", [(0, False), (1, True)])
 def test_linear(m, n, k, act, res):
     x, w, b = seeded_randn(m, m, k), seeded_randn(n, n, k) / k ** 0.5, seeded_randn(k, n)
@@ -948,7 +949,8 @@ def bf16_math():
     ops.set_matrix_math("fp32")
 
 
-@pytest.mark.parametrize("m,n,k", [(300, 128, 96), (1568, 384, 1536), (7840, 512, 512), (392, 256, 12800), (25088, 96, 384)])
+@pytest.mark.parametrize("m,n,k", [(300, 128, 96), (1568, 384, 1536), (7840, 512, 512), (392, 256, 12800), (25088, 96, 384),
+                                   (300, 768, 2560)])
 def test_linear_bf16_math(bf16_math, m, n, k):
     """Operands rounded to bf16 (RNE), fp32 accumulate: must equal an fp64 product of the ROUNDED operands to fp32
     round-off, and stay within bf16's 2^-8 operand precision of the exact product."""
@@ -997,7 +999,7 @@ def bf16x3_math():
 
 
 @pytest.mark.parametrize("m,n,k", [(300, 128, 96), (1568, 384, 1536), (7840, 512, 2048), (7840, 2048, 512), (392, 256, 12800),
-                                   (25088, 96, 384), (1960, 768, 3072)])
+                                   (25088, 96, 384), (1960, 768, 3072), (300, 768, 2560), (2000, 640, 1536)])
 def test_linear_bf16x3_math(m, n, k):
     """Three bf16 pieces per operand, six piece products, fp32 accumulate: the result must be as close to the fp64
     product as the native fp32-MFMA kernel is (same inputs, max and rms error compared), i.e. this is fp32 arithmetic
@@ -1054,7 +1056,8 @@ def test_full_model_bf16x3_math_t5(full_golden, bf16x3_math):
 
 
 # ------------------------------------------------------------------ two-piece mode: 16-bit-mantissa operands (TF32-class)
-@pytest.mark.parametrize("m,n,k", [(300, 128, 96), (1568, 384, 1536), (7840, 512, 2048), (7840, 2048, 512), (392, 256, 12800)])
+@pytest.mark.parametrize("m,n,k", [(300, 128, 96), (1568, 384, 1536), (7840, 512, 2048), (7840, 2048, 512), (392, 256, 12800),
+                                   (300, 768, 2560)])
 def test_linear_bf16x2_math(m, n, k):
     """Two bf16 pieces per operand, three piece products: must equal an fp64 product of the operands ROUNDED TO THE TWO-PIECE
     FORM to fp32 round-off, and stay within the 2^-17 operand precision of the exact product (between bf16 and fp32)."""
