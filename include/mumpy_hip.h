@@ -224,6 +224,15 @@ int mumpy_window_attention_bf16mm_fwd(const void* qkv, void* out, const float* b
                                       const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift,
                                       float scale, void* stream);
 
+/* fp32 storage, bf16 matrix math (opt-in; the forward of the training tape under ops.set_attention_math("bf16")): qkv and out
+ * are fp32 in memory, q / k / v are rounded to bf16 (nearest even) in registers and both products run on
+ * v_mfma_f32_32x32x16_bf16 exactly as in mumpy_window_attention_bf16mm_fwd (scale on the fp32 scores after the product, exp(s - max)
+ * rounded unnormalised, fp32 row sum); the output is stored unrounded.  Same arguments, validation and error codes as
+ * mumpy_window_attention_fwd.  Its backward is mumpy_window_attention_mm16_bwd. */
+int mumpy_window_attention_mm16_fwd(const float* qkv, float* out, const float* bias, const float* mask_tab,
+                                    const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift,
+                                    float scale, void* stream);
+
 /* ---- Deformable cross-view attention (SwinDAttention, deform:324-405) — four kernels -------------- */
 
 /* offsets: q (B, H*W, C) raster, one frame per batch entry (t=1), gathered per 7x7 window.
@@ -478,6 +487,19 @@ int mumpy_window_attention_bwd_csr(const float* qkv, const float* dout, const fl
                                    const int32_t* mask_id, int n_mask, const int32_t* rel_index, const int32_t* rel_csr, float* dqkv,
                                    float* dtable, void* workspace, int64_t workspace_bytes, int B, int Hs, int W, int C, int shift,
                                    float scale, int accumulate, void* stream);
+/* The backward with bf16 matrix math for the fp32-stored tape (opt-in; pairs with mumpy_window_attention_mm16_fwd): fp32 qkv / dout in,
+ * fp32 dqkv / dtable out, operands rounded to bf16 (nearest even, r()) in registers, products on v_mfma_f32_32x32x16_bf16 with fp32
+ * accumulation, softmax and every statistic in fp32:
+ *   S = scale (r(q) r(k)^T) + bias (+ mask),  P = softmax(S),  dP = r(dO) r(v)^T,  D = rowsum(P o dP),  dS = P o (dP - D),
+ *   dV = r(P)^T r(dO),  dQ = scale r(dS) r(k),  dK = scale r(dS)^T r(q),  dtable from the fp32 dS.
+ * The argument list of mumpy_window_attention_bwd_csr; rel_csr may be NULL (the table gradient then scans rel_index).  Same validation
+ * and error codes, `accumulate` included.  Deterministic.
+ * workspace: mumpy_window_attention_mm16_bwd_workspace_bytes(B,Hs,W,C) bytes (0 for an invalid shape). */
+int64_t mumpy_window_attention_mm16_bwd_workspace_bytes(int B, int Hs, int W, int C);
+int mumpy_window_attention_mm16_bwd(const float* qkv, const float* dout, const float* bias, const float* mask_tab,
+                                    const int32_t* mask_id, int n_mask, const int32_t* rel_index, const int32_t* rel_csr, float* dqkv,
+                                    float* dtable, void* workspace, int64_t workspace_bytes, int B, int Hs, int W, int C, int shift,
+                                    float scale, int accumulate, void* stream);
 
 /* relative_position_bias_table (169,nH) gathered through relative_position_index (49*49, int32) into the padded bias the
  * attention kernels read: out (nH,64,64) [head][query][key], rows >= 49 zero, key columns >= 49 = -1e30 (swin:148-151).

@@ -419,9 +419,51 @@ __device__ __forceinline__ f32x16 mfma16(bf16x8 a, bf16x8 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 
+// 8 fp32 values -> one bf16 operand fragment, round to nearest even (v_cvt_pk_bf16_f32)
+__device__ __forceinline__ bf16x8 cvt8(f32x4 lo, f32x4 hi) {
+    bf16x8 r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { r[i] = (__bf16)lo[i]; r[4 + i] = (__bf16)hi[i]; }
+    return r;
+}
+
+// the [k-step] operand fragments of an fp32 head row: channels 16 st + 8h .. +7, rounded to bf16 in registers (off includes 32h)
+__device__ __forceinline__ void load_frag_bf16(bf16x8 (&f)[2], const char* base, uint32_t off) {
+#pragma unroll
+    for (int st = 0; st < 2; ++st) f[st] = cvt8(*at16(base, off + 64u * st), *at16(base, off + 64u * st + 16u));
+}
+
+// channel c of an fp32 operand's rows in the permuted order of an accumulator-fed A operand: element j of fragment [tile t][k-step st]
+// is row 32t + 16st + 8(j>>2) + 4h + (j&3) (4-byte gathers, rounded to bf16).  Rows 49..51 / 53.. are zero, row 52 is slot 48's value
+// (token table clamp): the A operand is exactly 0 on all of them.
+__device__ __forceinline__ void load_perm_bf16(bf16x8 (&f)[2][2], const char* base, const uint32_t* tab, int c, int h) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            bf16x8 v;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = (__bf16)0.f;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                if (t == 1 && st == 1 && q == 1) continue;                                 // rows 56..63: all padding
+                const u32x4 t4 = *reinterpret_cast<const u32x4*>(&tab[32 * t + 16 * st + 8 * q + 4 * h]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (t == 1 && st == 1 && e > 0) continue;                              // rows 49..51 / 53..55: padding in both halves
+                    v[4 * q + e] = (__bf16)*reinterpret_cast<const float*>(base + (t4[e] + 4u * c));
+                }
+            }
+            f[t][st] = v;
+        }
+}
+
+// IO32: qkv and out are fp32 in memory (the training tape, mumpy_window_attention_mm16_fwd): operands are rounded to bf16 in registers,
+// everything after the load and before the store is the same instruction stream, so the tape's forward has the P its backward rebuilds.
+template <bool IO32>
 __global__ __launch_bounds__(256, 3) void win_attn_self_bf16mm_kernel(SelfArgs a) {
-    __shared__ __attribute__((aligned(16))) uint32_t tok_in[4][64];    // token * (3C*2): byte offset of the token's qkv row
-    __shared__ __attribute__((aligned(16))) uint32_t tok_out[4][64];   // token * (C*2):  byte offset of the token's out row
+    __shared__ __attribute__((aligned(16))) uint32_t tok_in[4][64];    // token * (3C * esize): byte offset of the token's qkv row
+    __shared__ __attribute__((aligned(16))) uint32_t tok_out[4][64];   // token * (C * esize):  byte offset of the token's out row
     __shared__ __attribute__((aligned(16))) float inv_s[4][64];        // 1 / row sum of the unit's 64 query slots
     __shared__ __attribute__((aligned(16))) float bias_s[WT * BLD];
     const int lane = threadIdx.x & 63;
@@ -439,7 +481,7 @@ __global__ __launch_bounds__(256, 3) void win_attn_self_bf16mm_kernel(SelfArgs a
         __syncthreads();
     }
     const int64_t L = (int64_t)a.Hs * a.W;
-    const uint32_t rsb = 6u * a.C, rob = 2u * a.C;                       // row strides in bytes
+    const uint32_t rsb = (IO32 ? 12u : 6u) * a.C, rob = (IO32 ? 4u : 2u) * a.C;   // row strides in bytes
     uint32_t* ti = tok_in[wave];
     uint32_t* to = tok_out[wave];
     float* invw = inv_s[wave];
@@ -453,14 +495,21 @@ __global__ __launch_bounds__(256, 3) void win_attn_self_bf16mm_kernel(SelfArgs a
             to[lane] = tok * rob;
         }
         __builtin_amdgcn_wave_barrier();
-        const char* base = reinterpret_cast<const char*>(reinterpret_cast<const __bf16*>(a.qkv) + b * L * 3 * a.C + head * HD);
-        const char* kbase = base + 2 * a.C;
-        const char* vbase = base + 4 * a.C;
+        const char* base = IO32 ? reinterpret_cast<const char*>(a.qkv + b * L * 3 * a.C + head * HD)
+                                : reinterpret_cast<const char*>(reinterpret_cast<const __bf16*>(a.qkv) + b * L * 3 * a.C + head * HD);
+        const char* kbase = base + (IO32 ? 4 : 2) * a.C;
+        const char* vbase = base + (IO32 ? 8 : 4) * a.C;
 
-        // q / k: [tile][k-step] fragments, 16 bytes each, straight from memory
+        // q / k: [tile][k-step] fragments, 16 bytes each, straight from memory (IO32: 32 bytes, rounded on the way)
         bf16x8 qf[2][2], kf[2][2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
+            if (IO32) {
+                const uint32_t off = ti[32 * t + c] + 32u * h;
+                load_frag_bf16(qf[t], base, off);
+                load_frag_bf16(kf[t], kbase, off);
+                continue;
+            }
             const uint32_t off = ti[32 * t + c] + 16u * h;
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
@@ -470,8 +519,9 @@ __global__ __launch_bounds__(256, 3) void win_attn_self_bf16mm_kernel(SelfArgs a
         }
         // v: [key tile][k-step] fragments in the permuted key order of the P operand; element j = key 32jt + 16s + 8(j>>2) + 4h + (j&3)
         bf16x8 vf[2][2];
+        if (IO32) load_perm_bf16(vf, vbase, ti, c, h);
 #pragma unroll
-        for (int jt = 0; jt < 2; ++jt)
+        for (int jt = 0; jt < 2 && !IO32; ++jt)
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
                 u16x8 pk = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -493,7 +543,8 @@ __global__ __launch_bounds__(256, 3) void win_attn_self_bf16mm_kernel(SelfArgs a
             const int id = a.mask_id[bw % a.n_mask];   // scalar load
             if (id >= 0) mask_w = a.mask_tab + (int64_t)id * 4096;
         }
-        char* obase = reinterpret_cast<char*>(reinterpret_cast<__bf16*>(a.out) + b * L * a.C + head * HD);
+        char* obase = IO32 ? reinterpret_cast<char*>(a.out + b * L * a.C + head * HD)
+                           : reinterpret_cast<char*>(reinterpret_cast<__bf16*>(a.out) + b * L * a.C + head * HD);
         auto tiles = [&](auto masked) {
             constexpr bool MASKED = decltype(masked)::value;
 #pragma unroll
@@ -539,7 +590,10 @@ __global__ __launch_bounds__(256, 3) void win_attn_self_bf16mm_kernel(SelfArgs a
                     for (int e = 0; e < 4; ++e) {
                         if (it == 1 && g == 2 && e > 0) continue;                                    // statically >= 49
                         const int i = 32 * it + 8 * g + 4 * h + e;
-                        if (i < WT) *reinterpret_cast<__bf16*>(obase + (to4[e] + 2u * c)) = (__bf16)(o[4 * g + e] * iv[e]);
+                        if (i < WT) {
+                            if (IO32) *reinterpret_cast<float*>(obase + (to4[e] + 4u * c)) = o[4 * g + e] * iv[e];
+                            else *reinterpret_cast<__bf16*>(obase + (to4[e] + 2u * c)) = (__bf16)(o[4 * g + e] * iv[e]);
+                        }
                     }
                 }
             }
@@ -885,6 +939,357 @@ __global__ __launch_bounds__(256, 1) void win_attn_bwd_kv_kernel(BwdArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// bf16-MFMA form of the backward pair for the fp32-stored training tape (mumpy_window_attention_mm16_bwd; opt-in, see
+// ops.set_attention_math): every product on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, operands rounded to bf16 in registers
+// (round to nearest even), softmax, D, dS and the bias gradient in fp32.  Arithmetic, r(x) = bf16 rounding:
+//   S = scale (r(q) r(k)^T) + bias (+ mask)      (scale on the fp32 product as in the bf16-MFMA forward: q is rounded once, unscaled)
+//   P = softmax(S),  dP = r(dO) r(v)^T,  D = rowsum(P o dP),  dS = P o (dP - D)                                   [all fp32]
+//   dV = r(P)^T r(dO),  dQ = scale r(dS) r(k),  dK = scale r(dS)^T r(q),  dBias += dS (the fp32 dS, before it is rounded)
+// Same two-orientation scheme, unit walk, statistics record {m, 1/l, D} and dBias partial layout as the fp32 pair above, so the
+// reduce and table kernels are shared.  What differs: an operand fragment is 4 registers instead of 16 (2 k-steps of 8 bf16), P / dS go
+// from the accumulator to the A operand by a pairwise cast (k order permuted as in the bf16-MFMA forward; the B operand is gathered in
+// that order by load_perm_bf16), 8 + 8 + 8 MFMAs per unit and kernel instead of 64 + 64 + 50.  P and dS are exactly 0 on padded
+// keys / queries BEFORE they are rounded, so whatever finite value a clamped slot holds in the B operand is multiplied by 0.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): q kernel 248 VGPRs, kv kernel 240, 0 AGPRs, no scratch, 15.4 / 18.4 KB of
+// LDS per block: 2 waves per SIMD (the fp32 pair: 256 + 59 / 256 + 110 registers, 1 wave per SIMD).  What that took: one branch per unit on the
+// mask pointer (a branch inside the tile code lets LLVM sink the operand conversions past it, and every raw fp32 row is then live at once),
+// operand rows loaded in batches that are rounded before the next batch is issued (sched_barrier), dP^T one key tile at a time and twice
+// in the q kernel, one query tile at a time straight into dV / dK in the kv kernel, the unit's statistics through LDS.
+// Measured against the fp32 kernels on the same input (tools/kernel_micro.py winattn_bwd16 / winattn_mm16; profiles/bf16mm_window_attention_train.md):
+//   (B, Hs, W, C)      backward, all 4 launches: fp32 -> bf16 MFMA        forward: fp32 -> bf16 MFMA (fp32 I/O)   [us, MI355X, medians of 12 x 20
+//                        shift 0                 shift 3                    shift 0            shift 3             alternating launches; the shapes of
+//   (2, 280, 56, 128)   100.3 -> 70.2 (1.43x)   104.3 -> 73.3 (1.42x)      23.0 -> 15.2       24.2 -> 17.1        the B=2, T=5 training step]
+//   (2, 140, 28, 256)    72.5 -> 48.3 (1.50x)    74.7 -> 50.4 (1.48x)      15.4 -> 10.4       16.6 -> 11.4
+//   (2,  70, 14, 512)    44.2 -> 33.5 (1.32x)    46.2 -> 35.1 (1.31x)      10.3 -> 10.2       11.0 -> 10.5
+//   (2,  35,  7, 1024)   40.7 -> 30.0 (1.36x)     --                       10.4 -> 10.3        --
+//   (2,  56, 56,  96)    41.5 -> 31.3 (1.33x)    43.8 -> 32.6 (1.34x)      10.3 -> 10.0       10.9 -> 10.6
+//   (2,  28, 28, 192)    38.2 -> 28.0 (1.36x)    40.2 -> 29.2 (1.38x)      10.4 -> 10.3       10.8 -> 10.4
+//   (2,  14, 14, 384)    35.6 -> 26.1 (1.36x)    38.2 -> 28.0 (1.36x)      10.4 -> 10.3       11.2 -> 10.9
+//   (2,   7,  7, 768)    33.6 -> 26.4 (1.27x)     --                       10.3 -> 10.4        --
+// The backward figure is the whole entry (q, kv, dBias reduce, table kernel; four launches, so ~26 us is the eager launch rate: the six
+// small shapes are paced by it with either pair, as the forward's ~10 us).  In the graphed B=2 bf16 step (rocprofv3 --kernel-trace, 60
+// launches per step): q kernel 20.2 -> 15.7 us, kv kernel 19.8 -> 12.9, forward 11.8 -> 8.7; the step 34.0 -> 33.1 ms.  Persistent blocks
+// (MUMPY_WA_BWD16_BLOCKS, tuning build) on (2,280,56,128,3): 256 / 384 / 512 / 640 / 1024 -> 73.5 / 66.5 / 72.8 / 79.0 / 79.8 us; no other
+// training shape has more window quads than blocks, so none moves ((2,140,28,256,3): 53.8 at 256, else 49.9-50.8).  384 (96 groups for 160
+// quads) beats the shipped 512 on that one shape by 6 us; not adopted on a single shape and shift.
+__global__ __launch_bounds__(256, 2) void win_attn_bwd_q_bf16mm_kernel(BwdArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tok_in[4][64];
+    __shared__ __attribute__((aligned(16))) uint32_t tok_out[4][64];
+    __shared__ __attribute__((aligned(16))) float bias_s[WT * BLD];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int head = blockIdx.x % a.nH;
+    const int slot = blockIdx.x / a.nH;
+    const int64_t nwin = (int64_t)a.B * a.nW;
+    {
+        const float* bsrc = a.bias + (int64_t)head * 4096;
+        for (int idx = threadIdx.x; idx < WT * 16; idx += 256) {
+            const int row = idx >> 4, c4 = idx & 15;
+            *reinterpret_cast<f32x4*>(&bias_s[row * BLD + 4 * c4]) = *reinterpret_cast<const f32x4*>(bsrc + row * 64 + 4 * c4);
+        }
+    }
+    __syncthreads();
+    const int64_t L = (int64_t)a.Hs * a.W;
+    const uint32_t rsb = 12u * a.C, rob = 4u * a.C;
+    uint32_t* ti = tok_in[wave];
+    uint32_t* to = tok_out[wave];
+    f32x16 dsum[2][2];                                                    // running sum of the fp32 dS^T over this wave's units
+#pragma unroll
+    for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) dsum[it][jt][r] = 0.f;
+
+    for (int64_t bw = (int64_t)slot * 4 + wave; bw < nwin; bw += (int64_t)a.groups * 4) {
+        // (the mask lookup comes first: a branch between the loads and their conversions would pin all raw rows at once)
+        const float* mask_w = nullptr;
+        if (a.mask_id) {
+            const int id = a.mask_id[bw % a.n_mask];
+            if (id >= 0) mask_w = a.mask_tab + (int64_t)id * 4096;
+        }
+        const int n = (int)(bw % a.nW);
+        const int64_t b = bw / a.nW;
+        const int wy = n / a.nWx, wx = n - wy * a.nWx;
+        {
+            const uint32_t tok = (uint32_t)window_token(wy, wx, lane < WT ? lane : WT - 1, a.Hs, a.W, a.shift);   // padded slots -> slot 48
+            ti[lane] = tok * rsb;
+            to[lane] = tok * rob;
+        }
+        __builtin_amdgcn_wave_barrier();
+        const char* qb = reinterpret_cast<const char*>(a.qkv + b * L * 3 * a.C + head * HD);
+        const char* kb = qb + 4 * a.C;
+        const char* vb = qb + 8 * a.C;
+        const char* dob = reinterpret_cast<const char*>(a.dout + b * L * a.C + head * HD);
+        bf16x8 qf[2][2], kf[2][2], vkf[2][2], dof[2][2];                  // [tile][k-step]
+        bf16x8 kp[2][2];                                                  // K in the permuted key order of the dS operand, lane = channel
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint32_t off = ti[32 * t + c] + 32u * h;
+            load_frag_bf16(qf[t], qb, off);
+            load_frag_bf16(kf[t], kb, off);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // fp32 rows are twice their fragments: a batch is rounded before the next is issued
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            load_frag_bf16(vkf[t], vb, ti[32 * t + c] + 32u * h);
+            load_frag_bf16(dof[t], dob, to[32 * t + c] + 32u * h);
+        }
+        load_perm_bf16(kp, kb, ti, c, h);
+        __builtin_amdgcn_sched_barrier(0);
+        char* dqb = reinterpret_cast<char*>(a.dqkv + b * L * 3 * a.C + head * HD);
+        float* st = a.stats + (bw * a.nH + head) * 192;                   // {m[64], inv[64], D[64]} of this unit
+        // one branch per unit on the mask pointer, as in the forward: the tile code is straight-line, so nothing is sunk past a branch
+        auto tiles = [&](auto masked) {
+        constexpr bool MASKED = decltype(masked)::value;
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            f32x16 s[2];
+#pragma unroll
+            for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) s[jt][r] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                for (int jt = 0; jt < 2; ++jt) s[jt] = mfma16(kf[jt][ks], qf[it][ks], s[jt]);   // S^T = K Q^T
+            // dP^T = V dO^T, one key tile at a time and computed TWICE (for D, then for dS; the same bits both times): two MFMAs more
+            // per tile buy the 16 registers that keep the kernel at 2 waves per SIMD without scratch.  Chosen on the register count
+            // alone: the form that keeps dP^T (and spills, or runs one wave per SIMD) was never timed against this one.
+            auto dp_tile = [&](int jt) {
+                f32x16 t;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) t[r] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) t = mfma16(vkf[jt][ks], dof[it][ks], t);
+                return t;
+            };
+            const int qi = 32 * it + c;
+            const float* brow = &bias_s[(qi < WT ? qi : WT - 1) * BLD + 4 * h];
+            auto bias_at = [&](int jt, int g) {
+                f32x4 bv = *reinterpret_cast<const f32x4*>(brow + 32 * jt + 8 * g);
+                if (jt == 1 && g == 2 && h) bv.x = -1e30f;                // key 52 is padding (key 48 is real)
+                return bv;
+            };
+            float m, inv;
+            bias_softmax<MASKED>(s, bias_at, mask_w, qi, h, a.scale, &m, &inv);
+            float d = 0.f;
+#pragma unroll
+            for (int jt = 0; jt < 2; ++jt) {
+                const f32x16 dp = dp_tile(jt);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if (jt == 1 && r >= 9) continue;                      // P == 0 on padded keys
+                    d += s[jt][r] * dp[r];
+                }
+            }
+            d += __shfl_xor(d, 32);
+            const bool qvalid = qi < WT;
+#pragma unroll
+            for (int jt = 0; jt < 2; ++jt) {
+                const f32x16 dp = dp_tile(jt);
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    if (jt == 1 && r >= 9) { s[jt][r] = 0.f; continue; }
+                    const float ds = qvalid ? s[jt][r] * (dp[r] - d) : 0.f;        // padded queries contribute nothing
+                    s[jt][r] = ds;
+                    dsum[it][jt][r] += ds;
+                }
+            }
+            if (h == 0 && qvalid) { st[qi] = m; st[64 + qi] = inv; st[128 + qi] = d; }
+            f32x16 o;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) o[r] = 0.f;
+#pragma unroll
+            for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    bf16x8 df;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) df[j] = (__bf16)s[jt][8 * ks + j];
+                    o = mfma16(df, kp[jt][ks], o);                        // dQ = dS K   (rows = queries, lanes = channels)
+                }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (it == 1 && g == 3) continue;                          // queries 56..63: padding
+                const u32x4 ti4 = *reinterpret_cast<const u32x4*>(&ti[32 * it + 8 * g + 4 * h]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (it == 1 && g == 2 && e > 0) continue;             // statically >= 49
+                    const int i = 32 * it + 8 * g + 4 * h + e;
+                    if (i < WT) *reinterpret_cast<float*>(dqb + (ti4[e] + 4u * c)) = o[4 * g + e] * a.scale;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);   // one query tile at a time: interleaving the two doubles the live accumulators
+        }
+        };
+        if (mask_w) tiles(std::true_type{}); else tiles(std::false_type{});
+        __builtin_amdgcn_wave_barrier();   // the token tables are rewritten by the next unit
+    }
+    float* part = a.dbias_part + ((int64_t)blockIdx.x * 4 + wave) * 4096;  // [it][jt][r][lane]
+#pragma unroll
+    for (int it = 0; it < 2; ++it)
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) part[((it * 2 + jt) * 16 + r) * 64 + lane] = dsum[it][jt][r];
+}
+
+__global__ __launch_bounds__(256, 2) void win_attn_bwd_kv_bf16mm_kernel(BwdArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tok_in[4][64];
+    __shared__ __attribute__((aligned(16))) uint32_t tok_out[4][64];
+    __shared__ __attribute__((aligned(16))) float biasT_s[WT * BLD];      // bias^T: row = key j, column = query i
+    __shared__ __attribute__((aligned(16))) float stat_s[4][192];         // the unit's {m, 1/l, D}: one coalesced read, then 16-byte LDS reads
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int head = blockIdx.x % a.nH;
+    const int slot = blockIdx.x / a.nH;
+    const int64_t nwin = (int64_t)a.B * a.nW;
+    {
+        const float* bsrc = a.bias + (int64_t)head * 4096;
+        for (int idx = threadIdx.x; idx < WT * WT; idx += 256) {
+            const int i = idx / WT, j = idx - i * WT;
+            biasT_s[j * BLD + i] = bsrc[i * 64 + j];
+        }
+        for (int idx = threadIdx.x; idx < WT * (64 - WT); idx += 256) {   // query columns 49..63 of every key row: finite filler
+            const int j = idx / (64 - WT), i = WT + idx % (64 - WT);
+            biasT_s[j * BLD + i] = 0.f;
+        }
+    }
+    __syncthreads();
+    const int64_t L = (int64_t)a.Hs * a.W;
+    const uint32_t rsb = 12u * a.C, rob = 4u * a.C;
+    uint32_t* ti = tok_in[wave];
+    uint32_t* to = tok_out[wave];
+    float* st = stat_s[wave];
+    for (int64_t bw = (int64_t)slot * 4 + wave; bw < nwin; bw += (int64_t)a.groups * 4) {
+        // (the mask lookup comes first: a branch between the loads and their conversions would pin all raw rows at once)
+        const float* mask_w = nullptr;
+        if (a.mask_id) {
+            const int id = a.mask_id[bw % a.n_mask];
+            if (id >= 0) mask_w = a.mask_tab + (int64_t)id * 4096;
+        }
+        const int n = (int)(bw % a.nW);
+        const int64_t b = bw / a.nW;
+        const int wy = n / a.nWx, wx = n - wy * a.nWx;
+        {
+            const uint32_t tok = (uint32_t)window_token(wy, wx, lane < WT ? lane : WT - 1, a.Hs, a.W, a.shift);
+            ti[lane] = tok * rsb;
+            to[lane] = tok * rob;
+            // query slots 49..63 were never written by the q kernel: finite filler (their P / dS are forced to 0 below)
+            const float* sg = a.stats + (bw * a.nH + head) * 192;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) st[64 * k + lane] = lane < WT ? sg[64 * k + lane] : 0.f;
+        }
+        __builtin_amdgcn_wave_barrier();
+        const char* qb = reinterpret_cast<const char*>(a.qkv + b * L * 3 * a.C + head * HD);
+        const char* kb = qb + 4 * a.C;
+        const char* vb = qb + 8 * a.C;
+        const char* dob = reinterpret_cast<const char*>(a.dout + b * L * a.C + head * HD);
+        bf16x8 qf[2][2], kf[2][2], vkf[2][2], dof[2][2];                  // [tile][k-step]
+        bf16x8 qp[2][2], dop[2][2];                                       // q / dO in the permuted query order of the P / dS operand
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const uint32_t off = ti[32 * t + c] + 32u * h;
+            load_frag_bf16(qf[t], qb, off);
+            load_frag_bf16(kf[t], kb, off);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // fp32 rows are twice their fragments: a batch is rounded before the next is issued
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            load_frag_bf16(vkf[t], vb, ti[32 * t + c] + 32u * h);
+            load_frag_bf16(dof[t], dob, to[32 * t + c] + 32u * h);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        load_perm_bf16(qp, qb, ti, c, h);
+        load_perm_bf16(dop, dob, to, c, h);
+        __builtin_amdgcn_sched_barrier(0);
+        char* dkb = reinterpret_cast<char*>(a.dqkv + b * L * 3 * a.C + head * HD) + 4 * a.C;
+        char* dvb = dkb + 4 * a.C;
+        auto tiles = [&](auto masked) {                                   // one branch per unit on the mask pointer: straight-line tile code
+        constexpr bool MASKED = decltype(masked)::value;
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt) {
+            const int kj = 32 * jt + c;                                   // lane = key 32jt+c, accumulator rows = queries
+            const int kjc = kj < WT ? kj : WT - 1;
+            const float* brow = &biasT_s[kjc * BLD + 4 * h];
+            f32x16 ov, ok;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { ov[r] = 0.f; ok[r] = 0.f; }
+            // one query tile at a time, straight into dV / dK: S and dP of one tile are live (32 registers), not of both
+#pragma unroll
+            for (int it = 0; it < 2; ++it) {
+                f32x4 mk[4];                                              // the key's mask row (the mask is symmetric in (i, j)): issued before the MFMAs
+                if (MASKED) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+                        if (!(it == 1 && g == 3)) mk[g] = *reinterpret_cast<const f32x4*>(mask_w + kjc * 64 + 32 * it + 8 * g + 4 * h);
+                }
+                f32x16 s, dp;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    s = mfma16(qf[it][ks], kf[jt][ks], s);                // S = Q K^T   (A = q rows, B = k rows)
+                    dp = mfma16(dof[it][ks], vkf[jt][ks], dp);            // dP = dO V^T
+                }
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    if (it == 1 && g == 3) {                              // queries 56..63: padding
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) { s[4 * g + e] = 0.f; dp[4 * g + e] = 0.f; }
+                        continue;
+                    }
+                    const int i0 = 32 * it + 8 * g + 4 * h;               // this lane's 4 consecutive queries i0 .. i0+3
+                    const f32x4 bv = *reinterpret_cast<const f32x4*>(brow + 32 * it + 8 * g);
+                    const f32x4 mv = *reinterpret_cast<const f32x4*>(st + i0);
+                    const f32x4 iv = *reinterpret_cast<const f32x4*>(st + 64 + i0);
+                    const f32x4 dv = *reinterpret_cast<const f32x4*>(st + 128 + i0);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const bool valid = (i0 + e < WT) && (kj < WT);
+                        float x = s[4 * g + e] * a.scale + bv[e];                          // the operation order of bias_softmax
+                        if (MASKED) x += mk[g][e];
+                        const float pr = valid ? __expf(x - mv[e]) * iv[e] : 0.f;
+                        s[4 * g + e] = pr;                                                 // P
+                        dp[4 * g + e] = valid ? pr * (dp[4 * g + e] - dv[e]) : 0.f;        // dS
+                    }
+                }
+#pragma unroll
+                for (int ks = 0; ks < 2; ++ks) {
+                    bf16x8 pf, df;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) { pf[j] = (__bf16)s[8 * ks + j]; df[j] = (__bf16)dp[8 * ks + j]; }
+                    ov = mfma16(pf, dop[it][ks], ov);                     // dV = P^T dO   (sum over all 64 query slots)
+                    ok = mfma16(df, qp[it][ks], ok);                      // dK = dS^T Q
+                }
+                __builtin_amdgcn_sched_barrier(0);   // the tiles one after the other: interleaved, their accumulators are all live at once
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (jt == 1 && g == 3) continue;                          // keys 56..63: padding
+                const u32x4 ti4 = *reinterpret_cast<const u32x4*>(&ti[32 * jt + 8 * g + 4 * h]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (jt == 1 && g == 2 && e > 0) continue;             // statically >= 49
+                    const int j = 32 * jt + 8 * g + 4 * h + e;
+                    if (j < WT) {
+                        *reinterpret_cast<float*>(dvb + (ti4[e] + 4u * c)) = ov[4 * g + e];
+                        *reinterpret_cast<float*>(dkb + (ti4[e] + 4u * c)) = ok[4 * g + e] * a.scale;
+                    }
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        };
+        if (mask_w) tiles(std::true_type{}); else tiles(std::false_type{});
+        __builtin_amdgcn_wave_barrier();   // the token tables are rewritten by the next unit
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // backward of the deformable cross-view attention core (deform:360-395 in window form): unit = (kv window b2, head);
 // q from q window b2 % B1w (x1.repeat, deform:330), k/v from kv[b2], dO from output window b2 / r (the r-tuple sum,
 // deform:394-395, hands the same dO to its r members).  Same two-orientation scheme as the self-attention backward;
@@ -1157,15 +1562,16 @@ static int window_attention_launch(int kind, const float* qkv, float* out, const
     a.groups = (int)groups; a.stagger = wa_stagger;
     const int64_t grid = groups * a.nH;
     const bool io16 = kind == 1;
-    if (kind == 3) {
-        // bf16-MFMA kernel: 4 resident blocks per CU; the quads are dealt evenly (every block walks the same number of them, +-0)
+    if (kind == 3 || kind == 4) {
+        // bf16-MFMA kernel (3: bf16 storage, 4: fp32 storage): 4 resident blocks per CU; the quads are dealt evenly (every block walks the same number of them, +-0)
         static const int wa16_blocks = tune_int("MUMPY_WA16_BLOCKS", 1024);
         int64_t g16 = (wa16_blocks + a.nH - 1) / a.nH;
         if (g16 > quads) g16 = quads;
         const int64_t per = (quads + g16 - 1) / g16;
         g16 = (quads + per - 1) / per;
         a.groups = (int)g16;
-        hipLaunchKernelGGL(win_attn_self_bf16mm_kernel, dim3((unsigned)(g16 * a.nH)), dim3(256), 0, as_stream(stream), a);
+        if (kind == 4) hipLaunchKernelGGL(win_attn_self_bf16mm_kernel<true>, dim3((unsigned)(g16 * a.nH)), dim3(256), 0, as_stream(stream), a);
+        else hipLaunchKernelGGL(win_attn_self_bf16mm_kernel<false>, dim3((unsigned)(g16 * a.nH)), dim3(256), 0, as_stream(stream), a);
     } else if (kind == 2) hipLaunchKernelGGL((win_attn_self_kernel<false, false, true>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     else if (io16) hipLaunchKernelGGL((win_attn_self_kernel<false, true>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     else if (dbgmask) hipLaunchKernelGGL((win_attn_self_kernel<true, false>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
@@ -1205,6 +1611,14 @@ extern "C" int mumpy_window_attention_bf16mm_fwd(const void* qkv, void* out, con
                                    B, Hs, W, C, shift, scale, stream);
 }
 
+// fp32 storage, bf16 matrix math: the forward of the training tape under ops.set_attention_math("bf16").  Same arguments, validation
+// and error codes as mumpy_window_attention_fwd; `scale` multiplies the fp32 scores after the product.
+extern "C" int mumpy_window_attention_mm16_fwd(const float* qkv, float* out, const float* bias, const float* mask_tab,
+                                               const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift,
+                                               float scale, void* stream) {
+    return window_attention_launch(4, qkv, out, bias, mask_tab, mask_id, n_mask, B, Hs, W, C, shift, scale, stream);
+}
+
 extern "C" int mumpy_deform_attention_fwd(const float* q, const float* kv, const float* padmask, float* out, int B,
                                           int H, int W, int C, int r, float scale, void* stream) {
     MUMPY_REQUIRE(q && kv && padmask && out, MUMPY_ENULL, "deform_attention: null pointer");
@@ -1225,22 +1639,32 @@ extern "C" int mumpy_deform_attention_fwd(const float* q, const float* kv, const
     return 0;
 }
 
-static int64_t wa_bwd_groups(int B, int nW, int nH) {
+static int64_t wa_bwd_groups(int B, int nW, int nH, bool mm16 = false) {
     const int64_t quads = ((int64_t)B * nW + 3) / 4;
     static const int target = tune_int("MUMPY_WA_BWD_BLOCKS", 256);
-    int64_t groups = (target + nH - 1) / nH;              // ~one 4-wave block per CU (1 wave per SIMD)
+    static const int target16 = tune_int("MUMPY_WA_BWD16_BLOCKS", 512);
+    // fp32 pair: ~one 4-wave block per CU (1 wave per SIMD); bf16-MFMA pair: two (2 waves per SIMD)
+    int64_t groups = ((mm16 ? target16 : target) + nH - 1) / nH;
     return groups > quads ? quads : groups;
 }
 
-extern "C" int64_t mumpy_window_attention_bwd_workspace_bytes(int B, int Hs, int W, int C) {
+static int64_t wa_bwd_workspace_bytes(int B, int Hs, int W, int C, bool mm16) {
     if (B <= 0 || Hs <= 0 || W <= 0 || C <= 0 || Hs % WS || W % WS || C % HD) return 0;
     const int nW = (Hs / WS) * (W / WS), nH = C / HD;
     const int64_t stats = (int64_t)B * nW * nH * 192;
-    const int64_t part = wa_bwd_groups(B, nW, nH) * nH * 4 * 4096;
+    const int64_t part = wa_bwd_groups(B, nW, nH, mm16) * nH * 4 * 4096;
     return (stats + part + (int64_t)nH * 4096) * (int64_t)sizeof(float);
 }
 
-static int window_attention_bwd_impl(const float* qkv, const float* dout, const float* bias, const float* mask_tab,
+extern "C" int64_t mumpy_window_attention_bwd_workspace_bytes(int B, int Hs, int W, int C) {
+    return wa_bwd_workspace_bytes(B, Hs, W, C, false);
+}
+
+extern "C" int64_t mumpy_window_attention_mm16_bwd_workspace_bytes(int B, int Hs, int W, int C) {
+    return wa_bwd_workspace_bytes(B, Hs, W, C, true);
+}
+
+static int window_attention_bwd_impl(bool mm16, const float* qkv, const float* dout, const float* bias, const float* mask_tab,
                                           const int32_t* mask_id, int n_mask, const int32_t* rel_index, const int32_t* rel_csr, float* dqkv,
                                           float* dtable, void* workspace, int64_t workspace_bytes, int B, int Hs, int W, int C,
                                           int shift, float scale, int accumulate, void* stream) {
@@ -1254,21 +1678,23 @@ static int window_attention_bwd_impl(const float* qkv, const float* dout, const 
                   "window_attention_bwd: grid (%d,%d) not divisible by window 7", Hs, W);
     MUMPY_REQUIRE(C > 0 && C % HD == 0 && shift >= 0 && shift < WS, MUMPY_EINVAL, "window_attention_bwd: bad C=%d / shift=%d", C, shift);
     MUMPY_REQUIRE(mask_id == nullptr || n_mask > 0, MUMPY_EINVAL, "window_attention_bwd: n_mask must be > 0 with a mask");
-    MUMPY_REQUIRE(workspace_bytes >= mumpy_window_attention_bwd_workspace_bytes(B, Hs, W, C), MUMPY_EINVAL,
+    MUMPY_REQUIRE(workspace_bytes >= wa_bwd_workspace_bytes(B, Hs, W, C, mm16), MUMPY_EINVAL,
                   "window_attention_bwd: workspace too small");
     BwdArgs a;
     a.qkv = qkv; a.dout = dout; a.bias = bias; a.mask_tab = mask_tab; a.mask_id = mask_id; a.dqkv = dqkv;
     a.B = B; a.Hs = Hs; a.W = W; a.C = C; a.nH = C / HD; a.shift = shift; a.nWx = W / WS; a.nW = (Hs / WS) * (W / WS);
     a.n_mask = n_mask > 0 ? n_mask : 1; a.scale = scale;
-    a.groups = (int)wa_bwd_groups(B, a.nW, a.nH);
+    a.groups = (int)wa_bwd_groups(B, a.nW, a.nH, mm16);
     float* ws = static_cast<float*>(workspace);
     a.stats = ws;
     a.dbias_part = ws + (int64_t)B * a.nW * a.nH * 192;
     float* full = a.dbias_part + (int64_t)a.groups * a.nH * 4 * 4096;
     const unsigned grid = (unsigned)(a.groups * a.nH);
-    hipLaunchKernelGGL(win_attn_bwd_q_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
+    if (mm16) hipLaunchKernelGGL(win_attn_bwd_q_bf16mm_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
+    else hipLaunchKernelGGL(win_attn_bwd_q_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
     MUMPY_CHECK_LAUNCH("window_attention_bwd(q)");
-    hipLaunchKernelGGL(win_attn_bwd_kv_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
+    if (mm16) hipLaunchKernelGGL(win_attn_bwd_kv_bf16mm_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
+    else hipLaunchKernelGGL(win_attn_bwd_kv_kernel, dim3(grid), dim3(256), 0, as_stream(stream), a);
     MUMPY_CHECK_LAUNCH("window_attention_bwd(kv)");
     hipLaunchKernelGGL(win_attn_dbias_reduce_kernel, dim3(64, a.nH), dim3(256), 0, as_stream(stream), a.dbias_part, full, a.nH,
                        (int)grid);
@@ -1288,7 +1714,7 @@ extern "C" int mumpy_window_attention_bwd(const float* qkv, const float* dout, c
                                           const int32_t* mask_id, int n_mask, const int32_t* rel_index, float* dqkv,
                                           float* dtable, void* workspace, int64_t workspace_bytes, int B, int Hs, int W, int C,
                                           int shift, float scale, int accumulate, void* stream) {
-    return window_attention_bwd_impl(qkv, dout, bias, mask_tab, mask_id, n_mask, rel_index, nullptr, dqkv, dtable, workspace,
+    return window_attention_bwd_impl(false, qkv, dout, bias, mask_tab, mask_id, n_mask, rel_index, nullptr, dqkv, dtable, workspace,
                                      workspace_bytes, B, Hs, W, C, shift, scale, accumulate, stream);
 }
 
@@ -1297,7 +1723,17 @@ extern "C" int mumpy_window_attention_bwd_csr(const float* qkv, const float* dou
                                               float* dqkv, float* dtable, void* workspace, int64_t workspace_bytes, int B, int Hs, int W,
                                               int C, int shift, float scale, int accumulate, void* stream) {
     MUMPY_REQUIRE(rel_csr, MUMPY_ENULL, "window_attention_bwd_csr: null inverse index");
-    return window_attention_bwd_impl(qkv, dout, bias, mask_tab, mask_id, n_mask, rel_index, rel_csr, dqkv, dtable, workspace,
+    return window_attention_bwd_impl(false, qkv, dout, bias, mask_tab, mask_id, n_mask, rel_index, rel_csr, dqkv, dtable, workspace,
+                                     workspace_bytes, B, Hs, W, C, shift, scale, accumulate, stream);
+}
+
+// bf16 matrix math on the fp32-stored tape (opt-in): the argument list of mumpy_window_attention_bwd_csr; rel_csr may be null (the
+// index-scanning table kernel); workspace from mumpy_window_attention_mm16_bwd_workspace_bytes.
+extern "C" int mumpy_window_attention_mm16_bwd(const float* qkv, const float* dout, const float* bias, const float* mask_tab,
+                                               const int32_t* mask_id, int n_mask, const int32_t* rel_index, const int32_t* rel_csr,
+                                               float* dqkv, float* dtable, void* workspace, int64_t workspace_bytes, int B, int Hs, int W,
+                                               int C, int shift, float scale, int accumulate, void* stream) {
+    return window_attention_bwd_impl(true, qkv, dout, bias, mask_tab, mask_id, n_mask, rel_index, rel_csr, dqkv, dtable, workspace,
                                      workspace_bytes, B, Hs, W, C, shift, scale, accumulate, stream);
 }
 

@@ -203,7 +203,10 @@ def drop_path_train(module, x):
 
 
 class WindowAttentionFn(torch.autograd.Function):
-    """softmax(q k^T * scale + bias + mask) v on raster-ordered qkv; differentiable in qkv and the bias table."""
+    """softmax(q k^T * scale + bias + mask) v on raster-ordered qkv; differentiable in qkv and the bias table.  The arithmetic is
+    ops.attention_math() AT THE FORWARD: "bf16" runs the bf16-MFMA forward and, whatever the switch says by then, its own backward.
+    The bf16-MFMA forward has no LDS-free "background" form (mumpy_window_attention_bg_fwd): inside ops.background() it is the regular
+    kernel that is launched -- same results, but no co-residency with the persistent GEMM."""
 
     @staticmethod
     def forward(ctx, qkv, table, rel_index, dims, mask_tab, mask_id):
@@ -213,14 +216,17 @@ class WindowAttentionFn(torch.autograd.Function):
         ctx.save_for_backward(qkv, bias_pad, idx32, ops.rel_index_csr(rel_index))      # (both index images are cached on the buffer)
         ctx.dims, ctx.mask = dims, (mask_tab, mask_id)
         ctx.table = table
-        return ops.window_attention(qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id)
+        ctx.math = ops.attention_math()
+        fwd = ops.window_attention_mm16 if ctx.math == "bf16" else ops.window_attention
+        return fwd(qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id)
 
     @staticmethod
     def backward(ctx, dout):
         qkv, bias_pad, idx32, csr = ctx.saved_tensors
         b, hs, w, c, shift, scale = ctx.dims
         dqkv, dtable = ops.window_attention_bwd(qkv, dout.contiguous(), bias_pad, idx32, b, hs, w, c, shift, scale, *ctx.mask,
-                                                dtable_out=_grad_slot(ctx.table) if ctx.needs_input_grad[1] else None, rel_csr=csr)
+                                                dtable_out=_grad_slot(ctx.table) if ctx.needs_input_grad[1] else None, rel_csr=csr,
+                                                math=ctx.math)
         return dqkv, dtable, None, None, None, None
 
 

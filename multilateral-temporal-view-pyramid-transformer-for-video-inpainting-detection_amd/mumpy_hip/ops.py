@@ -152,12 +152,17 @@ _ATTN_MATH = _attn_math_from_env()       # read once, at import
 
 
 def set_attention_math(mode: str) -> None:
-    """Arithmetic of the Swin window attention core when qkv is STORED as bf16 (set_storage("bf16")).  "fp32" (default): the bf16
-    values are widened and the unit runs the fp32 MFMA flow (mumpy_window_attention_bf16_fwd).  "bf16": Q K^T and P V run on
-    the bf16 MFMA with fp32 accumulation and an fp32 softmax (mumpy_window_attention_bf16mm_fwd; forward only).  fp32 qkv always
-    runs the fp32 kernels, and set_storage does not touch this switch.  The initial value is the environment variable
-    MUMPY_ATTN_MATH, read when this module is imported.  Like set_storage it is read at launch time: set it BEFORE a
-    GraphedForward is captured -- a captured graph keeps the kernels it was captured with."""
+    """Arithmetic of the Swin window attention core in the two places that have a bf16-MFMA form.  "fp32" (default): the fp32 MFMA
+    flow everywhere.  "bf16": Q K^T, P V and the backward's products run on the bf16 MFMA with fp32 accumulation and an fp32 softmax
+      * when qkv is STORED as bf16 (set_storage("bf16")): mumpy_window_attention_bf16mm_fwd instead of the widening
+        mumpy_window_attention_bf16_fwd (inference forward);
+      * on the TRAINING TAPE (autograd.WindowAttentionFn, so swin_block_train and the full training step): activations stay fp32 in
+        memory, the operands are rounded to bf16 in registers -- window_attention_mm16 in the forward, window_attention_bwd(...,
+        math="bf16") in the backward.  The mode is read in the tape's forward and carried to its backward.
+    Direct ops.window_attention / ops.window_attention_bwd calls on fp32 qkv never follow the switch (window_attention_bwd takes an
+    explicit math=), and set_storage does not touch it.  The initial value is the environment variable MUMPY_ATTN_MATH, read when
+    this module is imported.  Like set_storage it is read at launch time: set it BEFORE a GraphedForward or a graphed training step
+    is captured -- a captured graph keeps the kernels it was captured with."""
     global _ATTN_MATH
     if mode not in ("fp32", "bf16"):
         raise ValueError(f"unknown attention math mode {mode!r}")
@@ -629,6 +634,20 @@ def window_attention(qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, ma
     return out
 
 
+def window_attention_mm16(qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, out=None):
+    """window_attention with bf16 matrix math on fp32 storage: q / k / v are rounded to bf16 in registers, both products run on the
+    bf16 MFMA (fp32 accumulation, fp32 softmax), the fp32 output is stored unrounded.  The forward of the training tape under
+    set_attention_math("bf16"); its backward is window_attention_bwd(..., math="bf16")."""
+    qkv = _chk(qkv, "qkv")
+    if qkv.numel() != b * hs * w * 3 * c:
+        raise RuntimeError("window_attention_mm16: qkv shape mismatch")
+    out = torch.empty(b, hs * w, c, device=qkv.device, dtype=torch.float32) if out is None else out
+    n_mask = 0 if mask_id is None else mask_id.numel()
+    _call("mumpy_window_attention_mm16_fwd", _p(qkv), _p(out), _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
+          b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
+    return out
+
+
 def deform_offsets(q, dw_w, dw_b, ln_g, ln_b, pw_w, b, h, w, c):
     q = _chk(q, "q")
     nwin = b * (h // 7) * (w // 7)
@@ -1006,10 +1025,13 @@ def rel_index_csr(index: torch.Tensor) -> torch.Tensor:
 
 
 def window_attention_bwd(qkv, dout, bias_pad, rel_index32, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, dtable_out=None,
-                         rel_csr=None):
+                         rel_csr=None, math="fp32"):
     """-> (dqkv (B, hs*w, 3C), dtable (169, C/32)): gradients of the W-MSA core wrt qkv and the relative position bias table.
     dtable_out: a gradient buffer to ACCUMULATE into (the returned dtable is then None).  rel_csr = rel_index_csr(index): the table
-    gradient reads its pairs through the inverse index instead of scanning the index."""
+    gradient reads its pairs through the inverse index instead of scanning the index.  math: "fp32" (default; it does NOT follow
+    set_attention_math) or "bf16", the backward of window_attention_mm16 (mumpy_window_attention_mm16_bwd)."""
+    if math not in ("fp32", "bf16"):
+        raise ValueError(f"unknown attention math mode {math!r}")
     qkv, dout = _chk(qkv, "qkv"), _chk(dout, "dout")
     if qkv.numel() != b * hs * w * 3 * c or dout.numel() != b * hs * w * c:
         raise RuntimeError("window_attention_bwd: shape mismatch")
@@ -1020,13 +1042,19 @@ def window_attention_bwd(qkv, dout, bias_pad, rel_index32, b, hs, w, c, shift, s
     dtable = _chk(dtable_out, "dtable_out") if acc else torch.empty(169, c // 32, device=qkv.device, dtype=torch.float32)
     if dtable.shape != (169, c // 32):
         raise RuntimeError(f"window_attention_bwd: table gradient buffer {tuple(dtable.shape)} != {(169, c // 32)}")
-    wsb = _ws_bytes(("wabwd", b, hs, w, c), "mumpy_window_attention_bwd_workspace_bytes", b, hs, w, c)
+    if math == "bf16":
+        wsb = _ws_bytes(("wabwd16", b, hs, w, c), "mumpy_window_attention_mm16_bwd_workspace_bytes", b, hs, w, c)
+    else:
+        wsb = _ws_bytes(("wabwd", b, hs, w, c), "mumpy_window_attention_bwd_workspace_bytes", b, hs, w, c)
     ws = _ws(wsb, qkv.device)
     n_mask = 0 if mask_id is None else mask_id.numel()
     if rel_csr is not None and (rel_csr.dtype != torch.int32 or rel_csr.numel() != 170 + 49 * 49 or rel_csr.device != qkv.device):
         raise RuntimeError("window_attention_bwd: rel_csr must come from ops.rel_index_csr on this device")
-    csr_args = () if rel_csr is None else (_p(rel_csr),)
-    _call("mumpy_window_attention_bwd" + ("" if rel_csr is None else "_csr"), _p(qkv), _p(dout), _p(_chk(bias_pad, "bias")), _p(mask_tab),
+    if math == "bf16":
+        name, csr_args = "mumpy_window_attention_mm16_bwd", (_p(rel_csr),)        # one entry: a null rel_csr selects the scanning kernel
+    else:
+        name, csr_args = "mumpy_window_attention_bwd" + ("" if rel_csr is None else "_csr"), (() if rel_csr is None else (_p(rel_csr),))
+    _call(name, _p(qkv), _p(dout), _p(_chk(bias_pad, "bias")), _p(mask_tab),
           _p(mask_id), n_mask, _p(rel_index32.contiguous()), *csr_args, _p(dqkv), _p(dtable), _p(ws), wsb, b, hs, w, c, shift, scale, int(acc), _stream(),
           work=5 * 153664.0 * b * (hs // 7) * (w // 7) * (c // 32))
     return dqkv, (None if acc else dtable)

@@ -1,6 +1,7 @@
 """Training tail of config 5: parameter groups, fused AdamW / SGD / RMSprop on flat buffers, the polynomial LR
-schedule and the bucketed gradient all-reduce.  The model backward itself is not part of this round (forward kernels only), so these
-pieces are exercised on their own: loss + gradient wrt the logits, optimizer update, schedule, collective.
+schedule and the bucketed gradient all-reduce.  The model backward lives in mumpy_hip/autograd.py (full_model_train and the graphed
+step built on it); the pieces here are also exercised on their own: loss + gradient wrt the logits, optimizer update, schedule,
+collective.
 
 Reference behaviour reproduced:
   * three optimizers: encoder parameters whose name contains "cva" / the other encoder parameters / the decoder

@@ -4,7 +4,11 @@
   | kernel_micro.py winattn_bwd B Hs W C shift | kernel_micro.py ln_bwd rows C
   | kernel_micro.py adamw N | kernel_micro.py maskloss B P | kernel_micro.py ln rows C
   | kernel_micro.py winattn16 B Hs W C shift    bf16-stored qkv: the fp32-flow kernel and the bf16-MFMA kernel on the same input,
-                                                alternating in one process (ROUNDS rounds of REPS launches each, default 12 x 20)"""
+                                                alternating in one process (ROUNDS rounds of REPS launches each, default 12 x 20)
+  | kernel_micro.py winattn_mm16 B Hs W C shift   fp32-stored qkv: mumpy_window_attention_fwd and the bf16-MFMA forward of the training
+                                                tape (window_attention_mm16) on the same input, same alternating protocol
+  | kernel_micro.py winattn_bwd16 B Hs W C shift  the fp32 backward pair and the bf16-MFMA pair (window_attention_bwd math="fp32" /
+                                                "bf16", each with its reduce and table kernels) on the same input, same protocol"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "multilateral-temporal-view-pyramid-transformer-for-video-inpainting-detection_amd")]
@@ -39,6 +43,41 @@ if op == "winattn16":
     gb = 2.0 * 4 * b * hs * w * c / 1e3            # bf16 q, k, v read + out written, per us -> GB/s
     print(f"winattn16 {a}: fp32-flow {med['fp32']:.1f} us [{min(times['fp32']):.1f}..{max(times['fp32']):.1f}], "
           f"bf16-MFMA {med['bf16']:.1f} us [{min(times['bf16']):.1f}..{max(times['bf16']):.1f}] ({gb / med['bf16']:.0f} GB/s), "
+          f"fp32/bf16 = {med['fp32'] / med['bf16']:.2f}  (median of {rounds} rounds x {reps} launches, alternating)")
+    sys.exit(0)
+if op in ("winattn_mm16", "winattn_bwd16"):
+    b, hs, w, c, shift = a
+    from models.modules.swinTransformer import build_shift_mask, relative_position_index
+    qkv = torch.randn(b, hs * w, 3 * c, device=dev); dout = torch.randn(b, hs * w, c, device=dev)
+    idx = relative_position_index(7, 7).to(dev)
+    bias = ops.expand_relpos_bias(torch.randn(169, c // 32, device=dev) * 0.2, idx)
+    idx32, csr = ops.rel_index32(idx), ops.rel_index_csr(idx)
+    tab = ids = None
+    if shift:
+        tab, ids = ops.compact_attn_mask(build_shift_mask(hs, w, 7, shift).to(dev))
+    if op == "winattn_mm16":
+        run = {"fp32": lambda: ops.window_attention(qkv, bias, b, hs, w, c, shift, 32 ** -0.5, tab, ids),
+               "bf16": lambda: ops.window_attention_mm16(qkv, bias, b, hs, w, c, shift, 32 ** -0.5, tab, ids)}
+    else:
+        run = {m: (lambda m=m: ops.window_attention_bwd(qkv, dout, bias, idx32, b, hs, w, c, shift, 32 ** -0.5, tab, ids, rel_csr=csr, math=m))
+               for m in ("fp32", "bf16")}
+    rounds = int(os.environ.get("ROUNDS", "12"))
+    times = {"fp32": [], "bf16": []}
+    for math in ("fp32", "bf16"):
+        for _ in range(5):
+            run[math]()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for math in ("fp32", "bf16"):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                run[math]()
+            e1.record(); torch.cuda.synchronize()
+            times[math].append(e0.elapsed_time(e1) * 1e3 / reps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    print(f"{op} {a}: fp32 {med['fp32']:.1f} us [{min(times['fp32']):.1f}..{max(times['fp32']):.1f}], "
+          f"bf16-MFMA {med['bf16']:.1f} us [{min(times['bf16']):.1f}..{max(times['bf16']):.1f}], "
           f"fp32/bf16 = {med['fp32'] / med['bf16']:.2f}  (median of {rounds} rounds x {reps} launches, alternating)")
     sys.exit(0)
 if op == "linear":
