@@ -1,6 +1,6 @@
 // deform.hip — the non-GEMM parts of SwinDAttention (deform:324-405) and of its caller's residual wiring
 // (mTVE:138, 280-286): offset network, bilinear sampling, and the "scrambled" combine.
-// The attention + r-tuple aggregation lives in window_attention.hip (win_attn_cross_kernel); q/k/v/out projections
+// The attention + r-tuple aggregation lives in deform_attention.hip (win_attn_cross_kernel); q/k/v/out projections
 // and `pre` are mumpy_linear_fwd.
 #include <stdlib.h>
 #include "common.h"

@@ -173,6 +173,18 @@ def attention_math() -> str:
     return _ATTN_MATH
 
 
+def _window_attention(entry, chk, dtype, who, qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id, out=None):
+    """One body for the window-attention forward entries: C-ABI entry name, input check (_chk / _chk16) and output dtype."""
+    qkv = chk(qkv, "qkv")
+    if qkv.numel() != b * hs * w * 3 * c:
+        raise RuntimeError(f"{who}: qkv shape mismatch")
+    out = torch.empty(b, hs * w, c, device=qkv.device, dtype=dtype) if out is None else out
+    n_mask = 0 if mask_id is None else mask_id.numel()
+    _call(entry, _p(qkv), _p(out), _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
+          b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
+    return out
+
+
 def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, math=None):
     """bf16 qkv (B, hs*w, 3C) -> bf16 (B, hs*w, C).  math: None follows attention_math(); "fp32" / "bf16" force the fp32-flow /
     the bf16-MFMA kernel."""
@@ -180,15 +192,8 @@ def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=N
         math = _ATTN_MATH
     elif math not in ("fp32", "bf16"):
         raise ValueError(f"unknown attention math mode {math!r}")
-    qkv16 = _chk16(qkv16, "qkv")
-    if qkv16.numel() != b * hs * w * 3 * c:
-        raise RuntimeError("window_attention_bf16: qkv shape mismatch")
-    out = torch.empty(b, hs * w, c, device=qkv16.device, dtype=torch.bfloat16)
-    n_mask = 0 if mask_id is None else mask_id.numel()
-    _call("mumpy_window_attention_bf16mm_fwd" if math == "bf16" else "mumpy_window_attention_bf16_fwd", _p(qkv16), _p(out),
-          _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
-          b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
-    return out
+    return _window_attention("mumpy_window_attention_bf16mm_fwd" if math == "bf16" else "mumpy_window_attention_bf16_fwd", _chk16,
+                             torch.bfloat16, "window_attention_bf16", qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -624,28 +629,16 @@ def compact_attn_mask(mask: torch.Tensor):
 
 def window_attention(qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, out=None):
     """qkv (B, hs*w, 3C) raster -> (B, hs*w, C) raster attention output (before proj)."""
-    qkv = _chk(qkv, "qkv")
-    if qkv.numel() != b * hs * w * 3 * c:
-        raise RuntimeError("window_attention: qkv shape mismatch")
-    out = torch.empty(b, hs * w, c, device=qkv.device, dtype=torch.float32) if out is None else out
-    n_mask = 0 if mask_id is None else mask_id.numel()
-    _call("mumpy_window_attention_bg_fwd" if _in_background() else "mumpy_window_attention_fwd", _p(qkv), _p(out), _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
-          b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
-    return out
+    return _window_attention("mumpy_window_attention_bg_fwd" if _in_background() else "mumpy_window_attention_fwd", _chk, torch.float32,
+                             "window_attention", qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id, out)
 
 
 def window_attention_mm16(qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, out=None):
     """window_attention with bf16 matrix math on fp32 storage: q / k / v are rounded to bf16 in registers, both products run on the
     bf16 MFMA (fp32 accumulation, fp32 softmax), the fp32 output is stored unrounded.  The forward of the training tape under
     set_attention_math("bf16"); its backward is window_attention_bwd(..., math="bf16")."""
-    qkv = _chk(qkv, "qkv")
-    if qkv.numel() != b * hs * w * 3 * c:
-        raise RuntimeError("window_attention_mm16: qkv shape mismatch")
-    out = torch.empty(b, hs * w, c, device=qkv.device, dtype=torch.float32) if out is None else out
-    n_mask = 0 if mask_id is None else mask_id.numel()
-    _call("mumpy_window_attention_mm16_fwd", _p(qkv), _p(out), _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
-          b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
-    return out
+    return _window_attention("mumpy_window_attention_mm16_fwd", _chk, torch.float32, "window_attention_mm16", qkv, bias_pad, b, hs, w, c,
+                             shift, scale, mask_tab, mask_id, out)
 
 
 def deform_offsets(q, dw_w, dw_b, ln_g, ln_b, pw_w, b, h, w, c):
