@@ -107,6 +107,16 @@ int mumpy_deform_sample_kv_fwd(const float* x2, const float* pos, const float* W
 int mumpy_deform_out_combine_fwd(const float* o, const float* Wout, const float* bout, const float* x1, float* out, int B, int H,
                                  int W, int C, void* stream);
 
+/* The two fused kernels with bf16 matrix math (opt-in; ops.set_cva_math("bf16")): same arguments, validation and error codes as
+ * their fp32 siblings above, all tensors fp32 in memory.  The operands -- the finished fp32 bilinear sample and Wkv; Wout and o --
+ * are rounded to bf16 (nearest even) while staged and multiplied on v_mfma_f32_32x32x16_bf16 with fp32 accumulation; the bilinear
+ * sum, the bias adds and the residual terms stay fp32.  The sampled values are bitwise those of mumpy_deform_sample_fwd, so
+ * kv == linear(r(sample), r(Wkv)) + bkv up to the fp32 summation order (r = round to bf16). */
+int mumpy_deform_sample_kv_mm16_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv, int B, int Hs2,
+                                    int W, int C, int nq, void* stream);
+int mumpy_deform_out_combine_mm16_fwd(const float* o, const float* Wout, const float* bout, const float* x1, float* out, int B,
+                                      int H, int W, int C, void* stream);
+
 /* ---- data-movement / wiring kernels of the decoder and the encoder tail (round 3: formerly ATen launches) ----
  * 2x2 average pooling, stride 2 (the nn.AvgPool2d(2) of decoder.py:149-178's frequency blocks): x (B,H,W,C) NHWC -- or, nchw_in
  * = 1, (B,C,H,W) contiguous as FAF emits it (dct:79) -- -> out (B,H/2,W/2,Cpad) NHWC with channels [C,Cpad) zero (the
@@ -256,6 +266,16 @@ int mumpy_deform_sample_fwd(const float* x2, const float* pos, float* out, int B
  * out: (B1w, 49, C) window-major.  padmask: (1,64,64) with 0 for j<49 and -1e30 for j>=49. */
 int mumpy_deform_attention_fwd(const float* q, const float* kv, const float* padmask, float* out, int B, int H,
                                int W, int C, int r, float scale, void* stream);
+
+/* The same with bf16 matrix math (opt-in; ops.set_cva_math("bf16")): q, kv and out stay fp32 in memory, q / k / v are rounded to
+ * bf16 (nearest even) in registers and both products run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation, as in
+ * mumpy_window_attention_mm16_fwd: the scale multiplies the fp32 scores, the softmax is fp32, exp(s - max) is rounded unnormalised
+ * and the reciprocal of its fp32 row sum scales the fp32 product; the r-tuple sum is accumulated in fp32 in the order t = 0..r-1
+ * (deterministic).  Same arguments, validation and error codes as mumpy_deform_attention_fwd; additionally H * W * C * 4 < 2^32
+ * (MUMPY_ERANGE).  Against an exact evaluation on the rounded operands: |out - exact| <= 2^-8 sum_t P_t |r(v_t)| plus fp32-level
+ * terms (tests/test_cva_bf16mm.py). */
+int mumpy_deform_attention_mm16_fwd(const float* q, const float* kv, const float* padmask, float* out, int B, int H,
+                                    int W, int C, int r, float scale, void* stream);
 
 /* combine (deform:403 un-permuted reshape + mTVE:138 + mTVE:285-286):
  *   out[b, n*49+p, c] = x1[b, n*49+p, c] + x1[b, raster(n,p), c] + Yt[b*nWf+n][(p*C+c) % 49][(p*C+c) / 49]

@@ -18,12 +18,36 @@
 // Both are 4-wave tiled kernels on v_mfma_f32_32x32x2_f32 (exact fp32 products, as every GEMM of the fp32 path), 32-deep
 // chunks, two LDS buffers with 36-dword rows, global -> register -> LDS staging one chunk ahead.  They are mid-size launches
 // (0.5-9 GFLOP); what they buy is two launches and two HBM round trips less on the cross-view dependency chain.
+//
+// MM16 = true (mumpy_deform_sample_kv_mm16_fwd / mumpy_deform_out_combine_mm16_fwd; opt-in, ops.set_cva_math("bf16")): the same
+// tiling, loaders, group logic and epilogues with the two operands rounded to bf16 (nearest even) on their way to LDS and
+// multiplied on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  Everything before the rounding (the bilinear sum, in the
+// operation order of deform_sample_lds_kernel) and after the product (bias, residual terms) is the fp32 code of the fp32 form.
+// Both LDS images stay [row][k]: a 32-deep chunk is 32 bf16 = 16 dwords per row, rows LDH = 20 dwords apart -- 5 16-byte slots,
+// odd, so the 16 rows a ds_read_b128 lane group touches (distinct mod 16) fall on 16 distinct slots of the 64-bank row:
+// conflict-free fragment reads (the image and the reads of xgemm16_kernel, gemm_bwd.hip).  Two MFMA steps per chunk instead of 16.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / AGPRs / SGPRs / LDS per block / waves per SIMD; scratch 0):
+//   deform_sample_kv_kernel<96 | 192 | 384 | 768, true>    132 | 134 | 130 | 130 / 0 / 44 | 44 | 47 | 47 / 40,960 B / 3
+//     (the fp32 form: 154 | 184 | 172 | 172 / 0 / 44 | 44 | 47 | 47 / 73,728 B / 2)
+//   deform_out_combine_kernel<96 | 192 | 384 | 768, true>  54 | 58 | 60 | 58 / 0 / 20 / 20,480 B / 8
+//     (the fp32 form: 54 / 0 / 20 / 36,864 B / 4)
 #include "common.h"
 using namespace mumpy;
 
 namespace {
 
 constexpr int BK = 32, LDR = 36;
+constexpr int LDH = 20;   // MM16: dwords per LDS row (32 bf16 + 4 dwords of padding)
+
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+
+// MM16 staging: 4 fp32 -> 4 bf16 (round to nearest even), one 8-byte LDS store at dword `dw` of the image
+__device__ __forceinline__ void put_bf16x4(float* img, int dw, f32x4 v) {
+    *reinterpret_cast<uint2*>(img + dw) = __builtin_bit_cast(uint2, __builtin_convertvector(v, bf16x4));
+}
+// MM16 fragment of MFMA step st: lane (c, h) supplies k = 16 st + 8 h .. + 7 of its row (row_h = row start + 4 h dwords)
+__device__ __forceinline__ bf16x8 frag_bf16(const float* row_h, int st) { return *reinterpret_cast<const bf16x8*>(row_h + 8 * st); }
 
 // m / 49 and m % 49 for m < 2^31 / 49 (mulhi by ceil(2^37 / 49))
 __device__ __forceinline__ void divmod49(unsigned m, unsigned& q, unsigned& r) {
@@ -32,14 +56,14 @@ __device__ __forceinline__ void divmod49(unsigned m, unsigned& q, unsigned& r) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-template <int C>
+template <int C, bool MM16>
 __global__ __launch_bounds__(256, 2) void deform_sample_kv_kernel(const float* __restrict__ x2, const float* __restrict__ pos,
                                                                   const float* __restrict__ Wkv, const float* __restrict__ bkv,
                                                                   float* __restrict__ kv, int Hs2, int W, int nWx, int nW2, int nq,
                                                                   int M, unsigned gn) {
     constexpr int BM = 64, BN = 192, TN = 3, N = 2 * C, K = C, CG = C / 3, NK = K / BK, CPG = CG / BK;   // CPG: chunks per group
     constexpr int A_LD = BM / 32, B_LD = BN / 32;
-    __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * LDR];
+    __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * (MM16 ? LDH : LDR)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
     // XCD-major renumbering; the N tiles of one row panel are neighbours (they sample the same windows)
@@ -107,10 +131,17 @@ __global__ __launch_bounds__(256, 2) void deform_sample_kv_kernel(const float* _
         for (int i = 0; i < B_LD; ++i) breg[i] = *reinterpret_cast<const f32x4*>(brow[i] + k0);
     };
     auto lstore = [&](int buf) {
+        if constexpr (MM16) {                           // only the finished sample (and the W piece) is rounded
 #pragma unroll
-        for (int i = 0; i < A_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(ld_row + 32 * i) * LDR + 4 * ld_c4]) = areg[i];
+            for (int i = 0; i < A_LD; ++i) put_bf16x4(lds[buf], (ld_row + 32 * i) * LDH + 2 * ld_c4, areg[i]);
 #pragma unroll
-        for (int i = 0; i < B_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(BM + ld_row + 32 * i) * LDR + 4 * ld_c4]) = breg[i];
+            for (int i = 0; i < B_LD; ++i) put_bf16x4(lds[buf], (BM + ld_row + 32 * i) * LDH + 2 * ld_c4, breg[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < A_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(ld_row + 32 * i) * LDR + 4 * ld_c4]) = areg[i];
+#pragma unroll
+            for (int i = 0; i < B_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(BM + ld_row + 32 * i) * LDR + 4 * ld_c4]) = breg[i];
+        }
     };
     f32x16 acc[TN];
 #pragma unroll
@@ -118,18 +149,32 @@ __global__ __launch_bounds__(256, 2) void deform_sample_kv_kernel(const float* _
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
     auto compute = [&](int buf) {
-        const float* a_f = &lds[buf][(wm * 32 + c) * LDR + 16 * h];
-        const float* b_f = &lds[buf][(BM + wn * 96 + c) * LDR + 16 * h];
+        if constexpr (MM16) {
+            const float* a_f = &lds[buf][(wm * 32 + c) * LDH + 4 * h];
+            const float* b_f = &lds[buf][(BM + wn * 96 + c) * LDH + 4 * h];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(a_f + 4 * q);
-            f32x4 fb[TN];
+            for (int st = 0; st < 2; ++st) {
+                const bf16x8 fa = frag_bf16(a_f, st);
+                bf16x8 fb[TN];
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f32x4*>(b_f + 32 * j * LDR + 4 * q);
+                for (int j = 0; j < TN; ++j) fb[j] = frag_bf16(b_f + 32 * j * LDH, st);
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
+                for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb[j], acc[j], 0, 0, 0);
+            }
+        } else {
+            const float* a_f = &lds[buf][(wm * 32 + c) * LDR + 16 * h];
+            const float* b_f = &lds[buf][(BM + wn * 96 + c) * LDR + 16 * h];
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[j][e], acc[j], 0, 0, 0);
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 fa = *reinterpret_cast<const f32x4*>(a_f + 4 * q);
+                f32x4 fb[TN];
+#pragma unroll
+                for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const f32x4*>(b_f + 32 * j * LDR + 4 * q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[j][e], acc[j], 0, 0, 0);
+            }
         }
     };
     set_group(0);
@@ -161,14 +206,14 @@ __global__ __launch_bounds__(256, 2) void deform_sample_kv_kernel(const float* _
 
 // ------------------------------------------------------------------------------------------------------------------
 // out[win_base + f] = x1[win_base + f] + x1[(img + tok(f / C)) C + f % C] + Yt[p'][c'],  f = c' 49 + p'
-template <int C>
+template <int C, bool MM16>
 __global__ __launch_bounds__(256, 2) void deform_out_combine_kernel(const float* __restrict__ o, const float* __restrict__ Wout,
                                                                    const float* __restrict__ bout, const float* __restrict__ x1,
                                                                    float* __restrict__ out, int H, int W, int nWx, int nWf, int MO,
                                                                    unsigned gn) {
     constexpr int BM = 64, BN = 64, K = C, NK = K / BK;          // BM: output channels c' (rows of W_out); BN: rows of o
     constexpr int A_LD = BM / 32, B_LD = BN / 32;
-    __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * LDR];
+    __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * (MM16 ? LDH : LDR)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int c = lane & 31, h = lane >> 5, wm = wave >> 1, wn = wave & 1;
     const unsigned wgid = xcd_major_id(blockIdx.x, gridDim.x);
@@ -197,22 +242,37 @@ __global__ __launch_bounds__(256, 2) void deform_out_combine_kernel(const float*
         for (int i = 0; i < B_LD; ++i) breg[i] = *reinterpret_cast<const f32x4*>(brow[i] + kc * BK);
     };
     auto lstore = [&](int buf) {
+        if constexpr (MM16) {                           // W_out and o are rounded while staged
 #pragma unroll
-        for (int i = 0; i < A_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(ld_row + 32 * i) * LDR + 4 * ld_c4]) = areg[i];
+            for (int i = 0; i < A_LD; ++i) put_bf16x4(lds[buf], (ld_row + 32 * i) * LDH + 2 * ld_c4, areg[i]);
 #pragma unroll
-        for (int i = 0; i < B_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(BM + ld_row + 32 * i) * LDR + 4 * ld_c4]) = breg[i];
+            for (int i = 0; i < B_LD; ++i) put_bf16x4(lds[buf], (BM + ld_row + 32 * i) * LDH + 2 * ld_c4, breg[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < A_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(ld_row + 32 * i) * LDR + 4 * ld_c4]) = areg[i];
+#pragma unroll
+            for (int i = 0; i < B_LD; ++i) *reinterpret_cast<f32x4*>(&lds[buf][(BM + ld_row + 32 * i) * LDR + 4 * ld_c4]) = breg[i];
+        }
     };
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
     auto compute = [&](int buf) {
-        const float* a_f = &lds[buf][(wm * 32 + c) * LDR + 16 * h];
-        const float* b_f = &lds[buf][(BM + wn * 32 + c) * LDR + 16 * h];
+        if constexpr (MM16) {
+            const float* a_f = &lds[buf][(wm * 32 + c) * LDH + 4 * h];
+            const float* b_f = &lds[buf][(BM + wn * 32 + c) * LDH + 4 * h];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const f32x4 fa = *reinterpret_cast<const f32x4*>(a_f + 4 * q), fb = *reinterpret_cast<const f32x4*>(b_f + 4 * q);
+            for (int st = 0; st < 2; ++st)
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_bf16(a_f, st), frag_bf16(b_f, st), acc, 0, 0, 0);
+        } else {
+            const float* a_f = &lds[buf][(wm * 32 + c) * LDR + 16 * h];
+            const float* b_f = &lds[buf][(BM + wn * 32 + c) * LDR + 16 * h];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], acc, 0, 0, 0);
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 fa = *reinterpret_cast<const f32x4*>(a_f + 4 * q), fb = *reinterpret_cast<const f32x4*>(b_f + 4 * q);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], acc, 0, 0, 0);
+            }
         }
     };
     gload(0);
@@ -246,23 +306,25 @@ __global__ __launch_bounds__(256, 2) void deform_out_combine_kernel(const float*
 
 }  // namespace
 
-extern "C" int mumpy_deform_sample_kv_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv, int B,
-                                          int Hs2, int W, int C, int nq, void* stream) {
-    MUMPY_REQUIRE(x2 && pos && Wkv && bkv && kv, MUMPY_ENULL, "deform_sample_kv: null pointer");
-    MUMPY_REQUIRE(aligned16(x2) && aligned16(Wkv) && aligned16(kv), MUMPY_EALIGN, "deform_sample_kv: pointers must be 16-byte aligned");
+// one validation + launch body per kernel; `who` names the entry in mumpy_last_error
+template <bool MM16>
+static int sample_kv_launch(const char* who, const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv, int B,
+                            int Hs2, int W, int C, int nq, void* stream) {
+    MUMPY_REQUIRE(x2 && pos && Wkv && bkv && kv, MUMPY_ENULL, "%s: null pointer", who);
+    MUMPY_REQUIRE(aligned16(x2) && aligned16(Wkv) && aligned16(kv), MUMPY_EALIGN, "%s: pointers must be 16-byte aligned", who);
     MUMPY_REQUIRE(B > 0 && Hs2 > 0 && W > 0 && Hs2 % WS == 0 && W % WS == 0 && nq > 0, MUMPY_EINVAL,
-                  "deform_sample_kv: bad grid (%d,%d) / nq=%d", Hs2, W, nq);
+                  "%s: bad grid (%d,%d) / nq=%d", who, Hs2, W, nq);
     MUMPY_REQUIRE(C == 96 || C == 192 || C == 384 || C == 768, MUMPY_EINVAL,
-                  "deform_sample_kv: C=%d is not one of the encoder widths 96/192/384/768", C);
+                  "%s: C=%d is not one of the encoder widths 96/192/384/768", who, C);
     const int nWx = W / WS, nW2 = (Hs2 / WS) * nWx;
     const int64_t nwin = (int64_t)B * nW2, M = nwin * WT;
-    MUMPY_REQUIRE(M < (1ll << 31) - 64, MUMPY_ERANGE, "deform_sample_kv: too many windows");
+    MUMPY_REQUIRE(M < (1ll << 31) - 64, MUMPY_ERANGE, "%s: too many windows", who);
     const unsigned gn = (unsigned)((2 * C + 191) / 192);
     const int64_t grid = ((M + 63) / 64) * gn;
-    MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "deform_sample_kv: too many tiles");
-#define MUMPY_SKV(C_)                                                                                                     \
-    hipLaunchKernelGGL(deform_sample_kv_kernel<C_>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), x2, pos, Wkv, bkv, \
-                       kv, Hs2, W, nWx, nW2, nq, (int)M, gn)
+    MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "%s: too many tiles", who);
+#define MUMPY_SKV(C_)                                                                                                        \
+    hipLaunchKernelGGL((deform_sample_kv_kernel<C_, MM16>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), x2, pos, Wkv, \
+                       bkv, kv, Hs2, W, nWx, nW2, nq, (int)M, gn)
     switch (C) {
         case 96: MUMPY_SKV(96); break;
         case 192: MUMPY_SKV(192); break;
@@ -270,26 +332,27 @@ extern "C" int mumpy_deform_sample_kv_fwd(const float* x2, const float* pos, con
         default: MUMPY_SKV(768); break;
     }
 #undef MUMPY_SKV
-    MUMPY_CHECK_LAUNCH("deform_sample_kv");
+    MUMPY_CHECK_LAUNCH(who);
     return 0;
 }
 
-extern "C" int mumpy_deform_out_combine_fwd(const float* o, const float* Wout, const float* bout, const float* x1, float* out, int B,
-                                            int H, int W, int C, void* stream) {
-    MUMPY_REQUIRE(o && Wout && bout && x1 && out, MUMPY_ENULL, "deform_out_combine: null pointer");
-    MUMPY_REQUIRE(x1 != out, MUMPY_EINVAL, "deform_out_combine: out must not alias x1");
-    MUMPY_REQUIRE(aligned16(o) && aligned16(Wout), MUMPY_EALIGN, "deform_out_combine: pointers must be 16-byte aligned");
-    MUMPY_REQUIRE(B > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0, MUMPY_EINVAL, "deform_out_combine: bad grid (%d,%d)", H, W);
+template <bool MM16>
+static int out_combine_launch(const char* who, const float* o, const float* Wout, const float* bout, const float* x1, float* out,
+                              int B, int H, int W, int C, void* stream) {
+    MUMPY_REQUIRE(o && Wout && bout && x1 && out, MUMPY_ENULL, "%s: null pointer", who);
+    MUMPY_REQUIRE(x1 != out, MUMPY_EINVAL, "%s: out must not alias x1", who);
+    MUMPY_REQUIRE(aligned16(o) && aligned16(Wout), MUMPY_EALIGN, "%s: pointers must be 16-byte aligned", who);
+    MUMPY_REQUIRE(B > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0, MUMPY_EINVAL, "%s: bad grid (%d,%d)", who, H, W);
     MUMPY_REQUIRE(C == 96 || C == 192 || C == 384 || C == 768, MUMPY_EINVAL,
-                  "deform_out_combine: C=%d is not one of the encoder widths 96/192/384/768", C);
+                  "%s: C=%d is not one of the encoder widths 96/192/384/768", who, C);
     const int nWx = W / WS, nWf = (H / WS) * nWx;
     const int64_t MO = (int64_t)B * nWf * WT;
-    MUMPY_REQUIRE(MO * 49 < (1ll << 31) && MO < (1ll << 31) - 64, MUMPY_ERANGE, "deform_out_combine: too many windows");
+    MUMPY_REQUIRE(MO * 49 < (1ll << 31) && MO < (1ll << 31) - 64, MUMPY_ERANGE, "%s: too many windows", who);
     const unsigned gn = (unsigned)((C + 63) / 64);
     const int64_t grid = ((MO + 63) / 64) * gn;
-#define MUMPY_OC(C_)                                                                                                      \
-    hipLaunchKernelGGL(deform_out_combine_kernel<C_>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), o, Wout, bout, x1, \
-                       out, H, W, nWx, nWf, (int)MO, gn)
+#define MUMPY_OC(C_)                                                                                                         \
+    hipLaunchKernelGGL((deform_out_combine_kernel<C_, MM16>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), o, Wout, bout, \
+                       x1, out, H, W, nWx, nWf, (int)MO, gn)
     switch (C) {
         case 96: MUMPY_OC(96); break;
         case 192: MUMPY_OC(192); break;
@@ -297,6 +360,26 @@ extern "C" int mumpy_deform_out_combine_fwd(const float* o, const float* Wout, c
         default: MUMPY_OC(768); break;
     }
 #undef MUMPY_OC
-    MUMPY_CHECK_LAUNCH("deform_out_combine");
+    MUMPY_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int mumpy_deform_sample_kv_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv, int B,
+                                          int Hs2, int W, int C, int nq, void* stream) {
+    return sample_kv_launch<false>("deform_sample_kv", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, stream);
+}
+
+extern "C" int mumpy_deform_sample_kv_mm16_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv,
+                                               int B, int Hs2, int W, int C, int nq, void* stream) {
+    return sample_kv_launch<true>("deform_sample_kv_mm16", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, stream);
+}
+
+extern "C" int mumpy_deform_out_combine_fwd(const float* o, const float* Wout, const float* bout, const float* x1, float* out, int B,
+                                            int H, int W, int C, void* stream) {
+    return out_combine_launch<false>("deform_out_combine", o, Wout, bout, x1, out, B, H, W, C, stream);
+}
+
+extern "C" int mumpy_deform_out_combine_mm16_fwd(const float* o, const float* Wout, const float* bout, const float* x1, float* out,
+                                                 int B, int H, int W, int C, void* stream) {
+    return out_combine_launch<true>("deform_out_combine_mm16", o, Wout, bout, x1, out, B, H, W, C, stream);
 }

@@ -3,9 +3,16 @@
 // (win_attn_unit.h), fp32 MFMA, but not persistent: no bias table (only the 49 -> 64 key padding), the scale on the product, q
 // gathered from the raster, k/v window-major.
 //
+// win_attn_cross_mm16_kernel (mumpy_deform_attention_mm16_fwd; opt-in, ops.set_cva_math("bf16")) is the forward on
+// v_mfma_f32_32x32x16_bf16, built like win_attn_self_bf16mm_kernel<IO32 = true>: q / k rows rounded to bf16 in registers, S^T = K Q^T
+// so that the exponentials feed P V from the accumulator registers, V gathered in that permuted key order, the scale on the fp32 scores,
+// P rounded unnormalised with the fp32 row sum's reciprocal applied to the fp32 product -- here once per kv window t, as the r-tuple
+// sum o += (P_t V_t) / sum_t is accumulated in registers in the order t = 0 .. r-1.
+//
 // Replaces: the attention + "(b t)->b t" sum of SwinDAttention (deform:360-395).
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs + AGPRs / SGPRs / LDS per block / waves per SIMD; no scratch):
-//   win_attn_cross_kernel 229 + 0 / 47 / 1,024 B / 2;   deform_attn_bwd_q_kernel 180 + 80 / 40 / 0 / 1;   deform_attn_bwd_kv_kernel 256 + 62 / 44 / 0 / 1
+//   win_attn_cross_kernel 229 + 0 / 47 / 1,024 B / 2;   win_attn_cross_mm16_kernel 160 + 0 / 46 / 3,072 B / 3;
+//   deform_attn_bwd_q_kernel 180 + 80 / 40 / 0 / 1;   deform_attn_bwd_kv_kernel 256 + 62 / 44 / 0 / 1
 #include <stdlib.h>
 #include "win_attn_unit.h"
 
@@ -66,6 +73,80 @@ __global__ __launch_bounds__(256, 2) void win_attn_cross_kernel(CrossArgs a) {
             bias_softmax<false>(s, [&](int jt, int g) { return pad_bias(jt, g, h); }, nullptr, 32 * it + c, h,
                                 a.scale);                                       // scale on the product (deform:364)
             pv_product(o[it], s, vf);
+        }
+    }
+    float* obase = a.out + b1 * WT * a.C + head * HD;
+    store_o(o[0], 0, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
+    store_o(o[1], 1, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The same unit on the bf16 MFMA: 8 + 8 MFMAs per kv window instead of 64 + 50.  Token tables hold byte offsets: tq the q rows of the
+// raster (rewritten per kv window, its q window changes with t), tk the kv rows of a window (slot * 8C, the same for every t); padded
+// slots 49..63 are clamped to slot 48 -- finite duplicates whose scores get -1e30 (keys) or are never stored (queries).  1 / row sum
+// lives on the query's lane and the product has the query in its registers: it crosses through 64 floats of LDS per wave.
+__global__ __launch_bounds__(256, 2) void win_attn_cross_mm16_kernel(CrossArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tok_q[4][64];
+    __shared__ __attribute__((aligned(16))) uint32_t tok_k[4][64];
+    __shared__ __attribute__((aligned(16))) float inv_s[4][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t u = (int64_t)blockIdx.x * 4 + wave;
+    if (u >= a.units) return;
+    const int head = (int)(u % a.nH);
+    const int64_t b1 = u / a.nH;                 // output window
+    uint32_t* tq = tok_q[wave];
+    uint32_t* tk = tok_k[wave];
+    float* invw = inv_s[wave];
+    const int64_t L = (int64_t)a.H * a.W;
+    const int slot = lane < WT ? lane : WT - 1;
+    tk[lane] = (uint32_t)slot * 8u * a.C;
+    f32x16 o[2] = {};
+
+    for (int t = 0; t < a.r; ++t) {
+        const int64_t b2 = b1 * a.r + t;                  // kv window; adjacent r-tuples are summed (deform:394-395)
+        const int qw = (int)(b2 % a.B1w);                 // q window = kv window mod B1 (x1.repeat, deform:330)
+        const int qb = qw / a.nWf, qn = qw - qb * a.nWf;
+        const int wy = qn / a.nWx, wx = qn - wy * a.nWx;
+        __builtin_amdgcn_wave_barrier();
+        tq[lane] = (uint32_t)window_token(wy, wx, slot, a.H, a.W, 0) * 4u * a.C;
+        __builtin_amdgcn_wave_barrier();
+        const char* qbase = reinterpret_cast<const char*>(a.q + ((int64_t)qb * L) * a.C + head * HD);
+        const char* kbase = reinterpret_cast<const char*>(a.kv + b2 * WT * 2 * a.C + head * HD);
+        bf16x8 qf[2][2], kf[2][2], vf[2][2];
+#pragma unroll
+        for (int tl = 0; tl < 2; ++tl) {
+            load_frag_bf16(qf[tl], qbase, tq[32 * tl + c] + 32u * h);
+            load_frag_bf16(kf[tl], kbase, tk[32 * tl + c] + 32u * h);
+        }
+        load_perm_bf16(vf, kbase + 4 * a.C, tk, c, h);
+        if (h) vf[1][1][0] = (__bf16)0.f;                 // key 52 (slot 48's value through the clamp): V is 0 on every padded key
+
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            f32x16 s[2] = {};
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+#pragma unroll
+                for (int jt = 0; jt < 2; ++jt) s[jt] = mfma16(kf[jt][st], qf[it][st], s[jt]);       // S^T[jt] += K[jt] Q[it]^T
+            const int qi = 32 * it + c;
+            float m, inv;
+            bias_softmax<false, false>(s, [&](int jt, int g) { return pad_bias(jt, g, h); }, nullptr, qi, h, a.scale, &m,
+                                       &inv);                                   // scale on the product (deform:364)
+            invw[qi] = inv;                                                     // both lane halves hold the same value
+            f32x16 pv = {};
+#pragma unroll
+            for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+                for (int st = 0; st < 2; ++st) pv = mfma16(acc_frag(s[jt], st), vf[jt][st], pv);
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (acc_pad(it, g)) continue;
+                const f32x4 iv = *reinterpret_cast<const f32x4*>(&invw[32 * it + 8 * g + 4 * h]);   // queries 32it + 8g + 4h .. +3
+#pragma unroll
+                for (int e = 0; e < 4; ++e) o[it][4 * g + e] += pv[4 * g + e] * iv[e];
+            }
         }
     }
     float* obase = a.out + b1 * WT * a.C + head * HD;
@@ -231,24 +312,41 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs
 
 }  // namespace
 
-extern "C" int mumpy_deform_attention_fwd(const float* q, const float* kv, const float* padmask, float* out, int B,
-                                          int H, int W, int C, int r, float scale, void* stream) {
-    MUMPY_REQUIRE(q && kv && padmask && out, MUMPY_ENULL, "deform_attention: null pointer");
+// one validation + launch body for both forward kernels; `who` names the entry in mumpy_last_error
+template <bool MM16>
+static int cross_launch(const char* who, const float* q, const float* kv, const float* padmask, float* out, int B, int H, int W, int C,
+                        int r, float scale, void* stream) {
+    MUMPY_REQUIRE(q && kv && padmask && out, MUMPY_ENULL, "%s: null pointer", who);
     MUMPY_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(padmask) && aligned16(out), MUMPY_EALIGN,
-                  "deform_attention: pointers must be 16-byte aligned");
+                  "%s: pointers must be 16-byte aligned", who);
     MUMPY_REQUIRE(B > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && r >= 1, MUMPY_EINVAL,
-                  "deform_attention: bad grid (%d,%d) or ratio %d", H, W, r);
-    MUMPY_REQUIRE(C > 0 && C % HD == 0, MUMPY_EINVAL, "deform_attention: C=%d not a multiple of 32", C);
+                  "%s: bad grid (%d,%d) or ratio %d", who, H, W, r);
+    MUMPY_REQUIRE(C > 0 && C % HD == 0, MUMPY_EINVAL, "%s: C=%d not a multiple of 32", who, C);
     CrossArgs a;
     a.q = q; a.kv = kv; a.padmask = padmask; a.out = out;
     a.B = B; a.H = H; a.W = W; a.C = C; a.nH = C / HD; a.r = r;
     a.nWx = W / WS; a.nWf = (H / WS) * (W / WS); a.B1w = B * a.nWf; a.scale = scale;
     a.units = (int64_t)a.B1w * a.nH;
     const int64_t grid = (a.units + 3) / 4;
-    MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "deform_attention: too many windows");
-    hipLaunchKernelGGL(win_attn_cross_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
-    MUMPY_CHECK_LAUNCH("deform_attention");
+    MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "%s: too many windows", who);
+    if (MM16) {
+        MUMPY_REQUIRE((int64_t)H * W * C * 4 < (1ll << 32), MUMPY_ERANGE, "%s: image too large for 32-bit row offsets", who);
+        hipLaunchKernelGGL(win_attn_cross_mm16_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+    } else {
+        hipLaunchKernelGGL(win_attn_cross_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+    }
+    MUMPY_CHECK_LAUNCH(who);
     return 0;
+}
+
+extern "C" int mumpy_deform_attention_fwd(const float* q, const float* kv, const float* padmask, float* out, int B,
+                                          int H, int W, int C, int r, float scale, void* stream) {
+    return cross_launch<false>("deform_attention", q, kv, padmask, out, B, H, W, C, r, scale, stream);
+}
+
+extern "C" int mumpy_deform_attention_mm16_fwd(const float* q, const float* kv, const float* padmask, float* out, int B,
+                                               int H, int W, int C, int r, float scale, void* stream) {
+    return cross_launch<true>("deform_attention_mm16", q, kv, padmask, out, B, H, W, C, r, scale, stream);
 }
 
 extern "C" int64_t mumpy_deform_attention_bwd_workspace_bytes(int64_t B2w, int C) {

@@ -1,9 +1,19 @@
 """Window-based deformable cross-view attention (SwinDAttention) on the MI355X HIP kernels.
 
-State_dict keys and constructor follow the reference's models/modules/deformableAttention.py:218-309.  Execution is
-six launches on raster-ordered tokens:  proj_q GEMM -> offsets kernel (depthwise 5x5 + LN + GELU + 1x1 + tanh) ->
-bilinear sampling kernel -> [proj_k|proj_v] as ONE GEMM with concatenated weights -> fused attention + r-tuple
-aggregation kernel -> proj_out GEMM.  The reference's index behaviour is specification and is reproduced exactly:
+State_dict keys and constructor follow the reference's models/modules/deformableAttention.py:218-309.  Every route starts
+with the proj_q GEMM and the offsets kernel (depthwise 5x5 + LN + GELU + 1x1 + tanh) on raster-ordered tokens and then takes
+one of three forms, chosen at launch time:
+  * fused fp32 (default; fp32 matrix math and storage): sample -> [proj_k|proj_v] as ONE kernel whose A-operand loader is the
+    bilinear sampling (mumpy_deform_sample_kv_fwd) -> attention + r-tuple aggregation kernel -> proj_out, which in the cross
+    block is ONE kernel with the scrambled reshape and both residual terms (mumpy_deform_out_combine_fwd): 5 launches;
+  * unfused (set_matrix_math / set_storage other than fp32, or MUMPY_CVA_FUSED=0): bilinear sampling kernel -> [proj_k|proj_v]
+    as one generic GEMM with concatenated weights -> the same fp32 attention kernel -> proj_out generic GEMM -> combine kernel:
+    7 launches, the GEMMs in the generic GEMM's operand mode;
+  * fused bf16-MFMA (ops.set_cva_math("bf16"), opt-in): the fused route with the _mm16 form of all three kernels -- fp32
+    tensors in memory, operands rounded to bf16 on the way to v_mfma_f32_32x32x16_bf16, fp32 accumulation, softmax, bias and
+    residual terms.  The switch takes PRECEDENCE: when it is "bf16" these kernels run whatever matrix_math(), storage() and
+    MUMPY_CVA_FUSED say; proj_q and the offsets kernel keep following matrix_math().
+The reference's index behaviour is specification and is reproduced exactly:
 kv window i pairs with q window (i mod B1) (`x1.repeat`, deform:330), the "(b t)" sum adds ADJACENT kv windows
 (deform:394-395), and the output is the flat (C,49) image re-read as (49,C) (deform:403).  The (B, r*nH, 49, 49)
 attention tensor the reference also returns is discarded by its only caller (mTVE:284) and is not materialised.
@@ -101,13 +111,14 @@ class SwinDAttention(nn.Module):
         wkv = self._wkv.get((self.proj_k.weight, self.proj_v.weight),
                             lambda: torch.cat([self.proj_k.weight.reshape(c, c), self.proj_v.weight.reshape(c, c)], 0))
         bkv = self._bkv.get((self.proj_k.bias, self.proj_v.bias), lambda: torch.cat([self.proj_k.bias, self.proj_v.bias]))
-        if FUSED["sample_kv"] and ops.matrix_math() == "fp32" and ops.storage() == "fp32":
-            kv = ops.deform_sample_kv(x2, pos, wkv, bkv, b2, hs2, w2, c, nq)      # sampling = the projection's A loader
+        math = ops.cva_math()                                                     # "bf16": the _mm16 kernels, before any other mode
+        if math == "bf16" or (FUSED["sample_kv"] and ops.matrix_math() == "fp32" and ops.storage() == "fp32"):
+            kv = ops.deform_sample_kv(x2, pos, wkv, bkv, b2, hs2, w2, c, nq, math=math)   # sampling = the projection's A loader
         else:
             sampled = ops.deform_sample(x2, pos, b2, hs2, w2, c, nq)
             kv = ops.linear(sampled, wkv, bkv)                                    # (nkv,49,2C)
         pad = self._pad.get((self.proj_q.weight,), lambda: ops.pad_mask().to(x1.device))
-        o = ops.deform_attention(q, kv, pad, b, h, w, c, nkv // nq, self.scale)      # (nq,49,C)
+        o = ops.deform_attention(q, kv, pad, b, h, w, c, nkv // nq, self.scale, math=math)      # (nq,49,C)
         if not want_maps:
             return o
         # kv window i pairs with q window i mod nq; q is raster (b, h*w, C): gather its windows first (49 x C each)
@@ -118,10 +129,13 @@ class SwinDAttention(nn.Module):
     def attend_combine(self, x1, x2, b, h, w, hs2, prep=None):
         """The cross block's use of the module (mTVE:283-286): x1 + x1[window order] + the scrambled attention output, i.e.
         CVAModule's `x1w + D` laid out window-major and added to raster x1.  Fused form: proj_out, the un-permuted (C,49)->(49,C)
-        reshape and both residual terms are ONE launch (mumpy_deform_out_combine_fwd)."""
-        if FUSED["out_combine"] and ops.matrix_math() == "fp32" and ops.storage() == "fp32":
+        reshape and both residual terms are ONE launch (mumpy_deform_out_combine_fwd; under set_cva_math("bf16") its _mm16 form,
+        whatever the other modes say)."""
+        math = ops.cva_math()
+        if math == "bf16" or (FUSED["out_combine"] and ops.matrix_math() == "fp32" and ops.storage() == "fp32"):
             o = self._attend(x1, x2, (b, h, w), (b, hs2, w), prep)
-            return ops.deform_out_combine(o, self.proj_out.weight.reshape(self.nc, self.nc), self.proj_out.bias, x1, b, h, w, self.nc)
+            return ops.deform_out_combine(o, self.proj_out.weight.reshape(self.nc, self.nc), self.proj_out.bias, x1, b, h, w, self.nc,
+                                          math=math)
         yt = self._run(x1, x2, (b, h, w), (b, hs2, w), prep)
         return ops.deform_combine(x1, yt, b, h, w, self.nc)
 

@@ -173,6 +173,43 @@ def attention_math() -> str:
     return _ATTN_MATH
 
 
+def _cva_math_from_env() -> str:
+    mode = os.environ.get("MUMPY_CVA_MATH", "") or "fp32"
+    if mode not in ("fp32", "bf16"):
+        raise ValueError(f"MUMPY_CVA_MATH: unknown cross-view attention math mode {mode!r}")
+    return mode
+
+
+_CVA_MATH = _cva_math_from_env()         # read once, at import
+
+
+def set_cva_math(mode: str) -> None:
+    """Arithmetic of the cross-view attention module (SwinDAttention) in its inference forward.  "fp32" (default): the module's
+    existing routes.  "bf16": sample -> [k|v], the attention core and (in the cross block) proj_out -> combine run their bf16-MFMA
+    kernels (deform_sample_kv / deform_attention / deform_out_combine with math="bf16"): all tensors stay fp32 in memory, the matrix
+    operands are rounded to bf16 (nearest even) in registers or while staged, multiplied on v_mfma_f32_32x32x16_bf16 and accumulated
+    in fp32; the bilinear sum, softmax, bias adds and residual terms stay fp32.  Independent of set_matrix_math, set_storage and
+    set_attention_math: none of them touches it and it touches none of them.  The three ops never follow the switch by themselves
+    (their math= defaults to "fp32"), so the training tape, whose backward is fp32, keeps the fp32 forward.  The initial value is the
+    environment variable MUMPY_CVA_MATH, read when this module is imported.  Read at launch time: set it BEFORE a GraphedForward is
+    captured -- a captured graph keeps the kernels it was captured with."""
+    global _CVA_MATH
+    if mode not in ("fp32", "bf16"):
+        raise ValueError(f"unknown cross-view attention math mode {mode!r}")
+    _CVA_MATH = mode
+
+
+def cva_math() -> str:
+    return _CVA_MATH
+
+
+def _mm16(entry, math):
+    """C-ABI entry of a cross-view attention op for math= "fp32" (the entry itself) or "bf16" (its _mm16 form)."""
+    if math not in ("fp32", "bf16"):
+        raise ValueError(f"unknown cross-view attention math mode {math!r}")
+    return entry.replace("_fwd", "_mm16_fwd") if math == "bf16" else entry
+
+
 def _window_attention(entry, chk, dtype, who, qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id, out=None):
     """One body for the window-attention forward entries: C-ABI entry name, input check (_chk / _chk16) and output dtype."""
     qkv = chk(qkv, "qkv")
@@ -659,32 +696,40 @@ def deform_sample(x2, pos, b, hs2, w, c, nq):
     return out
 
 
-def deform_sample_kv(x2, pos, wkv, bkv, b, hs2, w, c, nq):
-    """[proj_k | proj_v] of the bilinearly sampled kv windows in one launch (the sampled map is never materialised)."""
+def deform_sample_kv(x2, pos, wkv, bkv, b, hs2, w, c, nq, math="fp32"):
+    """[proj_k | proj_v] of the bilinearly sampled kv windows in one launch (the sampled map is never materialised).
+    math="bf16": the fp32 sample and wkv are rounded to bf16 while staged and multiplied on the bf16 MFMA (see set_cva_math)."""
+    entry = _mm16("mumpy_deform_sample_kv_fwd", math)
     x2 = _chk(x2, "x2")
     nw2 = b * (hs2 // 7) * (w // 7)
     kv = torch.empty(nw2, 49, 2 * c, device=x2.device, dtype=torch.float32)
-    _call("mumpy_deform_sample_kv_fwd", _p(x2), _p(_chk(pos, "pos")), _p(_chk(wkv, "wkv")), _p(_chk(bkv, "bkv")), _p(kv), b, hs2, w, c, nq,
+    _call(entry, _p(x2), _p(_chk(pos, "pos")), _p(_chk(wkv, "wkv")), _p(_chk(bkv, "bkv")), _p(kv), b, hs2, w, c, nq,
           _stream(), work=2.0 * nw2 * 49 * 2 * c * c)
     return kv
 
 
-def deform_out_combine(o, wout, bout, x1, b, h, w, c):
-    """x1 + x1[window order] + scrambled proj_out(o) in one launch (replaces linear + deform_combine)."""
+def deform_out_combine(o, wout, bout, x1, b, h, w, c, math="fp32"):
+    """x1 + x1[window order] + scrambled proj_out(o) in one launch (replaces linear + deform_combine).
+    math="bf16": wout and o are rounded to bf16 while staged and multiplied on the bf16 MFMA; the epilogue stays fp32."""
+    entry = _mm16("mumpy_deform_out_combine_fwd", math)
     o, x1 = _chk(o, "o"), _chk(x1, "x1")
     out = torch.empty_like(x1)
-    _call("mumpy_deform_out_combine_fwd", _p(o), _p(_chk(wout, "wout")), _p(_chk(bout, "bout")), _p(x1), _p(out), b, h, w, c, _stream(),
+    _call(entry, _p(o), _p(_chk(wout, "wout")), _p(_chk(bout, "bout")), _p(x1), _p(out), b, h, w, c, _stream(),
           work=2.0 * o.numel() * c)
     return out
 
 
-def deform_attention(q, kv, padmask, b, h, w, c, r, scale):
+def deform_attention(q, kv, padmask, b, h, w, c, r, scale, math="fp32"):
+    """Cross-view attention core + r-tuple sum.  math is explicit and defaults to "fp32" whatever set_cva_math says: the training tape
+    (DeformAttentionFn) calls this and has an fp32 backward.  math="bf16": q / k / v rounded to bf16 in registers, both products on the
+    bf16 MFMA, fp32 softmax and accumulation."""
+    entry = _mm16("mumpy_deform_attention_fwd", math)
     q, kv = _chk(q, "q"), _chk(kv, "kv")
     b1w = b * (h // 7) * (w // 7)
     if kv.numel() != b1w * r * 49 * 2 * c:
         raise RuntimeError("deform_attention: kv shape mismatch")
     out = torch.empty(b1w, 49, c, device=q.device, dtype=torch.float32)
-    _call("mumpy_deform_attention_fwd", _p(q), _p(kv), _p(_chk(padmask, "padmask")), _p(out), b, h, w, c, r, scale,
+    _call(entry, _p(q), _p(kv), _p(_chk(padmask, "padmask")), _p(out), b, h, w, c, r, scale,
           _stream(), work=307328.0 * b1w * r * (c // 32))
     return out
 
