@@ -319,7 +319,7 @@ int mumpy_attention_probs_fwd(const float* q, const float* k, float* out, int64_
                               int64_t q_mod, float scale, void* stream);
 
 /* ---- Decoder glue in NHWC (decoder.py:67-225): everything between two convolutions ---------------------------
- * gn_stats: x (B,HW,C) NHWC -> partial (B, nsplit, G, 2) = per-slice {sum, sum of squares} of each GroupNorm group
+ * gn_stats: x (B,HW,C) NHWC -> partial (B, nsplit, G, 2) = per-slice {sum, M2 about the slice's own mean} of each GroupNorm group
  * (nn.GroupNorm statistics, decoder.py:70,77,84,91,101-119,151-180), combined in fixed order by gn_apply. */
 int mumpy_gn_stats_nhwc_fwd(const float* x, float* partial, int B, int64_t HW, int C, int G, int nsplit,
                             void* stream);
@@ -527,7 +527,7 @@ int mumpy_window_attention_mm16_bwd(const float* qkv, const float* dout, const f
 int mumpy_relpos_bias_expand_fwd(const float* table, const int32_t* rel_index, float* out, int nH, void* stream);
 
 /* GroupNorm (+ReLU) backward, NHWC (BaselineDecoder blocks, decoder.py:233-271): z, dy, dz (B,HW,C); stats_partial /
- * nsplit_stats = the partial sums mumpy_gn_stats_nhwc_fwd produced for z; `relu` is the activation that followed the
+ * nsplit_stats = the {sum, M2} partials mumpy_gn_stats_nhwc_fwd produced for z; `relu` is the activation that followed the
  * norm: 0 none, 1 ReLU (dy masked where GN(z) <= 0), 2 sigmoid (dy scaled by s(1-s)).
  * dgamma, dbeta (C): written, or -- `relu | MUMPY_GN_ACCUMULATE` -- added to what the buffers hold (the caller's flat gradient
  * buffer: no separate add launches).  Same C / G limits as mumpy_gn_stats_nhwc_fwd.  Deterministic. */

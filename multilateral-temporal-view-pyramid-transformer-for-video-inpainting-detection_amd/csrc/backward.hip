@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256) void conv_weight_dgrad_kernel(const float* __r
 //   dgamma_c = sum g xhat,  dbeta_c = sum g,  dz = rstd_g (g gamma_c - S1_g / n - xhat S2_g / n)
 //   S1_g = sum_{c in g} gamma_c T1[c],  S2_g = sum_{c in g} gamma_c T2[c],  T1[c] = sum_pixels g,  T2[c] = sum_pixels g xhat
 // pass 1 (grid (nsplit, B)): per-channel T1, T2 of its pixel range -> part[b][split][{T1,T2}][C]; pass 2: dz.
-// mean / rstd come from the forward's gn_stats partial sums (same layout, same fixed-order sum as the forward apply).
+// mean / rstd come from the forward's gn_stats partials {sum, M2} (same layout, same fixed-order combine as the forward apply).
 __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __restrict__ z, const float* __restrict__ dy,
                                                              const float* __restrict__ stats, int nsplit_s,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
     const int lpp = C >> 2, ppi = 256 / lpp, c4 = tid % lpp, pl = tid / lpp;
     const int cg = C / G;
     __shared__ double gred[256][2];
-    gn_block_stats(stats, nsplit_s, G, b, (double)HW * (double)cg, eps, gm, gr, gred);
+    gn_block_stats(stats, nsplit_s, G, b, HW, cg, eps, gm, gr, gred);
     const int64_t per = (HW + nsplit - 1) / nsplit;
     const int64_t p0 = split * per, p1 = (p0 + per < HW) ? p0 + per : HW;
     f32x4 t1 = {0, 0, 0, 0}, t2 = {0, 0, 0, 0};
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
         c1[c] = gamma[c] * t1; c2[c] = gamma[c] * t2;
     }
     __shared__ double red[256][2];
-    gn_block_stats(stats, nsplit_s, G, b, (double)HW * (double)cg, eps, gm, gr, red);      // (ends with a barrier: c1 / c2 are complete too)
+    gn_block_stats(stats, nsplit_s, G, b, HW, cg, eps, gm, gr, red);      // (ends with a barrier: c1 / c2 are complete too)
     if (tid < G) {
         float a1 = 0.f, a2 = 0.f;
         for (int c = tid * cg; c < (tid + 1) * cg; ++c) { a1 += c1[c]; a2 += c2[c]; }

@@ -97,29 +97,41 @@ __device__ __forceinline__ T ordered_sum(T first, const T* __restrict__ p, int64
     return s;
 }
 
-// GroupNorm: mean / rstd of every group of image b from the split partials {sum, sum of squares} that gn_stats_kernel wrote
-// ([b][split][group][2]).  Every consumer block needs them before it can start; with the partials of up to 256 splits one thread
-// per group walking them in sequence costs more than the streaming pass that follows, so all 256 threads take part: thread
-// (slice k, group g) adds splits k, k + nslice, ... in double, thread g then adds the slices in order (a fixed order: reproducible).
+// GroupNorm: mean / rstd of every group of image b from the split partials {sum, M2 about the split's own mean} that gn_stats_kernel
+// wrote ([b][split][group][2]; split i covers n_i = pixels of range i (per = ceil(HW / nsplit), the last one ragged, possibly none)
+// * cg values).  Pairwise update in double: with m_i = sum_i / n_i,  M2 = sum M2_i + sum n_i (m_i - m)^2.  Written about the pivot
+// P = m_0 so that one walk over the splits does: sum n_i (m_i - m)^2 = sum n_i (m_i - P)^2 - n (m - P)^2,
+// m - P = sum n_i (m_i - P) / n;
+// the differences are between split means, so nothing of size mean^2 is ever formed.  Every consumer block needs the result before it
+// can start; with the partials of up to 256 splits one thread per group walking them in sequence costs more than the streaming pass
+// that follows, so all 256 threads take part: thread (slice k, group g) adds splits k, k + nslice, ... in double, thread g then adds
+// the slices in order (a fixed order: reproducible).
+// var < 0 can only come from rounding in that last subtraction (a group that is constant up to its last bits): clamped.
 // Call from ALL threads of a 256-thread block; ends with a barrier.
-__device__ __forceinline__ void gn_block_stats(const float* __restrict__ stats, int nsplit, int G, int b, double n, float eps,
+__device__ __forceinline__ void gn_block_stats(const float* __restrict__ stats, int nsplit, int G, int b, int64_t HW, int cg, float eps,
                                                float* gm, float* gr, double (*red)[2]) {
     const int tid = threadIdx.x, nslice = 256 / G, g = tid % G, k = tid / G;
+    const int64_t per = (HW + nsplit - 1) / nsplit;
+    const float* base = stats + (int64_t)b * nsplit * G * 2 + g * 2;
+    const double piv = (double)base[0] / (double)((per < HW ? per : HW) * cg);       // mean of split 0 (never empty)
     double s = 0.0, q = 0.0;
     if (k < nslice)
         for (int sp = k; sp < nsplit; sp += nslice) {
-            const float* o = stats + (((int64_t)b * nsplit + sp) * G + g) * 2;
-            s += (double)o[0]; q += (double)o[1];
+            const int64_t p0 = sp * per, cnt = ((p0 + per < HW) ? p0 + per : HW) - p0;
+            if (cnt <= 0) continue;
+            const float* o = base + (int64_t)sp * G * 2;
+            const double ni = (double)(cnt * cg), dm = (double)o[0] / ni - piv;
+            s += ni * dm; q += (double)o[1] + ni * dm * dm;
         }
     red[tid][0] = s; red[tid][1] = q;
     __syncthreads();
     if (tid < G) {
         double ss = 0.0, qq = 0.0;
         for (int j = 0; j < nslice; ++j) { ss += red[j * G + tid][0]; qq += red[j * G + tid][1]; }
-        const double m = ss / n;
-        double var = qq / n - m * m;
+        const double n = (double)HW * (double)cg, dm = ss / n;
+        double var = qq / n - dm * dm;
         if (var < 0.0) var = 0.0;
-        gm[tid] = (float)m;
+        gm[tid] = (float)(piv + dm);
         gr[tid] = (float)(1.0 / sqrt(var + (double)eps));
     }
     __syncthreads();

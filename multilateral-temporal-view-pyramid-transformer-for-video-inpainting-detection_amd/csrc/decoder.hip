@@ -17,7 +17,14 @@ using namespace mumpy;
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
-// x (B, HW, C) NHWC.  grid (nsplit, B).  partial[((b*nsplit + s)*G + g)*2 + {0,1}] = {sum, sum of squares}
+// x (B, HW, C) NHWC.  grid (nsplit, B).  partial[((b*nsplit + s)*G + g)*2 + {0,1}] = {sum, M2}: the sum of the group's values in pixel
+// range s, and the sum of their squared distances from THAT RANGE'S OWN mean.  One pass, as shifted sums about a pivot K = the group's
+// first value in the range: S = sum (x - K), Q = sum (x - K)^2 in fp32, then (one thread per group, in double) sum = S + n K and
+// M2 = Q - S^2 / n.  K is one draw from the group: if it lies k sigma from the range's mean, Q is (1 + k^2) times M2 and the
+// subtraction loses that factor of fp32 precision -- typically a digit (not a bound: a lone outlier of 100 sigma as the first value
+// would cost four).  The plain sum of squares it replaces had lost var = E[x^2] - mean^2 to cancellation once |mean| was a few sigma
+// (a conv output that carries a bias), before anyone could combine it in double.  gn_block_stats (common.h) puts the ranges together.
+// n = pixels of the range (0 for a range past the end: per = ceil(HW / nsplit)) * channels per group.
 __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__ x, float* __restrict__ partial,
                                                        int64_t HW, int C, int G, int nsplit) {
     __shared__ float red[256][2];
@@ -25,13 +32,15 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     const int lpp = C >> 2;                 // lanes per pixel
     const int ppi = 256 / lpp;              // pixels per iteration
     const int c4 = tid % lpp, pl = tid / lpp;
+    const int cg4 = (C / G) >> 2;           // lanes per group inside a pixel slot
     const int64_t per = (HW + nsplit - 1) / nsplit;
     const int64_t p0 = split * per, p1 = (p0 + per < HW) ? p0 + per : HW;
     const float* xb = x + (int64_t)b * HW * C + 4 * c4;
+    const float K = (p0 < p1) ? x[((int64_t)b * HW + p0) * C + (c4 / cg4) * (C / G)] : 0.f;      // the same for every lane of a group
     float s = 0.f, q = 0.f;
     if (pl < ppi)
         for (int64_t p = p0 + pl; p < p1; p += ppi) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(xb + p * C);
+            const f32x4 v = *reinterpret_cast<const f32x4*>(xb + p * C) - K;
             s += (v.x + v.y) + (v.z + v.w);
             q += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
         }
@@ -39,7 +48,6 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
     red[tid][1] = q;
     __syncthreads();
     if (tid < G) {                          // fixed summation order: reproducible
-        const int cg4 = (C / G) >> 2;       // lanes per group inside a pixel slot
         float ss = 0.f, qq = 0.f;
         for (int slot = 0; slot < ppi; ++slot)
             for (int l = 0; l < cg4; ++l) {
@@ -47,9 +55,12 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const float* __restrict__
                 ss += red[t][0];
                 qq += red[t][1];
             }
+        const double n = (double)((p1 > p0 ? p1 - p0 : 0) * (C / G));
+        const double Kg = (p0 < p1) ? (double)x[((int64_t)b * HW + p0) * C + tid * (C / G)] : 0.0;
+        const double m2 = (n > 0.0) ? (double)qq - (double)ss * (double)ss / n : 0.0;
         float* o = partial + (((int64_t)b * nsplit + split) * G + tid) * 2;
-        o[0] = ss;
-        o[1] = qq;
+        o[0] = (float)((double)ss + n * Kg);
+        o[1] = (float)(m2 > 0.0 ? m2 : 0.0);
     }
 }
 
@@ -88,21 +99,21 @@ __device__ __forceinline__ void src_index(int o, int in, int out, int scale, int
 
 // grid (blocks, B); a thread produces 4 output channels of one output pixel
 __global__ __launch_bounds__(256) void gn_apply_resample_kernel(ApplyArgs a) {
-    __shared__ float sc[256], sh[256];
-    __shared__ float gm[32], gr[32];
+    __shared__ __align__(16) float sc[256], mu[256], be[256];       // per channel: out = (x - mu) * sc + be.  Centred before the scale: x * sc + (be - mu * sc)
+    __shared__ float gm[32], gr[32];                  // rounds at the size of mu * sc, which is |mean| / sigma times the output
     const int b = blockIdx.y, tid = threadIdx.x;
     const int C = a.C;
     if (a.partial) {
         __shared__ double red[256][2];
-        gn_block_stats(a.partial, a.nsplit, a.G, b, (double)a.H * a.W * (C / a.G), a.eps, gm, gr, red);
+        gn_block_stats(a.partial, a.nsplit, a.G, b, (int64_t)a.H * a.W, C / a.G, a.eps, gm, gr, red);
         for (int c = tid; c < C; c += 256) {
             const int g = c / (C / a.G);
-            const float s = gr[g] * a.gamma[c];
-            sc[c] = s;
-            sh[c] = a.beta[c] - gm[g] * s;
+            sc[c] = gr[g] * a.gamma[c];
+            mu[c] = gm[g];
+            be[c] = a.beta[c];
         }
     } else {
-        for (int c = tid; c < C; c += 256) { sc[c] = 1.f; sh[c] = 0.f; }
+        for (int c = tid; c < C; c += 256) { sc[c] = 1.f; mu[c] = 0.f; be[c] = 0.f; }
     }
     __syncthreads();
     const int Ho = a.H * a.scale, Wo = a.W * a.scale;
@@ -128,14 +139,14 @@ __global__ __launch_bounds__(256) void gn_apply_resample_kernel(ApplyArgs a) {
                     const f32x4 v = *reinterpret_cast<const f32x4*>(p + c0);
                     float m = 0.f;
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) m += activate(v[k] * sc[c0 + k] + sh[c0 + k], a.act);
+                    for (int k = 0; k < 4; ++k) m += activate((v[k] - mu[c0 + k]) * sc[c0 + k] + be[c0 + k], a.act);
                     r[e] = m * 0.25f;
                 }
             } else {
                 const int c0 = 4 * co4;
                 const f32x4 v = *reinterpret_cast<const f32x4*>(p + c0);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) r[k] = activate(v[k] * sc[c0 + k] + sh[c0 + k], a.act);
+                for (int k = 0; k < 4; ++k) r[k] = activate((v[k] - mu[c0 + k]) * sc[c0 + k] + be[c0 + k], a.act);
             }
             return r;
         };
