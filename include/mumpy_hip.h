@@ -52,6 +52,17 @@ extern "C" {
 
 int         mumpy_abi_version(void);
 const char* mumpy_last_error(void);
+/* The route of the most recent GEMM-family launch issued by the calling thread (mumpy_linear_*_fwd, mumpy_conv2d_nhwc_fwd,
+ * mumpy_linear_bf16s_fwd, mumpy_linear_bwd, mumpy_conv2d_wgrad_nhwc), as text valid until the thread's next call of this function:
+ *   "tiled tile=T ks=S np=N addr=A"     T: 0 128x128, 1 64x128, 2 64x64, 3 128x128 LDS-DMA; S: split-K factor launched;
+ *                                       N: bf16 pieces per operand (0 = fp32 products); A: dense | rows | kseg | conv
+ *   "tiled16 tile=T ks=1 np=1 addr=dense"                       bf16 storage, tiled kernel
+ *   "ws sched=whole|split P=p ln=none|producer|consumer addr=dense|conv"    persistent 128x128 kernel, p passes per chunk
+ *   "ws64 P=p addr=dense" / "ws16 P=p addr=dense"               persistent 64x64 kernel / persistent bf16-storage kernel
+ *   "xgemm np=N addr=dense|conv dx=WxS dw=WxS reduce=none|one|two-in-one|taps"     backward: wave tile W and split S of each
+ *                                       product ("-": not run), and the form of the slab reduce
+ *   "none" before the first such launch.  For tests and tools: a forced or planned route can be confirmed, not assumed. */
+const char* mumpy_last_route(void);
 /* 1: diagnostics build (`make TUNING=1`): planner / kernel A/B hooks read MUMPY_* environment variables.  0: the shipped library,
  * which reads no environment variable and keeps no mutable global state besides the thread-local error string and the cached
  * compute-unit count of the first device used. */

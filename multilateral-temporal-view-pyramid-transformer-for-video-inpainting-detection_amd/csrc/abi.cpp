@@ -11,6 +11,34 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
+thread_local Route g_route;
+static thread_local char g_route_text[160] = "";
+static const char* format_route() {
+    static const char* const addr[] = {"dense", "rows", "kseg", "conv"};
+    static const char* const ln[] = {"none", "producer", "consumer"};
+    static const char* const red[] = {"none", "one", "two-in-one", "taps"};
+    const Route& r = g_route;
+    char* t = g_route_text;
+    const size_t n = sizeof(g_route_text);
+    switch (r.family) {
+    case Route::TILED: snprintf(t, n, "tiled tile=%d ks=%d np=%d addr=%s", r.tile, r.ks, r.np, addr[r.addr & 3]); break;
+    case Route::TILED16: snprintf(t, n, "tiled16 tile=%d ks=%d np=%d addr=%s", r.tile, r.ks, r.np, addr[r.addr & 3]); break;
+    case Route::WS:
+        snprintf(t, n, "ws sched=%s P=%d ln=%s addr=%s", r.split ? "split" : "whole", r.passes, ln[r.ln < 3 ? r.ln : 0], addr[r.addr & 3]);
+        break;
+    case Route::WS64: snprintf(t, n, "ws64 P=%d addr=dense", r.passes); break;
+    case Route::WS16: snprintf(t, n, "ws16 P=%d addr=dense", r.passes); break;
+    case Route::XGEMM: {
+        char dx[24] = "-", dw[24] = "-";
+        if (r.prod[0].wt) snprintf(dx, sizeof(dx), "%dx%d", r.prod[0].wt, r.prod[0].ks);
+        if (r.prod[1].wt) snprintf(dw, sizeof(dw), "%dx%d", r.prod[1].wt, r.prod[1].ks);
+        snprintf(t, n, "xgemm np=%d addr=%s dx=%s dw=%s reduce=%s", r.np, addr[r.addr & 3], dx, dw, red[r.reduce & 3]);
+        break;
+    }
+    default: snprintf(t, n, "none");
+    }
+    return t;
+}
 #ifdef MUMPY_TUNING
 #include <stdlib.h>
 int tune_int(const char* name, int dflt) {
@@ -32,3 +60,4 @@ extern "C" int mumpy_tuning_build(void) {
 
 extern "C" int mumpy_abi_version(void) { return MUMPY_ABI_VERSION; }
 extern "C" const char* mumpy_last_error(void) { return mumpy::g_err; }
+extern "C" const char* mumpy_last_route(void) { return mumpy::format_route(); }

@@ -27,6 +27,27 @@ inline int tune_int(const char*, int dflt) { return dflt; }
 inline const char* tune_str(const char*) { return nullptr; }
 #endif
 
+// Route record: which kernel the most recent GEMM-family launch of the calling thread took (gemm.hip's launch_linear and
+// mumpy_linear_bf16s_fwd, gemm_bwd.hip's mumpy_linear_bwd and mumpy_conv2d_wgrad_nhwc).  A launch stores this POD; only
+// mumpy_last_route() (abi.cpp) turns it into text.  Present in both builds: a test that forces a route through the tuning hooks
+// reads here whether the force took effect (a split whose slabs do not fit, or a schedule without its workspace, is dropped silently).
+struct Route {
+    enum Family : uint8_t { NONE, TILED, TILED16, WS, WS64, WS16, XGEMM };
+    enum Addr : uint8_t { DENSE, ROWS, KSEG, CONV };
+    enum Reduce : uint8_t { R_NONE, R_ONE, R_TWO_IN_ONE, R_TAPS };
+    uint8_t family = NONE;
+    uint8_t tile = 0;        // tiled: Plan::tile as run (the bf16-piece family has only 0 and 2); tiled16: 0 wide, 2 narrow
+    uint8_t np = 0;          // bf16 pieces per operand (0: fp32 products)
+    uint8_t addr = DENSE;
+    uint8_t split = 0;       // ws: 1 = split schedule
+    uint8_t passes = 0;      // ws / ws64 / ws16: epilogue passes per chunk (the P of the instantiation)
+    uint8_t ln = 0;          // ws: 0 none, 1 LayerNorm producer, 2 consumer
+    uint8_t reduce = R_NONE; // xgemm
+    int ks = 1;              // tiled: split-K factor actually launched
+    struct { int wt, ks; } prod[2] = {{0, 0}, {0, 0}};      // xgemm: wave tile and split of the dX (0) and dW (1) products; wt 0 = not run
+};
+extern thread_local Route g_route;
+
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 

@@ -886,11 +886,22 @@ int launch_linear(const LinearArgs& a) {
     // which a kept workspace (mumpy_linear_wsz_fwd) promises to leave zero
     if (ws) { ws += 1024; ws_bytes -= 4096; }
     if (p.ksplit > 1 && (int64_t)p.ksplit * M * N * (int64_t)sizeof(float) > ws_bytes) p.ksplit = 1;
+    // The bf16-piece family has two tile shapes (launch_tiled_bf16: 128x128 and 64x64).  The planner only hands it tiles 0 and 2;
+    // MUMPY_GEMM_FORCE (tuning) can also ask for 3, which is the same wide kernel, and for 1, which it was never built for: with
+    // the 64x128 tile's grid the 64x64 kernel would leave every second 64-column band of y unwritten.  Re-routed here.
+    if (math_bf16 || math_x3) {
+        if (p.tile == 3) p.tile = 0;
+        if (p.tile == 1) { p.tile = 2; p.gn = (unsigned)((N + 63) / 64); }
+    }
     const int64_t grid = p.gm * p.gn * p.ksplit;
     MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "linear: too many tiles");
     static const bool use_glds = tune_int("MUMPY_GEMM_GLDS", 0) != 0;
     const bool wide = (p.tile == 0 || p.tile == 3);
     const TiledArgs t{a.x, a.W, a.bias, a.residual, a.y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg, grid, a.s};
+    g_route = Route{};
+    g_route.family = Route::TILED; g_route.tile = (uint8_t)p.tile; g_route.ks = p.ksplit;
+    g_route.np = math_x2 ? 2 : math_x3 ? 3 : math_bf16 ? 1 : 0;
+    g_route.addr = conv ? Route::CONV : a.kseg ? Route::KSEG : rpb < M ? Route::ROWS : Route::DENSE;
     if (math_x2) launch_tiled_bf16<2>(wide, conv != nullptr, t);
     else if (math_x3) launch_tiled_bf16<3>(wide, conv != nullptr, t);
     else if (math_bf16) launch_tiled_bf16<1>(wide, conv != nullptr, t);
@@ -999,6 +1010,8 @@ extern "C" int mumpy_linear_bf16s_fwd(const void* x, const void* W, const float*
     MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "linear_bf16s: too many tiles");
     const TiledArgs t{static_cast<const float*>(x), static_cast<const float*>(W), bias, residual, static_cast<float*>(y), M, N, K, act,
                       gn, 1, nullptr, M, 0, ConvGeom{0, 0, 0, 0, 0, 0, 0, 0, 0}, grid, s};
+    g_route = Route{};
+    g_route.family = Route::TILED16; g_route.tile = wide ? 0 : 2; g_route.np = 1;
     launch_tiled_bf16<1, true>(wide, out_bf16 != 0, t);
     MUMPY_CHECK_LAUNCH("linear_bf16s");
     return 0;

@@ -533,6 +533,7 @@ int launch_xgemm(bool a_t, const float* A, int64_t lda, const float* B, int64_t 
     a.R = R; a.C = C; a.KK = KK; a.ks = p.ks; a.chunks_per_split = p.cps; a.nchunks = p.nchunks; a.accum = accum; a.gc = p.gc;
     a.cvH = a.cvW = a.cv_kw = a.cv_ph = a.cv_pw = 0; a.cv_mhw = a.cv_shw = a.cv_mw = a.cv_sw = 0;
     const dim3 grid((unsigned)(p.gr * p.gc), (unsigned)p.ks);
+    g_route.prod[a_t ? 1 : 0] = {p.wt, p.ks};
     if (bf16) {
         if (p.wt == 64) {
             if (a_t) hipLaunchKernelGGL((xgemm16_kernel<64, true>), grid, dim3(256), 0, s, a);
@@ -624,12 +625,17 @@ extern "C" int mumpy_linear_bwd(const float* x, const float* W, const float* dy,
     float* ws_x = ws ? ws + w_bytes / 4 : nullptr;
     const int64_t ws_x_bytes = workspace ? workspace_bytes - w_bytes : 0;
     Deferred dfx{}, dfw{};
+    g_route = Route{};
+    g_route.family = Route::XGEMM; g_route.np = bf16 ? 1 : 0;
     if (dx)          // dX[M,K] = dY[M,N] W[N,K]
         if (int rc = launch_xgemm(false, dy, N, W, K, dx, K, (int)M, K, N, 0, ws_x, ws_x_bytes > 0 ? ws_x_bytes : 0, s, nullptr, 0, bf16,
                                   dW ? &dfx : nullptr)) return rc;
     if (dW)          // dW[N,K] (+)= dY^T X
         if (int rc = launch_xgemm(true, dy, N, x, K, dW, K, N, K, (int)M, accumulate & 1, ws, workspace ? workspace_bytes : 0, s, db,
                                   (accumulate >> 1) & 1, bf16, dx ? &dfw : nullptr)) return rc;
+    // (a product that is split without the other one wanted has run its own reduce inside launch_xgemm)
+    g_route.reduce = (dfx.pending && dfw.pending) ? Route::R_TWO_IN_ONE
+                     : (g_route.prod[0].ks > 1 || g_route.prod[1].ks > 1) ? Route::R_ONE : Route::R_NONE;
     if (dfx.pending && dfw.pending) {
         hipLaunchKernelGGL(xgemm_reduce2_kernel, dim3(dfx.job.blocks + dfw.job.blocks), dim3(256), 0, s, dfx.job, dfw.job, dfw.rs);
         MUMPY_CHECK_LAUNCH("linear_bwd(reduce x2)");
@@ -678,6 +684,9 @@ extern "C" int mumpy_conv2d_wgrad_nhwc(const float* x, const float* dy, float* d
     magic_div31((unsigned)W, a.cv_mw, a.cv_sw);
     hipStream_t s = as_stream(stream);
     const dim3 grid((unsigned)(p.gr * p.gc), (unsigned)p.ks, (unsigned)taps);
+    g_route = Route{};
+    g_route.family = Route::XGEMM; g_route.np = bf16 ? 1 : 0; g_route.addr = Route::CONV;
+    g_route.prod[1] = {p.wt, p.ks}; g_route.reduce = p.ks > 1 ? Route::R_TAPS : Route::R_NONE;
     if (bf16 && p.wt == 64) hipLaunchKernelGGL((xgemm16_kernel<64, true, true>), grid, dim3(256), 0, s, a);
     else if (bf16) hipLaunchKernelGGL((xgemm16_kernel<32, true, true>), grid, dim3(256), 0, s, a);
     else if (p.wt == 64) hipLaunchKernelGGL((xgemm_kernel<64, true, true>), grid, dim3(256), 0, s, a);

@@ -856,6 +856,9 @@ inline int launch(const float* x, const float* W, const float* bias, const float
             if (e != hipSuccess) { set_error("gemm_ws: flag reset failed: %s", hipGetErrorString(e)); return (int)e; }
         }
     }
+    g_route = Route{};
+    g_route.family = Route::WS; g_route.addr = cv ? Route::CONV : Route::DENSE;
+    g_route.split = split; g_route.passes = (uint8_t)P; g_route.ln = (uint8_t)ln_mode;
     return with_passes(P, [&](auto pc) {
         constexpr int PC = decltype(pc)::value;
         if (cv) return launch_ws<gemm_ws_kernel<PC, true>>(grid, LDS_BYTES, LDS_BYTES, s, p);
@@ -878,6 +881,8 @@ inline int launch16(const void* x16, const void* W16, const float* bias, const f
     const unsigned grid = base_params(p, x16, W16, bias, residual, y, M, N, K, act, BM, 64, (unsigned)num_cu);
     const int P = passes_per_chunk(PASSES, p.nk);
     p.lmin = 1 + PASSES / P;
+    g_route = Route{};
+    g_route.family = Route::WS16; g_route.passes = (uint8_t)P;
     return with_passes(P, [&](auto pc) {
         constexpr int PC = decltype(pc)::value;
         if (out_bf16) return launch_ws<gemm_ws_kernel<PC, false, 1>>(grid, LDS_BYTES, LDS_BYTES, s, p);

@@ -242,6 +242,8 @@ inline int launch(const float* x, const float* W, const float* bias, const float
     const unsigned grid = gemm_ws::base_params(p, x, W, bias, residual, y, M, N, K, act, T, BK, (unsigned)per_cu * (unsigned)num_cu);
     const int P = gemm_ws::passes_per_chunk(PASSES, p.nk);        // (4 passes per tile: at most 4 per chunk)
     const int lds_bytes = per_cu == 1 ? 2 * LDS_BYTES + 1024 : LDS_BYTES;
+    g_route = Route{};
+    g_route.family = Route::WS64; g_route.passes = (uint8_t)(P > 4 ? 4 : P);
     return gemm_ws::with_passes<4>(P, [&](auto pc) {
         return gemm_ws::launch_ws<gemm_ws64_kernel<decltype(pc)::value>>(grid, lds_bytes, 2 * LDS_BYTES + 1024, s, p, "gemm_ws64");
     });

@@ -148,6 +148,8 @@ def load_library():
     lib = ctypes.CDLL(path)
     lib.mumpy_abi_version.restype = c_i
     lib.mumpy_last_error.restype = ctypes.c_char_p
+    lib.mumpy_last_route.restype = ctypes.c_char_p      # (AttributeError = stale library, as below)
+    lib.mumpy_last_route.argtypes = []
     if lib.mumpy_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.mumpy_abi_version()} != binding {ABI_VERSION}; rebuild")
     for name, args in SIGNATURES.items():

@@ -12,6 +12,7 @@
 
 namespace mumpy {
 void set_error(const char* fmt, ...) { fprintf(stderr, "error: %s\n", fmt); }
+thread_local Route g_route;      // (the library's lives in abi.cpp)
 }
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_)); exit(1); } } while (0)
