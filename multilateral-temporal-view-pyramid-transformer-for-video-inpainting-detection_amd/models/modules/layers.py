@@ -4,7 +4,7 @@ import collections.abc
 import torch
 import torch.nn as nn
 
-from mumpy_hip.state import weights_epoch
+from mumpy_hip.state import derived_seen, weights_epoch
 
 
 def to_2tuple(x):
@@ -64,21 +64,53 @@ class ConfigDict(dict):
 
 
 class Derived:
-    """Cache of a tensor derived from parameters/buffers (transposed weights, expanded bias tables, compacted masks);
-    recomputed when any source's storage, version or device changes (load_state_dict, .cuda(), a torch optimizer step) or
-    when a HIP kernel rewrote parameters in place (mumpy_hip.state.weights_epoch, bumped by FlatAdamW.step)."""
+    """Cache of a tensor derived from parameters/buffers (transposed weights, expanded bias tables, compacted masks).
+
+    The key is, per source, (storage address, tensor version, device), plus mumpy_hip.state.weights_epoch when any source is an
+    nn.Parameter (trainable or frozen).  Followed by themselves, because torch moves the version or the address: load_state_dict,
+    a torch.optim step, any in-place op under no_grad (an EMA update, nn.init.*_), `p.data = new`, .to() / .cuda() / .double().
+    Followed through the epoch: FlatAdamW / FlatSGD / FlatRMSprop steps (a HIP kernel rewrites the weights; they bump it).
+    NOT seen: an in-place edit through `.data` (p.data.mul_(), p.data.copy_()) -- `.data` has a version counter of its own -- and
+    an nn.Parameter object swapped for another one while nothing calls the module.  After those call
+    mumpy_hip.state.bump_weights_epoch().  Buffer-only keys (attn_mask, relative_position_index) ignore the epoch: no optimizer
+    writes them, and rebuilding the compacted mask synchronises with the host, which a captured training step must not do.
+
+    The cache keeps an alias of each source it was built from, so a storage it has seen stays allocated until the next rebuild
+    and a replacement (`p.data = new`, a .to() round trip) can never come back at the same address with the same version.
+    A copy of the owning module (copy.deepcopy, pickling) starts with an empty cache."""
 
     def __init__(self):
         self._key = None
         self._val = None
+        self._sources = ()
+        self._held = ()
+
+    def __reduce__(self):
+        return (Derived, ())
+
+    @staticmethod
+    def _key_of(sources):
+        epoch = weights_epoch[0] if any(isinstance(s, nn.Parameter) for s in sources) else 0
+        return (epoch,) + tuple((s.data_ptr(), s._version, s.device) for s in sources)
+
+    @property
+    def key(self):
+        """What the cached value was built from; a value built later has another key."""
+        return self._key
+
+    def current(self):
+        """True while the sources of the last get() are what the cached value was built from (fn is not called)."""
+        return self._key is not None and self._key == self._key_of(self._sources)
 
     def get(self, sources, fn):
-        # the optimizer epoch only matters for sources an optimizer can rewrite (parameters); buffers such as attn_mask keep
-        # their cache across steps (and stay host-sync free inside a captured training step)
-        epoch = weights_epoch[0] if any(getattr(s, "requires_grad", False) for s in sources) else 0
-        key = (epoch,) + tuple((s.data_ptr(), s._version, str(s.device)) for s in sources)
+        seen = derived_seen[0]
+        if seen is not None:               # a GraphedForward is warming up: it re-checks these keys before every replay
+            seen.append(self)
+        key = self._key_of(sources)
         if key != self._key:
             with torch.no_grad():
                 self._val = fn()
             self._key = key
+            self._sources = tuple(sources)
+            self._held = tuple(s.detach() for s in sources)
         return self._val
