@@ -288,6 +288,16 @@ int mumpy_deform_attention_fwd(const float* q, const float* kv, const float* pad
 int mumpy_deform_attention_mm16_fwd(const float* q, const float* kv, const float* padmask, float* out, int B, int H,
                                     int W, int C, int r, float scale, void* stream);
 
+/* ---- launch plans of the attention cores: pure host functions of the shape, no GPU needed ----
+ * Which form a launch of mumpy_window_attention_fwd / mumpy_deform_attention_fwd with this shape takes.  Bit 0 = split: a small
+ * grid runs each (window, head) unit on two waves, one per 32-query tile.  Bit 1 = ring: K/V of a wave's next unit prefetched
+ * through LDS (reserved; no launch sets it).  Every form computes bitwise the same output.  mumpy_window_attention_bf16_plan is
+ * the plan of the bf16-storage entry points (mumpy_window_attention_bf16_fwd / _bf16mm_fwd): always 0.  MUMPY_EINVAL for a shape
+ * the entry points reject. */
+int mumpy_window_attention_plan(int B, int Hs, int W, int C);
+int mumpy_window_attention_bf16_plan(int B, int Hs, int W, int C);
+int mumpy_deform_attention_plan(int B, int H, int W, int C, int r);
+
 /* combine (deform:403 un-permuted reshape + mTVE:138 + mTVE:285-286):
  *   out[b, n*49+p, c] = x1[b, n*49+p, c] + x1[b, raster(n,p), c] + Yt[b*nWf+n][(p*C+c) % 49][(p*C+c) / 49]
  * x1, out: (B, H*W, C) (out must not alias x1); Yt: (B*nWf, 49, C) = proj_out output, window-major. */

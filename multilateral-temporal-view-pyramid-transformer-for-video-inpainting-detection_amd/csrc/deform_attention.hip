@@ -3,6 +3,20 @@
 // (win_attn_unit.h), fp32 MFMA, but not persistent: no bias table (only the 49 -> 64 key padding), the scale on the product, q
 // gathered from the raster, k/v window-major.
 //
+// Small grids: one unit on two waves (win_attn_cross_kernel<SPLIT = true>; mumpy_deform_attention_plan bit 0).  The launches of the
+// forward have 192 .. 1,536 units: one wave per unit leaves most of the chip idle while each wave walks r x 114 MFMAs alone.  Split by
+// 32-query tile the chain is r x 57 MFMAs; the r kv windows stay inside each wave in the order t = 0 .. r-1, so the output is bitwise
+// the same (tests/test_window_attention_schedule.py).  Fitted rule (cross_plan): split while units <= 1,024 -- what 256 CUs x 2
+// resident blocks x 2 units hold, i.e. while every split block is resident at once.  Both forms of every shape of the B=8, T=5 forward
+// (each launched with r = 1 against view 2 and r = 5 against view 3), timed on one MI355X against the parent commit's library
+// (tools/kernel_micro.py cva_attn: medians of 12 alternating replays of 20 captured launches, us per launch; "whole" = <SPLIT = false>;
+// the parent's own repeats differ by <= 0.1 us):
+//   (B, H, W, C)      units   r = 1: parent  whole  split     r = 5: parent  whole  split     plan
+//   (8, 56, 56,  96)  1,536          15.9   15.9   15.0             56.5   56.6   56.9      whole (r = 5 is slower split)
+//   (8, 28, 28, 192)    768          10.2   10.1    9.7             35.7   35.6   32.8      split
+//   (8, 14, 14, 384)    384           9.5    9.5    6.9             34.6   34.6   22.9      split
+//   (8,  7,  7, 768)    192           9.3    9.2    6.7             33.3   33.3   21.6      split
+//
 // win_attn_cross_mm16_kernel (mumpy_deform_attention_mm16_fwd; opt-in, ops.set_cva_math("bf16")) is the forward on
 // v_mfma_f32_32x32x16_bf16, built like win_attn_self_bf16mm_kernel<IO32 = true>: q / k rows rounded to bf16 in registers, S^T = K Q^T
 // so that the exponentials feed P V from the accumulator registers, V gathered in that permuted key order, the scale on the fp32 scores,
@@ -11,7 +25,8 @@
 //
 // Replaces: the attention + "(b t)->b t" sum of SwinDAttention (deform:360-395).
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs + AGPRs / SGPRs / LDS per block / waves per SIMD; no scratch):
-//   win_attn_cross_kernel 229 + 0 / 47 / 1,024 B / 2;   win_attn_cross_mm16_kernel 160 + 0 / 46 / 3,072 B / 3;
+//   win_attn_cross_kernel<false> 229 + 0 / 47 / 1,024 B / 2;   win_attn_cross_kernel<true> 194 + 0 / 50 / 1,024 B / 2 (no spills);
+//   win_attn_cross_mm16_kernel 160 + 0 / 46 / 3,072 B / 3;
 //   deform_attn_bwd_q_kernel 180 + 80 / 40 / 0 / 1;   deform_attn_bwd_kv_kernel 256 + 62 / 44 / 0 / 1
 #include <stdlib.h>
 #include "win_attn_unit.h"
@@ -32,17 +47,25 @@ struct CrossArgs {
 __device__ __forceinline__ f32x4 pad_bias(int jt, int g, int h) { return pad_key52(f32x4{0.f, 0.f, 0.f, 0.f}, jt, g, h); }
 
 // ---------------------------------------------------------------------------------------------------------------
+// SPLIT (small grids, see cross_plan): ONE unit on TWO waves, split by query tile.  The two 32-query tiles of a unit share only K
+// and V, so wave 2p + it of a block takes tile `it` of the block's unit p: per kv window it loads all of K and V (the second reader
+// hits L2) and its own 32 queries and runs one qk_product / bias_softmax / pv_product.  The loop over the r kv windows stays inside
+// the wave, in the order t = 0 .. r-1, and every product and softmax is the same instruction sequence on the same values, so the
+// outputs are bitwise those of the one-wave form; a unit's dependent chain is roughly half as long.
+template <bool SPLIT>
 __global__ __launch_bounds__(256, 2) void win_attn_cross_kernel(CrossArgs a) {
     __shared__ int tok_tab[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
-    const int64_t u = (int64_t)blockIdx.x * 4 + wave;
+    const int it0 = SPLIT ? __builtin_amdgcn_readfirstlane(wave & 1) : 0;      // SPLIT: this wave's query tile
+    const int64_t u = SPLIT ? (int64_t)blockIdx.x * 2 + (wave >> 1) : (int64_t)blockIdx.x * 4 + wave;
     if (u >= a.units) return;
     const int head = (int)(u % a.nH);
     const int64_t b1 = u / a.nH;                 // output window
     int* tt = tok_tab[wave];
     const int64_t L = (int64_t)a.H * a.W;
-    f32x16 o[2] = {};
+    constexpr int NT = SPLIT ? 1 : 2;            // query tiles of this wave
+    f32x16 o[NT] = {};
 
     for (int t = 0; t < a.r; ++t) {
         const int64_t b2 = b1 * a.r + t;                  // kv window; adjacent r-tuples are summed (deform:394-395)
@@ -54,30 +77,39 @@ __global__ __launch_bounds__(256, 2) void win_attn_cross_kernel(CrossArgs a) {
         __builtin_amdgcn_wave_barrier();
         const float* qbase = a.q + ((int64_t)qb * L) * a.C + head * HD;
         const float* kbase = a.kv + b2 * WT * 2 * a.C + head * HD;
-        f32x4 qf[2][4], kf[2][4];
+        f32x4 qf[NT][4], kf[2][4];
 #pragma unroll
         for (int tl = 0; tl < 2; ++tl) {
             const int p = 32 * tl + c;
             const bool valid = p < WT;
-            load_frag(qf[tl], qbase + (int64_t)tt[p & 63] * a.C + 16 * h, valid);
+            if (!SPLIT) load_frag(qf[tl], qbase + (int64_t)tt[p & 63] * a.C + 16 * h, valid);
             load_frag(kf[tl], kbase + (int64_t)(valid ? p : 0) * 2 * a.C + 16 * h, valid);
+        }
+        if (SPLIT) {
+            const int p = 32 * it0 + c;
+            load_frag(qf[0], qbase + (int64_t)tt[p & 63] * a.C + 16 * h, p < WT);
         }
         float vf[2][16];
         const float* vbase = kbase + a.C;
         load_v(vf, [&](int j) { return vbase + (int64_t)j * 2 * a.C; }, c, h);
 
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
+        for (int it = 0; it < NT; ++it) {
             f32x16 s[2] = {};
             qk_product(s, kf, qf[it]);
-            bias_softmax<false>(s, [&](int jt, int g) { return pad_bias(jt, g, h); }, nullptr, 32 * it + c, h,
+            bias_softmax<false>(s, [&](int jt, int g) { return pad_bias(jt, g, h); }, nullptr, 32 * (it0 + it) + c, h,
                                 a.scale);                                       // scale on the product (deform:364)
             pv_product(o[it], s, vf);
         }
     }
     float* obase = a.out + b1 * WT * a.C + head * HD;
-    store_o(o[0], 0, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
-    store_o(o[1], 1, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
+    if constexpr (SPLIT) {
+        if (it0 == 0) store_o(o[0], 0, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
+        else store_o(o[0], 1, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
+    } else {
+        store_o(o[0], 0, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
+        store_o(o[1], 1, [&](int i) { return obase + (int64_t)i * a.C; }, c, h);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -312,6 +344,19 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs
 
 }  // namespace
 
+// Which form a launch of the fp32 forward takes: bit 0 = split (win_attn_cross_kernel<true>: one unit on two waves), bit 1 = ring
+// (never set here: the name of the bit in mumpy_window_attention_plan).  A pure function of the unit count: split while `units` is
+// at most CROSS_SPLIT_UNITS (the fitted rule and its table are in the file header).  MUMPY_CVA_SPLIT_UNITS moves the threshold in
+// the tuning build; it is read per launch there so that tools/kernel_micro.py can time both forms in one process.
+constexpr int CROSS_SPLIT_UNITS = 1024;
+static int cross_plan(int64_t units) { return units <= tune_int("MUMPY_CVA_SPLIT_UNITS", CROSS_SPLIT_UNITS) ? 1 : 0; }
+
+extern "C" int mumpy_deform_attention_plan(int B, int H, int W, int C, int r) {
+    MUMPY_REQUIRE(B > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && r >= 1 && C > 0 && C % HD == 0, MUMPY_EINVAL,
+                  "deform_attention_plan: bad shape (%d,%d,%d,%d) or ratio %d", B, H, W, C, r);
+    return cross_plan((int64_t)B * (H / WS) * (W / WS) * (C / HD));
+}
+
 // one validation + launch body for both forward kernels; `who` names the entry in mumpy_last_error
 template <bool MM16>
 static int cross_launch(const char* who, const float* q, const float* kv, const float* padmask, float* out, int B, int H, int W, int C,
@@ -333,7 +378,10 @@ static int cross_launch(const char* who, const float* q, const float* kv, const 
         MUMPY_REQUIRE((int64_t)H * W * C * 4 < (1ll << 32), MUMPY_ERANGE, "%s: image too large for 32-bit row offsets", who);
         hipLaunchKernelGGL(win_attn_cross_mm16_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     } else {
-        hipLaunchKernelGGL(win_attn_cross_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+        if (cross_plan(a.units) & 1)
+            hipLaunchKernelGGL(win_attn_cross_kernel<true>, dim3((unsigned)((a.units + 1) / 2)), dim3(256), 0, as_stream(stream), a);
+        else
+            hipLaunchKernelGGL(win_attn_cross_kernel<false>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     }
     MUMPY_CHECK_LAUNCH(who);
     return 0;

@@ -1,6 +1,6 @@
 // window_attention.hip — forward of the Swin window attention core (self-attention), one (window, head) unit per wave,
 // everything in registers: win_attn_self_kernel (fp32 MFMA; fp32 or bf16 storage; the LDS-free "background" form),
-// win_attn_self_bf16mm_kernel (bf16 MFMA; bf16 or fp32 storage), the relative-position bias expansion, their entry points.
+// win_attn_self_split_kernel (the same unit on two waves, for grids too small to fill the chip), win_attn_self_bf16mm_kernel (bf16 MFMA; bf16 or fp32 storage), the relative-position bias expansion, their entry points.
 // The unit's data flow and the helpers every attention kernel shares are in win_attn_unit.h; the backward is
 // window_attention_bwd.hip, the deformable cross-view attention deform_attention.hip.
 //
@@ -12,6 +12,7 @@
 //   win_attn_self_kernel<DBG=0, IO16=1>         159 / 71 /   0 B / 15,376 B / 3
 //   win_attn_self_kernel<DBG=0, IO16=0, NOLDS>  128 / 70 / 296 B /      0 B / 4
 //   win_attn_self_kernel<DBG=1> (diagnostic)    166 / 81 /   0 B / 15,376 B / 3
+//   win_attn_self_split_kernel                  136 / 46 /   0 B /  2,048 B / 3   (no spills)
 //   win_attn_self_bf16mm_kernel<IO32=0>         134 / 71 /   0 B / 16,400 B / 3
 //   win_attn_self_bf16mm_kernel<IO32=1>         146 / 68 /   0 B / 16,400 B / 3
 // No AGPRs anywhere.
@@ -31,7 +32,30 @@
 // change: a per-wave s_memtime trace shows the SIMD busy in some wave's compute phase ~all the time; the remaining gap
 // is the memory phase of a unit not overlapping its own wave's compute); cross-unit REGISTER prefetch at 2 waves/SIMD
 // (spills) and at 1 wave/SIMD (no overlap: hipcc's waitcnt insertion drains loop-carried prefetches); row-coalesced q/k
-// address pattern (-5 %, needs an LDS transpose).  Next step: K/V of the next unit through an LDS-DMA ring at 2 waves/SIMD.
+// address pattern (-5 %, needs an LDS transpose).
+// Not built: K/V of the next unit through an LDS-DMA ring at 2 waves/SIMD.  It can only help launches in which a wave walks
+// several units: since the split form below, those are the 10,240- and 5,120-unit launches, FOUR launches of the B=8, T=5
+// forward (2 x 58 us + 2 x 32 us).  With the memory phase hidden completely (the 46 us "MFMAs + softmax only" ablation against
+// 65.9 us: 30 %) that is at most ~0.05 ms of a 21.5 ms forward, below what the benchmark resolves (profiles/window_attention_overlap.md).
+//
+// Small grids: one unit on two waves (win_attn_self_split_kernel; mumpy_window_attention_plan bit 0).  Up to 2,560 units the
+// persistent form gives every wave ONE unit (768 blocks x 4 waves hold 3,072), so the launch is one unit's dependent chain
+// with the chip's waves in lockstep: everybody loads, then everybody computes.  The split form halves that chain (one 32-query
+// tile per wave), drops the bias staging round trip ahead of it, and above 1,536 units runs as two rounds of blocks whose memory
+// and compute phases overlap.  Bitwise the same output (tests/test_window_attention_schedule.py).
+// Fitted rule (self_plan): split while units <= 2,560.  Both forms of every self-attention shape of the B=8, T=5 forward, timed on
+// one MI355X against the parent commit's library (tools/kernel_micro.py winattn_ab: medians of 12 alternating replays of 20 captured
+// launches, us per launch; "whole" = this file's persistent form; the parent's own repeats differ by <= 0.1 us, 1.1 us on the largest):
+//   (B, Hs, W, C)      units   shift 0: parent  whole  split     shift 3: parent  whole  split     plan
+//   (8, 280, 56, 128) 10,240            57.9   58.9   63.1                58.0   57.9   64.7      whole
+//   (8, 140, 28, 256)  5,120            30.7   30.7   35.9                34.3   34.4   36.5      whole
+//   (8,  70, 14, 512)  2,560            22.4   22.4   21.8                24.5   24.5   22.4      split
+//   (8,  56, 56,  96)  1,536            15.6   15.6   13.4                16.9   17.0   13.9      split
+//   (8,  35,  7, 1024) 1,280            14.7   14.7   12.7                 --                     split
+//   (8,  28, 28, 192)    768             9.8    9.9    9.5                11.2   11.1   10.5      split
+//   (8,  14, 14, 384)    384             9.2    9.1    6.8                10.3   10.4    7.1      split
+//   (8,   7,  7, 768)    192             8.9    8.9    6.6                 --                     split
+// The split form reads K and V twice (the second wave of a pair hits L2), which is what it loses on the two HBM-bound launches.
 #include <stdlib.h>
 #include "win_attn_unit.h"
 
@@ -187,6 +211,79 @@ __global__ __launch_bounds__(256, (NOLDS ? 4 : 3)) void win_attn_self_kernel(Sel
     if (mask_w) tiles(std::true_type{}); else tiles(std::false_type{});
     __builtin_amdgcn_wave_barrier();   // the token tables are rewritten by the next unit
     }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Small grids (window_attention_split): ONE unit on TWO waves, split by query tile.  A launch of a few hundred units leaves most
+// of the chip idle while each wave walks its unit's dependent chain alone (bias staging + block barrier, token table, loads,
+// 2 x (32 + 25 MFMAs around a softmax), stores).  The two 32-query tiles of a unit share only K and V, so here wave 2p + it of
+// a block takes tile `it` of the block's window p: it loads all of K and V (the second reader hits L2), its own 32 queries, and
+// runs ONE qk_product / bias_softmax / pv_product.  A block is one head x 2 windows and is not persistent (one unit pair per
+// block, at most 1,280 blocks: see the fitted rule in the file header).  The bias row of the lane's query comes
+// straight from the global table, issued with the q/k/v loads: one round trip instead of the staged table's load -> LDS ->
+// block barrier ahead of them (the L1 tag cycles that made the row-strided reads slow in a streaming launch do not matter
+// on a single unit's chain).
+// Every value is computed by the same instructions in the same order as in win_attn_self_kernel (the MFMA k order, q * scale,
+// s + bias (+ mask), max / exp / sum / normalise over the same registers, the cross-half exchanges), so outputs are bitwise
+// those of the one-wave form.  fp32 storage and math only.
+__global__ __launch_bounds__(256, 2) void win_attn_self_split_kernel(SelfArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t tok_in[4][64];
+    __shared__ __attribute__((aligned(16))) uint32_t tok_out[4][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int head = blockIdx.x % a.nH;
+    const int it = wave & 1;                                             // this wave's query tile
+    const int64_t bw = (int64_t)(blockIdx.x / a.nH) * 2 + (wave >> 1);
+    if (bw >= (int64_t)a.B * a.nW) return;                               // odd window count: no block barrier below
+    const int64_t L = (int64_t)a.Hs * a.W;
+    uint32_t* ti = tok_in[wave];
+    uint32_t* to = tok_out[wave];
+    const int64_t b = unit_tokens(a, bw, lane, 12u * a.C, 4u * a.C, ti, to);
+    const char* base = reinterpret_cast<const char*>(a.qkv + b * L * 3 * a.C + head * HD);
+    const char* kbase = base + 4 * a.C;
+    const char* vbase = base + 8 * a.C;
+    const int qi = 32 * it + c;
+
+    f32x4 qf[4], kf[2][4], bq[2][4];
+    float vf[2][16];
+    const uint32_t qoff = ti[qi] + 64u * h;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qf[i] = *at16(base, qoff + 16u * i);
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        const uint32_t off = ti[32 * t + c] + 64u * h;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) kf[t][i] = *at16(kbase, off + 16u * i);
+    }
+    for_pv_steps([&](int jt, int g, int e) {
+        vf[jt][4 * g + e] = *reinterpret_cast<const float*>(vbase + (ti[32 * jt + 8 * g + 4 * h + e] + 4u * c));
+    });
+    const float* brow = a.bias + (int64_t)head * 4096 + (qi < WT ? qi : WT - 1) * 64 + 4 * h;   // as bias_row: padded queries re-read row 48
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (!(jt == 1 && g == 3)) bq[jt][g] = *reinterpret_cast<const f32x4*>(brow + 32 * jt + 8 * g);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) qf[i] *= a.scale;                        // q = q * scale before QK^T (swin:145)
+
+    const float* mask_w = unit_mask(a, bw);
+    f32x16 s[2];
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s[jt][r] = 0.f;
+    qk_product(s, kf, qf);
+    auto bias_at = [&](int jt, int g) { return pad_key52(bq[jt][g], jt, g, h); };
+    if (mask_w) bias_softmax<true>(s, bias_at, mask_w, qi, h, 1.0f);
+    else bias_softmax<false>(s, bias_at, mask_w, qi, h, 1.0f);
+    f32x16 o = {};
+    pv_product(o, s, vf);
+    char* obase = reinterpret_cast<char*>(a.out + b * L * a.C + head * HD);
+    auto orow = [&](int i) { return reinterpret_cast<float*>(obase + to[i]); };
+    if (it == 0) store_o(o, 0, orow, c, h);
+    else store_o(o, 1, orow, c, h);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -371,6 +468,16 @@ static int64_t bf16mm_groups(int64_t quads, int nH) {
     return (quads + per - 1) / per;
 }
 
+// Which form a launch takes: bit 0 = split (win_attn_self_split_kernel: one unit on two waves), bit 1 = K/V ring (reserved: no
+// launch takes it, see the file header).  A pure function of the entry point and the shape.  Only the fp32 entry point splits, and
+// only while `units` is at most SPLIT_UNITS (the fitted rule and its table are in the file header).  MUMPY_WA_SPLIT_UNITS moves the
+// threshold in the tuning build; it is read per launch there so that tools/kernel_micro.py can time both forms in one process.
+constexpr int SPLIT_UNITS = 2560;
+static int self_plan(SelfKind kind, int64_t units) {
+    if (kind.storage != Storage::F32 || kind.math != Math::F32 || kind.background) return 0;
+    return units <= tune_int("MUMPY_WA_SPLIT_UNITS", SPLIT_UNITS) ? 1 : 0;
+}
+
 static int window_attention_launch(SelfKind kind, const float* qkv, float* out, const float* bias, const float* mask_tab,
                                    const int32_t* mask_id, int n_mask, int B, int Hs, int W, int C, int shift, float scale,
                                    void* stream) {
@@ -402,6 +509,8 @@ static int window_attention_launch(SelfKind kind, const float* qkv, float* out, 
     else if (kind.background) hipLaunchKernelGGL((win_attn_self_kernel<false, false, true>), grid, block, 0, s, a);
     else if (io16) hipLaunchKernelGGL((win_attn_self_kernel<false, true>), grid, block, 0, s, a);
     else if (dbgmask) hipLaunchKernelGGL((win_attn_self_kernel<true, false>), grid, block, 0, s, a);
+    else if (self_plan(kind, a.units) & 1)
+        hipLaunchKernelGGL(win_attn_self_split_kernel, dim3((unsigned)((((int64_t)B * a.nW + 1) / 2) * a.nH)), block, 0, s, a);
     else hipLaunchKernelGGL((win_attn_self_kernel<false, false>), grid, block, 0, s, a);
     MUMPY_CHECK_LAUNCH("window_attention");
     return 0;
@@ -412,6 +521,20 @@ extern "C" int mumpy_window_attention_fwd(const float* qkv, float* out, const fl
                                           float scale, void* stream) {
     return window_attention_launch({Storage::F32, Math::F32, false}, qkv, out, bias, mask_tab, mask_id, n_mask, B, Hs, W, C, shift, scale,
                                    stream);
+}
+
+// The launch form of mumpy_window_attention_fwd / of the bf16-storage entry points for this shape (self_plan; no GPU needed):
+// bit 0 = split, bit 1 = ring; negative = the shape is one the entry points reject.
+static int window_attention_plan(SelfKind kind, int B, int Hs, int W, int C) {
+    MUMPY_REQUIRE(B > 0 && Hs > 0 && W > 0 && Hs % WS == 0 && W % WS == 0 && C > 0 && C % HD == 0, MUMPY_EINVAL,
+                  "window_attention_plan: bad shape (%d,%d,%d,%d)", B, Hs, W, C);
+    return self_plan(kind, (int64_t)B * (Hs / WS) * (W / WS) * (C / HD));
+}
+extern "C" int mumpy_window_attention_plan(int B, int Hs, int W, int C) {
+    return window_attention_plan({Storage::F32, Math::F32, false}, B, Hs, W, C);
+}
+extern "C" int mumpy_window_attention_bf16_plan(int B, int Hs, int W, int C) {
+    return window_attention_plan({Storage::BF16, Math::F32, false}, B, Hs, W, C);
 }
 
 // "Background" form: identical arithmetic and results, NO LDS allocation (token tables in registers via ds_bpermute, bias rows from

@@ -49,6 +49,9 @@ SIGNATURES = {
     "mumpy_deform_sample_kv_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
     "mumpy_deform_out_combine_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
     "mumpy_deform_attention_mm16_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+    "mumpy_window_attention_plan": [c_i, c_i, c_i, c_i],
+    "mumpy_window_attention_bf16_plan": [c_i, c_i, c_i, c_i],
+    "mumpy_deform_attention_plan": [c_i, c_i, c_i, c_i, c_i],
     "mumpy_deform_sample_kv_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
     "mumpy_deform_out_combine_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
     "mumpy_deform_combine_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],

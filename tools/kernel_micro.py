@@ -8,7 +8,15 @@
   | kernel_micro.py winattn_mm16 B Hs W C shift   fp32-stored qkv: mumpy_window_attention_fwd and the bf16-MFMA forward of the training
                                                 tape (window_attention_mm16) on the same input, same alternating protocol
   | kernel_micro.py winattn_bwd16 B Hs W C shift  the fp32 backward pair and the bf16-MFMA pair (window_attention_bwd math="fp32" /
-                                                "bf16", each with its reduce and table kernels) on the same input, same protocol"""
+                                                "bf16", each with its reduce and table kernels) on the same input, same protocol
+  | kernel_micro.py winattn_ab B Hs W C shift     mumpy_window_attention_fwd of several LIBRARIES / launch forms on the same input
+  | kernel_micro.py cva_attn B H W C r            mumpy_deform_attention_fwd, likewise.  MUMPY_AB_LIBS="name=path[@VAR=VALUE],..." names
+                                                the variants (e.g. parent=<old>/libmumpy_hip.so, new=<lib>/libmumpy_hip.so, and the tuning
+                                                build twice with @MUMPY_WA_SPLIT_UNITS=0 / =1000000 to force a form; VAR is set while that
+                                                variant's launches are issued).  Each variant's REPS launches are captured in one graph (an
+                                                eager loop of ~10 us kernels measures the launch rate, not the kernel); the graphs replay
+                                                alternately for ROUNDS rounds; prints median [min..max] us per launch and whether every
+                                                variant's output is bitwise the first one's"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "multilateral-temporal-view-pyramid-transformer-for-video-inpainting-detection_amd")]
@@ -44,6 +52,66 @@ if op == "winattn16":
     print(f"winattn16 {a}: fp32-flow {med['fp32']:.1f} us [{min(times['fp32']):.1f}..{max(times['fp32']):.1f}], "
           f"bf16-MFMA {med['bf16']:.1f} us [{min(times['bf16']):.1f}..{max(times['bf16']):.1f}] ({gb / med['bf16']:.0f} GB/s), "
           f"fp32/bf16 = {med['fp32'] / med['bf16']:.2f}  (median of {rounds} rounds x {reps} launches, alternating)")
+    sys.exit(0)
+if op in ("winattn_ab", "cva_attn"):
+    import ctypes
+    from mumpy_hip.lib import SIGNATURES
+    entry = "mumpy_window_attention_fwd" if op == "winattn_ab" else "mumpy_deform_attention_fwd"
+    variants = []                                   # (name, function, (VAR, VALUE) or None)
+    for spec in os.environ["MUMPY_AB_LIBS"].split(","):
+        name, path = spec.split("=", 1)
+        path, _, setting = path.partition("@")
+        fn = getattr(ctypes.CDLL(os.path.abspath(path)), entry)
+        fn.argtypes, fn.restype = SIGNATURES[entry], ctypes.c_int
+        variants.append((name, fn, tuple(setting.split("=", 1)) if setting else None))
+    torch.manual_seed(0)
+    if op == "winattn_ab":
+        b, hs, w, c, shift = a
+        from models.modules.swinTransformer import build_shift_mask, relative_position_index
+        qkv = torch.randn(b, hs * w, 3 * c, device=dev)
+        bias = ops.expand_relpos_bias(torch.randn(169, c // 32, device=dev) * 0.2, relative_position_index(7, 7).to(dev))
+        tab = ids = None
+        if shift:
+            tab, ids = ops.compact_attn_mask(build_shift_mask(hs, w, 7, shift).to(dev))
+        ptr = lambda t: None if t is None else t.data_ptr()
+        shape = (b, hs * w, c)
+        args = lambda out, st: (qkv.data_ptr(), out.data_ptr(), bias.data_ptr(), ptr(tab), ptr(ids), 0 if ids is None else ids.numel(),
+                                b, hs, w, c, shift, 32 ** -0.5, st)
+    else:
+        b, h, w, c, r = a
+        b1w = b * (h // 7) * (w // 7)
+        q = torch.randn(b, h * w, c, device=dev); kv = torch.randn(b1w * r, 49, 2 * c, device=dev); pad = ops.pad_mask(dev)
+        shape = (b1w, 49, c)
+        args = lambda out, st: (q.data_ptr(), kv.data_ptr(), pad.data_ptr(), out.data_ptr(), b, h, w, c, r, 32 ** -0.5, st)
+    rounds = int(os.environ.get("ROUNDS", "12"))
+    outs, graphs = {}, {}
+    for name, fn, setting in variants:
+        if setting:
+            os.environ[setting[0]] = setting[1]
+        outs[name] = torch.full(shape, float("nan"), device=dev)
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                assert fn(*args(outs[name], side.cuda_stream)) == 0
+        side.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name], stream=side):
+            for _ in range(reps):
+                assert fn(*args(outs[name], torch.cuda.current_stream().cuda_stream)) == 0
+        if setting:
+            del os.environ[setting[0]]
+        graphs[name].replay()
+    torch.cuda.synchronize()
+    times = {name: [] for name, _, _ in variants}
+    for _ in range(rounds):
+        for name, _, _ in variants:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); graphs[name].replay(); e1.record(); torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+    first = variants[0][0]
+    print(f"{op} {a}: " + ", ".join(f"{n} {sorted(t)[len(t) // 2]:.2f} us [{min(t):.2f}..{max(t):.2f}]" for n, t in times.items())
+          + f"  (median of {rounds} alternating replays of {reps} captured launches); bitwise equal to {first}: "
+          + ", ".join(f"{n} {bool(torch.equal(outs[n], outs[first]))}" for n in outs if n != first))
     sys.exit(0)
 if op in ("winattn_mm16", "winattn_bwd16"):
     b, hs, w, c, shift = a
