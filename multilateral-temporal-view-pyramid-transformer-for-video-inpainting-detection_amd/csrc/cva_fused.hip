@@ -25,7 +25,7 @@
 // operation order of deform_sample_lds_kernel) and after the product (bias, residual terms) is the fp32 code of the fp32 form.
 // Both LDS images stay [row][k]: a 32-deep chunk is 32 bf16 = 16 dwords per row, rows LDH = 20 dwords apart -- 5 16-byte slots,
 // odd, so the 16 rows a ds_read_b128 lane group touches (distinct mod 16) fall on 16 distinct slots of the 64-bank row:
-// conflict-free fragment reads (the image and the reads of xgemm16_kernel, gemm_bwd.hip).  Two MFMA steps per chunk instead of 16.
+// conflict-free fragment reads (the image and the reads of the bf16 form of xgemm_kernel, gemm_bwd.hip).  Two MFMA steps per chunk instead of 16.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs / AGPRs / SGPRs / LDS per block / waves per SIMD; scratch 0):
 //   deform_sample_kv_kernel<96 | 192 | 384 | 768, true>    132 | 134 | 130 | 130 / 0 / 44 | 44 | 47 | 47 / 40,960 B / 3
 //     (the fp32 form: 154 | 184 | 172 | 172 / 0 / 44 | 44 | 47 | 47 / 73,728 B / 2)

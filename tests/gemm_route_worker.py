@@ -38,6 +38,7 @@ first_chunk test, and it gives up after 2^24 polls, raising the workspace's stic
 other loop on memory another workgroup writes.
 """
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -310,6 +311,15 @@ def rel_err(a, b):
     return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
+def digest(tensors):
+    """sha256 of the tensors' bytes in the order given.  Informational (no check reads it): it lets the cells of two libraries be
+    compared bit for bit."""
+    h = hashlib.sha256()
+    for t in tensors:
+        h.update(t.detach().cpu().contiguous().numpy().tobytes())
+    return h.hexdigest()
+
+
 # ---------------------------------------------------------------------------------------------------------------- running cells
 class Runner:
     def __init__(self, config):
@@ -533,7 +543,7 @@ class Runner:
         err = max(rel_err(t.cpu(), refs[name] + base.get(name, 0.0)) for name, t in got.items())
         bitwise = all(bool(torch.equal(t, again[name])) for name, t in got.items())
         return {"err": err, "bar": 1e-5 if arith == "fp32" else 2e-5, "bitwise": bitwise, "guards": True, "got_route": route1,
-                "route_ok": route1 == cell["route"] and route2 == cell["route"]}
+                "route_ok": route1 == cell["route"] and route2 == cell["route"], "digest": digest(got[name] for name in sorted(got))}
 
     def run_wgrad(self, cell):
         ops, dev = self.ops, self.dev
@@ -567,7 +577,7 @@ class Runner:
             ops.set_matrix_math("fp32")
         torch.cuda.synchronize()
         return {"err": rel_err(got.cpu(), ref), "bar": 1e-5 if arith == "fp32" else 2e-5, "bitwise": bool(torch.equal(got, again)),
-                "guards": True, "got_route": route1, "route_ok": route1 == cell["route"] and route2 == cell["route"]}
+                "guards": True, "got_route": route1, "route_ok": route1 == cell["route"] and route2 == cell["route"], "digest": digest([got])}
 
     def run(self, cell):
         if cell["epi"] == "ln":

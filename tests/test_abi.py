@@ -129,3 +129,21 @@ def test_gemm_planner_matches_the_recorded_values():
     assert len(shapes) == 640 == len(gold["workspace_bytes"]) == len(gold["ln_tiles"])
     assert [int(lib.mumpy_linear_workspace_bytes(*s)) for s in shapes] == gold["workspace_bytes"]
     assert [int(lib.mumpy_linear_ln_tiles(*s)) for s in shapes] == gold["ln_tiles"]
+
+
+def test_gemm_bwd_planner_matches_the_recorded_values():
+    """mumpy_linear_bwd_workspace_bytes and mumpy_conv2d_wgrad_workspace_bytes are pure host functions of the shape (the planner and
+    the workspace layout of csrc/gemm_bwd.hip).  Their values over the sweeps of tests/golden/gemm_bwd_planner.json were recorded
+    before the launch layer of that file was refactored; a change of it must not move any of them."""
+    import json
+    from mumpy_hip.lib import load_library
+    lib = load_library()
+    with open(os.path.join(ROOT, "tests", "golden", "gemm_bwd_planner.json")) as f:
+        gold = json.load(f)
+    lin, conv = gold["linear_bwd"], gold["conv2d_wgrad"]
+    shapes = [(m, n, k) for m in lin["M"] for n in lin["N"] for k in lin["K"]]
+    assert len(shapes) == 832 == len(lin["workspace_bytes"])
+    assert [int(lib.mumpy_linear_bwd_workspace_bytes(*s)) for s in shapes] == lin["workspace_bytes"]
+    convs = [(b, h, w, ci, co, kh, kw) for b in conv["B"] for h, w in conv["HW"] for ci, co in conv["CinCout"] for kh, kw in conv["taps"]]
+    assert len(convs) == 192 == len(conv["workspace_bytes"])
+    assert [int(lib.mumpy_conv2d_wgrad_workspace_bytes(*s)) for s in convs] == conv["workspace_bytes"]

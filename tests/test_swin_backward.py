@@ -86,6 +86,28 @@ def test_hip_linear_bwd_one_call(m, n, k):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("m", [37, 4096, 4097, 9000])
+def test_hip_linear_bwd_bias_gradient_alone(m):
+    """mumpy_linear_bwd asked for db only (a convolution's bias): no dW product carries the column sums, so they run on their own --
+    one launch of the 16-group tree up to 4096 rows (4096: its last shape), above that one partial row per block of rows
+    (4097: 33 blocks of 125 rows, the last one ragged; 9000: 71 blocks) and a fixed-order reduce.  N = 96 is one full and one
+    half 64-column block.  Fresh and accumulated into an existing buffer, vs the float64 column sum; a second call is bitwise
+    equal."""
+    from mumpy_hip import ops
+    dy = seeded_randn(6, m, 96)
+    dyd, ref = dy.cuda(), dy.double().sum(0)
+    dx, dw, db = ops.linear_bwd(None, None, dyd, need_dx=False, need_dw=False, need_db=True)
+    assert dx is None and dw is None and rel_err(db.cpu(), ref) < 1e-5
+    assert torch.equal(ops.linear_bwd(None, None, dyd, need_dx=False, need_dw=False, need_db=True)[2], db)
+    gb0 = seeded_randn(7, 96).cuda()
+    gb, gb2 = gb0.clone(), gb0.clone()
+    assert ops.linear_bwd(None, None, dyd, need_dx=False, need_dw=False, need_db=True, db_out=gb) == (None, None, None)
+    assert rel_err(gb.cpu(), gb0.cpu().double() + ref) < 1e-5
+    ops.linear_bwd(None, None, dyd, need_dx=False, need_dw=False, need_db=True, db_out=gb2)
+    assert torch.equal(gb, gb2)
+
+
+@pytest.mark.gpu
 def test_hip_linear_fn_accumulates_into_grad_slots():
     """LinearFn with `.grad` pre-pointed at a buffer (FlatAdamW's layout): the backward kernels add into it and autograd gets
     None; without a slot the gradients come back as tensors -- both equal torch autograd of F.linear."""
