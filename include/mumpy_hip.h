@@ -453,6 +453,35 @@ int mumpy_rmsprop_hyper(float* out8_host, double lr, double alpha, double eps, d
 int mumpy_rmsprop_step_dev(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n,
                            const float* hyper_dev, void* stream);
 
+/* gradient-norm clipping over the flat gradient buffers (torch.nn.utils.clip_grad_norm_, L2 norm), folded into the *_step_dev
+ * updates: nothing here synchronises or allocates, pointer tables are read on the HOST at call time, so every call may be captured
+ * into a hipGraph.  The gradient buffers are only read: the clipped gradient is what the update kernel forms from grad * scale.
+ *
+ * mumpy_grad_norm_partials(n): how many partials mumpy_grad_norm_partial writes for a buffer of n floats; a pure host function of
+ * n (0 for n < 1, otherwise 1 ... 2048, non-decreasing).  The partials buffer of a group holds 2 * partials 4-byte words: the
+ * fp32 sums of squares, then the counts of non-finite elements (uint32).
+ * mumpy_grad_norm_partial: one streaming read of grad (n >= 1 floats, 16-byte aligned); every word of `partials` is written.
+ * Fixed-order sums on a grid that depends on n alone: bitwise reproducible across launches and devices.  Squares are not
+ * rescaled: a gradient whose square overflows fp32 gives an infinite norm, as torch's fp32 norm does.
+ * mumpy_grad_norm_finish: for `groups` (1 ... 8) buffers, HOST tables partials[g], n[g], hyper_dev[g] (the DEVICE constants of
+ * group g's *_step_dev, already staged) and optimizer_kind[g] (MUMPY_OPT_*: selects where that layout keeps its gradient scale).
+ * With s_g = the staged gradient scale of group g and sumsq_g its partials added in double:
+ *   stats[0] = total_norm = fp32(sqrt(sum_g s_g^2 sumsq_g))     the norm of the gradient the updates will consume
+ *   stats[1] = coef = min(1, max_norm / (total_norm + 1e-6))    in fp32, correctly rounded; NaN / 0 for a NaN / Inf norm, as torch
+ *   stats[2] = number of non-finite gradient elements, as a float (saturates at 2^24)
+ *   stats[3] = 0
+ *   stats[4 + g] = |s_g| sqrt(sumsq_g)                          the norm of group g
+ * (4 + groups floats, all written) and the gradient-scale float of every hyper_dev[g] is MULTIPLIED IN PLACE by coef: stage the
+ * constants again before the next call.  clip = 0 measures only: max_norm is ignored, coef is exactly 1 and no hyper_dev buffer is
+ * written.  clip != 0 requires max_norm > 0. */
+#define MUMPY_OPT_ADAMW   0
+#define MUMPY_OPT_SGD     1
+#define MUMPY_OPT_RMSPROP 2
+int mumpy_grad_norm_partials(int64_t n);
+int mumpy_grad_norm_partial(const float* grad, int64_t n, float* partials, void* stream);
+int mumpy_grad_norm_finish(const float* const* partials, const int64_t* n, float* const* hyper_dev, const int* optimizer_kind,
+                           int groups, int clip, double max_norm, float* stats, void* stream);
+
 /* ---- backward kernels of the Swin block (rows 5-7 of 8a in training) ---------------------------------
  * LayerNorm backward (swin:266,305): x, dy, dx (rows,C); gamma, dgamma, dbeta (C); C % 4 == 0, C <= 2048.
  * dx_add (rows,C) or null: added to dx -- the gradient arriving over the residual branch that bypasses the LayerNorm

@@ -469,3 +469,188 @@ extern "C" int mumpy_rmsprop_step_dev(float* param, const float* grad, float* sq
     if (n == 0) return 0;
     return rmsprop_launch(param, grad, square_avg, momentum_buf, n, nullptr, hyper_dev, stream);
 }
+
+// ---- gradient-norm clipping on the flat buffers (torch.nn.utils.clip_grad_norm_, L2) ----
+// Two kinds of launch, both replayable in a captured step.  The partial kernel streams one group's flat gradient once (4 B per
+// parameter) and leaves one fp32 sum of squares and one count of non-finite elements per workgroup.  The finish kernel (one
+// workgroup) adds the partials of up to 8 groups in double, reads each group's incoming gradient scale s_g from the scale slot of its
+// hyper_dev buffer, forms total = sqrt(sum_g s_g^2 sumsq_g) and coef = min(1, max_norm / (total + 1e-6)) as torch does, and
+// multiplies the scale slots by coef: the update kernels then consume the clipped gradient without a second pass over it and without
+// a host round trip.  The gradient buffers themselves are never written.
+// Every sum runs in a fixed order and the grid is a pure function of n (never of the CU count): the result is bitwise the same on
+// every launch and on every device.  Squares are not rescaled: a gradient whose square overflows fp32 gives an infinite norm, as
+// torch's fp32 norm does.
+namespace {
+
+constexpr int GN_THREADS = 256;
+constexpr int GN_UNROLL = 4;                   // independent 16-B loads (and vector accumulators) per thread and sweep
+constexpr int GN_SWEEP = GN_THREADS * GN_UNROLL * 4;      // elements one workgroup reads per sweep (16 KB)
+constexpr int GN_MAX_PARTIALS = 2048;          // 8 workgroups per CU on 256 CUs; 8 groups x 2048 partials is still one workgroup's finish
+constexpr int GN_MAX_GROUPS = 8;
+
+int grad_norm_grid(int64_t n) {
+    int64_t grid = (n + GN_SWEEP - 1) / GN_SWEEP;
+    if (grid > GN_MAX_PARTIALS) grid = GN_MAX_PARTIALS;
+    return grid < 1 ? 1 : (int)grid;
+}
+
+__device__ __forceinline__ unsigned non_finite(float v) {            // Inf or NaN: exponent all ones
+    return (__builtin_bit_cast(unsigned, v) & 0x7fffffffu) > 0x7f7fffffu ? 1u : 0u;
+}
+
+// partial[b] = sum of squares over workgroup b's share, bad[b] = its non-finite elements.  A thread's 16 scalar accumulators take one
+// term per sweep each; they are combined pairwise in a fixed order, then the wave's butterfly, then the four waves in order.
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_partial_kernel(const float* __restrict__ g, int64_t n,
+                                                                        float* __restrict__ partial, unsigned* __restrict__ bad) {
+    __shared__ float red[GN_THREADS / 64];
+    __shared__ unsigned redc[GN_THREADS / 64];
+    const f32x4* g4 = reinterpret_cast<const f32x4*>(g);
+    const int64_t n4 = n >> 2;
+    const int64_t stride = (int64_t)gridDim.x * (GN_THREADS * GN_UNROLL);
+    f32x4 acc[GN_UNROLL];
+#pragma unroll
+    for (int u = 0; u < GN_UNROLL; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+    unsigned cnt = 0;
+    for (int64_t i = (int64_t)blockIdx.x * (GN_THREADS * GN_UNROLL) + threadIdx.x; i < n4; i += stride) {
+        f32x4 v[GN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < GN_UNROLL; ++u) {                        // the loads of a sweep are issued before their use
+            const int64_t j = i + u * GN_THREADS;
+            v[u] = j < n4 ? g4[j] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < GN_UNROLL; ++u) {
+            acc[u] += v[u] * v[u];
+            cnt += non_finite(v[u][0]) + non_finite(v[u][1]) + non_finite(v[u][2]) + non_finite(v[u][3]);
+        }
+    }
+    const f32x4 q = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+    float s = (q[0] + q[1]) + (q[2] + q[3]);
+    if (blockIdx.x == 0 && (n4 << 2) + threadIdx.x < n) {            // tail (< 4 elements)
+        const float t = g[(n4 << 2) + threadIdx.x];
+        s += t * t;
+        cnt += non_finite(t);
+    }
+    s = wave_sum(s, 64);
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) cnt += __shfl_xor(cnt, o);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { red[wave] = s; redc[wave] = cnt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+        bad[blockIdx.x] = (redc[0] + redc[1]) + (redc[2] + redc[3]);
+    }
+}
+
+struct GradNormFinishArgs {
+    const float* partials[GN_MAX_GROUPS];      // per group: np sums of squares, then np counts
+    float* hyper[GN_MAX_GROUPS];
+    int np[GN_MAX_GROUPS];
+    int slot[GN_MAX_GROUPS];                   // index of the gradient-scale float in the group's hyper_dev
+    float* stats;
+    float max_norm;
+    int groups, clip;
+};
+
+__global__ __launch_bounds__(GN_THREADS) void grad_norm_finish_kernel(GradNormFinishArgs a) {
+    __shared__ double red[GN_THREADS];
+    __shared__ unsigned long long redc[GN_THREADS];
+    __shared__ float coef_s;
+    const int tid = threadIdx.x;
+    double total2 = 0.0;                       // thread 0 only
+    unsigned long long bad = 0;
+    for (int g = 0; g < a.groups; ++g) {
+        const float* ps = a.partials[g];
+        const unsigned* pc = reinterpret_cast<const unsigned*>(ps) + a.np[g];
+        constexpr int PER = GN_MAX_PARTIALS / GN_THREADS;          // a thread's partials: tid, tid + 256, ...; all loaded, then added in order
+        float v[PER];
+        unsigned k[PER];
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            const int i = tid + u * GN_THREADS;
+            v[u] = i < a.np[g] ? ps[i] : 0.f;
+            k[u] = i < a.np[g] ? pc[i] : 0u;
+        }
+        double s = 0.0;
+        unsigned long long c = 0;
+#pragma unroll
+        for (int u = 0; u < PER; ++u) { s += (double)v[u]; c += k[u]; }
+        __syncthreads();
+        red[tid] = s; redc[tid] = c;
+        __syncthreads();
+        for (int o = GN_THREADS / 2; o > 0; o >>= 1) {
+            if (tid < o) { red[tid] += red[tid + o]; redc[tid] += redc[tid + o]; }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const double sg = (double)a.hyper[g][a.slot[g]];
+            a.stats[4 + g] = (float)(fabs(sg) * sqrt(red[0]));
+            total2 += sg * sg * red[0];
+            bad += redc[0];
+        }
+    }
+    if (tid == 0) {
+        const float total = (float)sqrt(total2);
+        float coef = 1.0f;
+        if (a.clip) {                                                // clip_coef = max_norm / (total_norm + 1e-6), clamped to 1.0
+            const float c = __fdiv_rn(a.max_norm, total + 1e-6f);
+            coef = c > 1.0f ? 1.0f : c;                              // (a NaN stays a NaN, as under torch.clamp)
+        }
+        a.stats[0] = total; a.stats[1] = coef;
+        a.stats[2] = bad > 16777216ull ? 16777216.0f : (float)bad;   // saturates where fp32 stops counting exactly
+        a.stats[3] = 0.f;
+        coef_s = coef;
+    }
+    __syncthreads();
+    if (a.clip && tid < a.groups) {
+        float* h = a.hyper[tid] + a.slot[tid];
+        *h = *h * coef_s;
+    }
+}
+
+}  // namespace
+
+extern "C" int mumpy_grad_norm_partials(int64_t n) { return n < 1 ? 0 : grad_norm_grid(n); }
+
+extern "C" int mumpy_grad_norm_partial(const float* grad, int64_t n, float* partials, void* stream) {
+    MUMPY_REQUIRE(grad && partials, MUMPY_ENULL, "grad_norm_partial: null pointer");
+    MUMPY_REQUIRE(n >= 1, MUMPY_EINVAL, "grad_norm_partial: bad size n=%lld", (long long)n);
+    MUMPY_REQUIRE(aligned16(grad), MUMPY_EALIGN, "grad_norm_partial: the gradient buffer must be 16-byte aligned");
+    MUMPY_REQUIRE((reinterpret_cast<uintptr_t>(partials) & 3u) == 0, MUMPY_EALIGN, "grad_norm_partial: partials must be 4-byte aligned");
+    const int np = grad_norm_grid(n);
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)np), dim3(GN_THREADS), 0, as_stream(stream), grad, n, partials,
+                       reinterpret_cast<unsigned*>(partials) + np);
+    MUMPY_CHECK_LAUNCH("grad_norm_partial");
+    return 0;
+}
+
+extern "C" int mumpy_grad_norm_finish(const float* const* partials, const int64_t* n, float* const* hyper_dev,
+                                      const int* optimizer_kind, int groups, int clip, double max_norm, float* stats,
+                                      void* stream) {
+    MUMPY_REQUIRE(partials && n && hyper_dev && optimizer_kind && stats, MUMPY_ENULL, "grad_norm_finish: null pointer");
+    MUMPY_REQUIRE(groups >= 1, MUMPY_EINVAL, "grad_norm_finish: bad group count %d", groups);
+    MUMPY_REQUIRE(groups <= GN_MAX_GROUPS, MUMPY_ERANGE, "grad_norm_finish: %d groups (at most %d)", groups, GN_MAX_GROUPS);
+    MUMPY_REQUIRE(!clip || max_norm > 0., MUMPY_EINVAL, "grad_norm_finish: max_norm must be positive, got %g", max_norm);
+    MUMPY_REQUIRE((reinterpret_cast<uintptr_t>(stats) & 3u) == 0, MUMPY_EALIGN, "grad_norm_finish: stats must be 4-byte aligned");
+    GradNormFinishArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int g = 0; g < groups; ++g) {
+        MUMPY_REQUIRE(partials[g] && hyper_dev[g], MUMPY_ENULL, "grad_norm_finish: null pointer (group %d)", g);
+        MUMPY_REQUIRE(((reinterpret_cast<uintptr_t>(partials[g]) | reinterpret_cast<uintptr_t>(hyper_dev[g])) & 3u) == 0, MUMPY_EALIGN,
+                      "grad_norm_finish: partials and hyper_dev must be 4-byte aligned (group %d)", g);
+        MUMPY_REQUIRE(n[g] >= 1, MUMPY_EINVAL, "grad_norm_finish: bad size n=%lld (group %d)", (long long)n[g], g);
+        size_t off = 0;
+        switch (optimizer_kind[g]) {
+            case MUMPY_OPT_ADAMW: off = offsetof(AdamHyper, grad_scale); break;
+            case MUMPY_OPT_SGD: off = offsetof(SgdHyper, grad_scale); break;
+            case MUMPY_OPT_RMSPROP: off = offsetof(RmsHyper, grad_scale); break;
+            default: MUMPY_REQUIRE(false, MUMPY_EINVAL, "grad_norm_finish: unknown optimizer kind %d (group %d)", optimizer_kind[g], g);
+        }
+        a.partials[g] = partials[g]; a.hyper[g] = hyper_dev[g]; a.np[g] = grad_norm_grid(n[g]); a.slot[g] = (int)(off / sizeof(float));
+    }
+    a.stats = stats; a.max_norm = clip ? (float)max_norm : 0.f; a.groups = groups; a.clip = clip ? 1 : 0;
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_THREADS), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH("grad_norm_finish");
+    return 0;
+}

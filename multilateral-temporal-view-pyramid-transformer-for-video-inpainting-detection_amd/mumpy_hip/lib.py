@@ -110,6 +110,9 @@ SIGNATURES = {
     "mumpy_rmsprop_step": [c_f, c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_d, c_d, c_f],
     "mumpy_rmsprop_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_d, c_d],
     "mumpy_rmsprop_step_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f],
+    "mumpy_grad_norm_partials": [c_l],
+    "mumpy_grad_norm_partial": [c_f, c_l, c_f, c_f],
+    "mumpy_grad_norm_finish": [c_f, c_f, c_f, c_f, c_i, c_i, c_d, c_f, c_f],      # (the first four: HOST tables, one entry per group)
 }
 ABI_VERSION = 2
 

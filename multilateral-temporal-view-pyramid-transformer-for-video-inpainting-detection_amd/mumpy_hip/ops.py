@@ -1295,3 +1295,61 @@ def rmsprop_step_dev(param, grad, square_avg, momentum_buf, hyper_dev):
     _call("mumpy_rmsprop_step_dev", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")),
           _stream(), work=(28.0 if momentum_buf is not None else 20.0) * n)
     return param
+
+
+GRAD_NORM_MAX_GROUPS = 8
+_OPT_KINDS = {"AdamW": 0, "SGD": 1, "RMSprop": 2}        # MUMPY_OPT_* of include/mumpy_hip.h, keyed by _FlatOptimizer.KIND
+
+
+def grad_norm_partials(n):
+    """Partials that grad_norm_partial writes for a flat buffer of n floats (a pure host function of n); the partials buffer of a
+    group holds twice as many 4-byte words: the fp32 sums of squares, then the uint32 counts of non-finite elements."""
+    return int(_lib().mumpy_grad_norm_partials(int(n)))
+
+
+def grad_norm_partial(grad, partials):
+    """One streaming read of the flat gradient buffer `grad`: per-workgroup sums of squares and non-finite counts into `partials`
+    (2 * grad_norm_partials(grad.numel()) floats; the second half holds integers).  `grad` is not written.  Capturable."""
+    n = grad.numel()
+    _flat_bufs("grad_norm_partial", n, grad=grad)
+    need = 2 * grad_norm_partials(n)
+    _chk(partials, "partials")
+    if n < 1 or partials.numel() != need or not partials.is_contiguous():
+        raise RuntimeError(f"grad_norm_partial: partials must be a contiguous buffer of {need} floats for a gradient of {n}")
+    _call("mumpy_grad_norm_partial", _p(grad), n, _p(partials), _stream(), work=4.0 * n)
+    return partials
+
+
+def grad_norm_finish(partials, sizes, hypers, kinds, stats, max_norm=None):
+    """Finish of up to 8 groups: `partials[g]` from grad_norm_partial over a buffer of `sizes[g]` floats, `hypers[g]` the staged
+    device constants of that group's *_step_dev, `kinds[g]` its _FlatOptimizer.KIND.  Writes stats = [total_norm, coef, non-finite
+    count, 0, norm_0 ... norm_{G-1}] (4 + G floats) and, when max_norm is given, multiplies every group's staged gradient scale by
+    coef = min(1, max_norm / (total_norm + 1e-6)) in place.  max_norm None: measure only (coef = 1, `hypers` untouched).
+    Capturable: the tables are packed into the launch on the host."""
+    import ctypes
+    groups = len(partials)
+    if not (len(sizes) == len(hypers) == len(kinds) == groups):
+        raise RuntimeError("grad_norm_finish: one partials buffer, size, hyper buffer and optimizer kind per group")
+    if groups > GRAD_NORM_MAX_GROUPS:
+        raise ValueError(f"grad_norm_finish: {groups} groups (at most {GRAD_NORM_MAX_GROUPS})")
+    for g, (p, n, h, k) in enumerate(zip(partials, sizes, hypers, kinds)):
+        if k not in _OPT_KINDS:
+            raise ValueError(f"grad_norm_finish: unknown optimizer kind {k!r} (group {g})")
+        _chk(p, "partials")
+        _chk(h, "hyper")
+        if not p.is_contiguous() or p.numel() != 2 * grad_norm_partials(n):
+            raise RuntimeError(f"grad_norm_finish: partials of group {g} must hold {2 * grad_norm_partials(n)} floats")
+        if not h.is_contiguous() or h.numel() < (4 if k == "SGD" else 8):
+            raise RuntimeError(f"grad_norm_finish: hyper buffer of group {g} is too small for {k}")
+    _chk(stats, "stats")
+    if not stats.is_contiguous() or stats.numel() != 4 + groups:
+        raise RuntimeError(f"grad_norm_finish: stats must be a contiguous buffer of {4 + groups} floats")
+    if max_norm is not None and not float(max_norm) > 0.0:
+        raise ValueError(f"grad_norm_finish: max_norm must be positive, got {max_norm}")
+    ptrs = (ctypes.c_void_p * groups)(*[_p(p) for p in partials])
+    hyps = (ctypes.c_void_p * groups)(*[_p(h) for h in hypers])
+    ns = (ctypes.c_int64 * groups)(*[int(n) for n in sizes])
+    ks = (ctypes.c_int * groups)(*[_OPT_KINDS[k] for k in kinds])
+    _call("mumpy_grad_norm_finish", ptrs, ns, hyps, ks, groups, int(max_norm is not None), float(max_norm or 0.0), _p(stats),
+          _stream(), work=8.0 * sum(grad_norm_partials(n) for n in sizes))
+    return stats

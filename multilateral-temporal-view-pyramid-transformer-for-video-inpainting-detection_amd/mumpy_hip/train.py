@@ -13,7 +13,9 @@ Reference behaviour reproduced:
   * gradient accumulation: loss / accumulation_steps (train.py:115), update every accumulation_steps iterations (eager,
     or replayed: GraphedTrainStep(accumulation_steps=k));
   * nn.DataParallel's gradient (grad of the mean loss over the global batch) == the mean over ranks of per-rank gradients
-    for equal shards: one sum all-reduce of the flat gradient buffer in buckets + the 1/world factor folded into the update.
+    for equal shards: one sum all-reduce of the flat gradient buffer in buckets + the 1/world factor folded into the update;
+  * timm's `clip_grad=` knob of the optimizer recipes (train.py:223-273, None there): `GradClip`, torch's clip_grad_norm_ measured on
+    the flat gradient buffers and folded into the update's gradient scale on the device (eager, or GraphedTrainStep(clip_grad=...)).
 """
 from typing import Dict, Iterable, List, Optional
 
@@ -342,6 +344,81 @@ def build_optimizers(encoder, decoder, lr_cnn: float, lr: float, lr_cva: Optiona
     return opts
 
 
+class GradClip:
+    """Gradient-norm clipping (torch.nn.utils.clip_grad_norm_, L2) over the flat gradient buffers of up to 8 optimizers, folded into
+    their device-side updates.  `measure()` reads each gradient buffer once (one launch per optimizer) and one finish launch forms
+        total_norm = sqrt(sum_g s_g^2 |grad_g|^2),   coef = min(1, max_norm / (total_norm + 1e-6))
+    where s_g is the gradient scale `stage_hyper` staged for optimizer g (the 1/world factor of the all-reduce, a loss-scale
+    correction), and multiplies every staged scale by coef.  The `.grad` buffers are NOT rewritten: they keep the unclipped sum and
+    are zeroed by the update as before; the clipped gradient is what `step_dev` forms from grad * scale.  No host synchronisation,
+    no allocation per call: capturable into a hipGraph (GraphedTrainStep(clip_grad=...)).
+
+    One GradClip over several optimizers clips by one global norm, like clip_grad_norm_ over all their parameters; one GradClip
+    per optimizer is timm's per-optimizer `clip_grad` (the knob of the reference's recipes, train.py:223-273).
+    max_norm=None only measures: coef is exactly 1 and the staged constants are left alone.
+    `stats` (device, 4 + G floats) = [total_norm, coef, non-finite element count, 0, norm_0 ... norm_{G-1}].
+    Not covered: skipping an update whose gradient is non-finite (coef is then NaN or 0 exactly as torch's is, and the update runs),
+    clip_grad_value_, adaptive clipping, norms other than L2."""
+    MAX_GROUPS = ops.GRAD_NORM_MAX_GROUPS
+
+    @staticmethod
+    def _validate(opts, max_norm):
+        if not opts:
+            raise ValueError("GradClip: no optimizers")
+        if len(opts) > GradClip.MAX_GROUPS:
+            raise ValueError(f"GradClip: {len(opts)} optimizers (at most {GradClip.MAX_GROUPS} share one norm)")
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise ValueError(f"GradClip: max_norm must be positive (or None to measure only), got {max_norm}")
+        for o in opts:
+            if getattr(o, "KIND", None) not in ops._OPT_KINDS:
+                raise ValueError(f"GradClip: {type(o).__name__} is not a flat optimizer of this package")
+
+    def __init__(self, optimizers, max_norm: Optional[float] = None):
+        self.opts = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
+        self._validate(self.opts, max_norm)
+        self.max_norm = None if max_norm is None else float(max_norm)
+        for o in self.opts:
+            if not hasattr(o, "hyper_dev"):
+                o.enable_device_hyper()
+        dev = self.opts[0].grad.device
+        self.sizes = [o.grad.numel() for o in self.opts]
+        counts = [2 * ops.grad_norm_partials(n) for n in self.sizes]
+        self._ws = torch.zeros(sum(counts), device=dev, dtype=torch.float32)
+        self.partials = list(self._ws.split(counts))
+        self.stats = torch.zeros(4 + len(self.opts), device=dev, dtype=torch.float32)
+
+    def measure(self):
+        """Enqueue the G partial launches and the finish on the current stream.  Must follow the optimizers' `stage_hyper` in stream
+        order (it reads, and with a max_norm rescales, the staged gradient scales) and precede their `step_dev`."""
+        for o, part in zip(self.opts, self.partials):
+            ops.grad_norm_partial(o.grad, part)
+        ops.grad_norm_finish(self.partials, self.sizes, [o.hyper_dev for o in self.opts], [o.KIND for o in self.opts], self.stats,
+                             self.max_norm)
+        return self.stats
+
+    def step(self, scales=None):
+        """The eager update with clipping, in place of `for o in opts: o.step(grad_scale=scale)`: stage every optimizer's constants
+        (scales: None = 1.0, one float for all, or one per optimizer -- e.g. what all_reduce_grads returned), measure, update.
+        Gradients are not reset (call zero_grad as after step()).  Synchronises nowhere; `read()` does."""
+        if scales is None or isinstance(scales, (int, float)):
+            scales = [1.0 if scales is None else float(scales)] * len(self.opts)
+        scales = list(scales)
+        if len(scales) != len(self.opts):
+            raise ValueError(f"GradClip.step: {len(scales)} scales for {len(self.opts)} optimizers")
+        for o, sc in zip(self.opts, scales):
+            o.stage_hyper(sc)
+        self.measure()
+        for o in self.opts:
+            o.step_dev()
+        bump_weights_epoch()
+        return self.stats
+
+    def read(self) -> dict:
+        """The statistics of the last measure() on the host.  This is the one call here that synchronises (a device-to-host copy)."""
+        s = self.stats.cpu().tolist()
+        return {"total_norm": s[0], "coef": s[1], "nonfinite": int(s[2]), "norms": s[4:]}
+
+
 class GraphedTrainStep:
     """One training step (taped forward, mask loss, backward, the update of every group, gradient reset) captured into a hipGraph
     and replayed: at config 5's micro-batch the eager step is bound by ~10^4 host-side launches, not by the GPU.
@@ -349,10 +426,15 @@ class GraphedTrainStep:
     Train mode works: the stochastic-depth masks are drawn by torch's graph-safe Philox generator inside the capture, so every
     replay draws new ones (test_hip_graphed_train_step_draws_fresh_drop_path_masks).  Learning-rate schedules keep working: the
     optimizers' constants are staged into device memory before each update.  Call `step(x, target)` -> loss3 (device tensor
-    [total, iou, focal])."""
+    [total, iou, focal]).
+    clip_grad: gradient-norm clipping inside the replayed update (GradClip).  A float clips all the optimizers by one global norm;
+    a dict keyed like the `optimizers` dict clips each named optimizer by its own norm (a missing key leaves that optimizer
+    unclipped).  The norm is measured at the head of the update -- after the all-reduce, with the 1/world factor staged, once per
+    update under accumulation -- and `.grad_stats` is the device statistics tensor (a dict of them for the dict form; GradClip.stats
+    gives the layout).  The `.grad` buffers keep the unclipped sum until the update zeroes them.  None: nothing is launched."""
 
     def __init__(self, forward_fn, optimizers, x, target, warmup: int = 3, loss_scale: float = 1.0, all_reduce: bool = False,
-                 accumulation_steps: int = 1):
+                 accumulation_steps: int = 1, clip_grad=None):
         """all_reduce=True (data-parallel ranks): TWO graphs -- forward + loss + backward, and update + gradient reset -- with
         the bucketed gradient all-reduce (RCCL) issued eagerly between their replays.
         accumulation_steps=k > 1 (train.py:115-120): every step() is one micro-batch whose loss gradient is scaled by
@@ -361,6 +443,20 @@ class GraphedTrainStep:
         if accumulation_steps < 1:
             raise ValueError(f"GraphedTrainStep: accumulation_steps must be >= 1, got {accumulation_steps}")
         self.opts = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
+        clip_plan = []                    # [(key or None, optimizers, max_norm)], checked before anything touches the GPU
+        if isinstance(clip_grad, dict):
+            if not isinstance(optimizers, dict):
+                raise ValueError("GraphedTrainStep: a clip_grad dict needs the optimizers as a dict with the same keys")
+            for key, c in clip_grad.items():
+                if key not in optimizers:
+                    raise ValueError(f"GraphedTrainStep: clip_grad names {key!r}, which is not one of the optimizers {sorted(optimizers)}")
+                clip_plan.append((key, [optimizers[key]], c))
+        elif clip_grad is not None:
+            clip_plan.append((None, self.opts, clip_grad))
+        for _, group, c in clip_plan:
+            if c is None or isinstance(c, bool) or not isinstance(c, (int, float)):
+                raise ValueError(f"GraphedTrainStep: clip_grad must be a positive number, got {c!r}")
+            GradClip._validate(group, c)
         self.x, self.target = x.clone(), target.clone()
         self.all_reduce = all_reduce
         self.accumulation_steps = k = int(accumulation_steps)
@@ -368,6 +464,12 @@ class GraphedTrainStep:
         self._updated = False
         for o in self.opts:
             o.enable_device_hyper()
+        self.clips = [GradClip(group, c) for _, group, c in clip_plan]
+        self.grad_stats = None
+        if isinstance(clip_grad, dict):
+            self.grad_stats = {key: clip.stats for (key, _, _), clip in zip(clip_plan, self.clips)}
+        elif self.clips:
+            self.grad_stats = self.clips[0].stats
 
         def fwd_bwd():
             logits = forward_fn(self.x)
@@ -376,6 +478,8 @@ class GraphedTrainStep:
             return loss3
 
         def update():
+            for clip in self.clips:               # reads the staged gradient scales and folds the clip coefficient into them
+                clip.measure()
             for o in self.opts:
                 o.step_dev()
                 o.zero_grad()

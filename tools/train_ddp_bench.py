@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the step from hipGraphs (forward+backward | update), all-reduce eager between them")
     ap.add_argument("--optim", choices=["adam", "sgd", "rmsprop"], default="adam", help="the reference's -optim / -optim_cnn (utils/utils.py:252-261)")
     ap.add_argument("--accumulation-steps", type=int, default=1, help="micro-batches per update (train.py:115-120); --steps counts micro-batches")
+    ap.add_argument("--clip-grad", type=float, default=None, help="clip all groups by one global L2 norm (GradClip; after the all-reduce, on the averaged gradient)")
     args = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     backend = os.environ.get("MUMPY_BENCH_BACKEND", "nccl")
@@ -42,7 +43,7 @@ def main():
     from models.decoder.decoder import Decoder
     from models.encoder.encoder import Encoder
     from mumpy_hip.autograd import decoder_train, encoder_train
-    from mumpy_hip.train import build_optimizers
+    from mumpy_hip.train import GradClip, build_optimizers
     from weight_fill import fill_module_, seeded_randn
     ops.set_matrix_math(args.math)
     enc = fill_module_(Encoder(num_frames=args.frames)).eval().to(dev)          # same weights on every rank (deterministic fill)
@@ -52,6 +53,7 @@ def main():
     opts = build_optimizers(enc, dec, lr_cnn=1e-6, lr=1e-5, lr_cva=1e-6, weight_decay=1e-4, weight_decay_cnn=1e-4,
                             optim=args.optim, optim_cnn=args.optim)
     k = args.accumulation_steps
+    clip = GradClip(opts, args.clip_grad) if args.clip_grad is not None and not args.graph else None
     micro = [0]                                                                   # micro-batches run (the reference's `iteration`)
     x = seeded_randn(100 + rank, args.batch, args.frames, 3, 224, 224).to(dev)
     target = (torch.rand(args.batch, 1, 224, 224, generator=torch.Generator().manual_seed(7 + rank)) < 0.1).float().to(dev)
@@ -63,16 +65,20 @@ def main():
         logits.backward(dlogits)
         micro[0] += 1
         if micro[0] % k == 0:
+            if clip is not None:
+                clip.step([o.all_reduce_grads(bucket_bytes=args.bucket_mb << 20) for o in opts.values()])
             for o in opts.values():
-                scale = o.all_reduce_grads(bucket_bytes=args.bucket_mb << 20)   # the step's collectives
-                o.step(grad_scale=scale)
+                if clip is None:
+                    scale = o.all_reduce_grads(bucket_bytes=args.bucket_mb << 20)   # the step's collectives
+                    o.step(grad_scale=scale)
                 o.zero_grad()
         return loss3
 
     if args.graph:
         from mumpy_hip.train import GraphedTrainStep
         gs = GraphedTrainStep(lambda xx: decoder_train(dec, *encoder_train(enc, xx))[0], opts, x, target, warmup=max(args.warmup, 2),
-                              all_reduce=world > 1 or os.environ.get("MUMPY_FORCE_DIST", "0") == "1", accumulation_steps=k)
+                              all_reduce=world > 1 or os.environ.get("MUMPY_FORCE_DIST", "0") == "1", accumulation_steps=k,
+                              clip_grad=args.clip_grad)
 
         def step():
             micro[0] += 1
@@ -103,12 +109,14 @@ def main():
         lo, hi = chk.clone(), chk.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN); dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         same = bool(torch.equal(lo, hi))
+    gstat = (gs.grad_stats if args.graph else clip.stats).tolist() if args.clip_grad is not None else None
     if rank == 0:
         print(json.dumps({"metric": "train clips/s (fwd + loss + bwd + grad all-reduce + update)", "value": round(args.batch * world * args.steps / dt, 3),
                           "unit": "clips/s", "n_gpus": world, "ms_per_step": round(1e3 * dt / args.steps, 2), "ms_per_update": round(1e3 * dt * k / args.steps, 2),
                           "optim": args.optim, "accumulation_steps": k, "graph": bool(args.graph), "micro_batch": args.batch,
                           "frames": args.frames, "math": args.math, "train_mode": bool(args.train_mode), "backend": backend, "loss": [round(float(v), 5) for v in loss3],
-                          "replicas_identical_after_steps": same}))
+                          "replicas_identical_after_steps": same,
+                          **({"clip_grad": args.clip_grad, "total_norm": gstat[0], "coef": gstat[1]} if gstat else {})}))
     if dist.is_initialized():
         dist.destroy_process_group()
 
