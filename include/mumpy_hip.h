@@ -189,7 +189,7 @@ int mumpy_linear_bf16s_fwd(const void* x, const void* W, const float* bias, cons
 /* Same, with the rows of x grouped in blocks: row m lives at x + (m / rows_per_block) * block_stride +
  * (m % rows_per_block) * K (floats).  Feeds one time slice of the (B, T*n, C) view-3 tokens to the decoder's
  * Conv3d(k=(T,1,1)) heads (decoder.py:98-120) as a (B*n, C) operand without the merge/permute copy of decoder.py:43-53;
- * the T slices are chained through `residual`. */
+ * the T slices are chained through `residual`.  block_stride >= 0, block_stride % 4 == 0, M % rows_per_block == 0. */
 int mumpy_linear_rows_fwd(const float* x, int64_t rows_per_block, int64_t block_stride, const float* W,
                           const float* bias, const float* residual, float* y, int64_t M, int N, int K, int act,
                           void* workspace, int64_t workspace_bytes, void* stream);
@@ -334,7 +334,7 @@ int mumpy_temporal_attention_q_fwd(const float* qkv, float* out, int64_t S, int 
 
 /* Attention MAPS for the `return_attention=True` variants (blocks:85-87; deform:364-396; mTVE:134-137) -- a visualisation path:
  * out (outer, heads, nq, nk) = softmax(scale * q k^T) per (outer, head); q row i of unit (o, h) at q + (o % q_mod) * q_outer_stride +
- * i * q_row_stride + h * d, k row j at k + o * k_outer_stride + j * k_row_stride + h * d (strides in floats); nq, nk, d <= 64. */
+ * i * q_row_stride + h * d, k row j at k + o * k_outer_stride + j * k_row_stride + h * d (strides in floats, >= 0); nq, nk, d <= 64. */
 int mumpy_attention_probs_fwd(const float* q, const float* k, float* out, int64_t outer, int heads, int nq, int nk, int d,
                               int64_t q_outer_stride, int64_t q_row_stride, int64_t k_outer_stride, int64_t k_row_stride,
                               int64_t q_mod, float scale, void* stream);
@@ -352,7 +352,7 @@ int mumpy_gn_stats_nhwc_fwd(const float* x, float* partial, int B, int64_t HW, i
  *   nn.Upsample (True: decoder.py:72-93; False: decoder.py:10,136-137);
  *   ep_mode 0: none, 1: + ep_a*ep_b (decoder.py:219-220), 2: * ep_a (decoder.py:221, 14), operands dense
  *   (B,Ho,Wo,Cout);  out: (B,Ho,Wo,out_ctot) written at channel offset out_coff (lets a torch.cat operand be
- *   produced in place, decoder.py:210,213).  C <= 256. */
+ *   produced in place, decoder.py:210,213): 0 <= out_coff, out_coff + Cout <= out_ctot, both % 4 == 0.  C <= 256. */
 int mumpy_gn_apply_resample_nhwc_fwd(const float* x, const float* partial, int nsplit, const float* gamma,
                                      const float* beta, int G, float eps, int act, int mean4, int scale,
                                      int align_corners, int ep_mode, const float* ep_a, const float* ep_b,

@@ -547,8 +547,8 @@ extern "C" int mumpy_gn_bwd_nhwc(const float* z, const float* stats_partial, int
     MUMPY_REQUIRE(aligned16(z) && aligned16(dy) && aligned16(dz) && aligned16(gamma) && aligned16(beta) && aligned16(workspace),
                   MUMPY_EALIGN, "gn_bwd: pointers must be 16-byte aligned");
     MUMPY_REQUIRE(B > 0 && B <= 65535 && HW > 0 && nsplit_stats > 0, MUMPY_EINVAL, "gn_bwd: bad sizes");
-    MUMPY_REQUIRE(C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && G > 0 && G <= 32 && C % G == 0 && (C / G) % 4 == 0, MUMPY_EINVAL,
-                  "gn_bwd: unsupported C=%d G=%d", C, G);
+    MUMPY_REQUIRE(C >= 4 && C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && G > 0 && G <= 32 && C % G == 0 && (C / G) % 4 == 0,
+                  MUMPY_EINVAL, "gn_bwd: unsupported C=%d G=%d", C, G);
     MUMPY_REQUIRE(workspace_bytes >= mumpy_gn_bwd_workspace_bytes(B, HW, C), MUMPY_EINVAL, "gn_bwd: workspace too small");
     const int accumulate = (relu & MUMPY_GN_ACCUMULATE) ? 1 : 0;
     relu &= ~MUMPY_GN_ACCUMULATE;

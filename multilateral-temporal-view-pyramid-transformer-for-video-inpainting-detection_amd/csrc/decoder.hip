@@ -559,7 +559,7 @@ extern "C" int mumpy_gn_stats_nhwc_fwd(const float* x, float* partial, int B, in
     MUMPY_REQUIRE(x && partial, MUMPY_ENULL, "gn_stats: null pointer");
     MUMPY_REQUIRE(aligned16(x), MUMPY_EALIGN, "gn_stats: x must be 16-byte aligned");
     MUMPY_REQUIRE(B > 0 && HW > 0 && nsplit > 0 && nsplit <= 1024, MUMPY_EINVAL, "gn_stats: bad sizes");
-    MUMPY_REQUIRE(C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && G > 0 && G <= 32 && C % G == 0 && (C / G) % 4 == 0,
+    MUMPY_REQUIRE(C >= 4 && C % 4 == 0 && C <= 1024 && 256 % (C / 4) == 0 && G > 0 && G <= 32 && C % G == 0 && (C / G) % 4 == 0,
                   MUMPY_EINVAL, "gn_stats: unsupported C=%d G=%d", C, G);
     hipLaunchKernelGGL(gn_stats_kernel, dim3(nsplit, B), dim3(256), 0, as_stream(stream), x, partial, HW, C, G, nsplit);
     MUMPY_CHECK_LAUNCH("gn_stats");
@@ -584,7 +584,7 @@ extern "C" int mumpy_gn_apply_resample_nhwc_fwd(const float* x, const float* par
     MUMPY_REQUIRE(ep_mode == 0 || ep_a, MUMPY_ENULL, "gn_apply: epilogue operand missing");
     MUMPY_REQUIRE(ep_mode != 1 || ep_b, MUMPY_ENULL, "gn_apply: epilogue operand b missing");
     const int Cout = mean4 ? C / 4 : C;
-    MUMPY_REQUIRE(out_ctot >= out_coff + Cout && out_ctot % 4 == 0 && out_coff % 4 == 0, MUMPY_EINVAL,
+    MUMPY_REQUIRE(out_coff >= 0 && out_ctot >= out_coff + Cout && out_ctot % 4 == 0 && out_coff % 4 == 0, MUMPY_EINVAL,
                   "gn_apply: output channel slice [%d,+%d) does not fit %d", out_coff, Cout, out_ctot);
     ApplyArgs a;
     a.x = x; a.partial = partial; a.gamma = gamma; a.beta = beta; a.ep_a = ep_a; a.ep_b = ep_b; a.out = out;

@@ -322,7 +322,7 @@ extern "C" int mumpy_deform_combine_fwd(const float* x1, const float* Yt, float*
                                         void* stream) {
     MUMPY_REQUIRE(x1 && Yt && out, MUMPY_ENULL, "deform_combine: null pointer");
     MUMPY_REQUIRE(x1 != out, MUMPY_EINVAL, "deform_combine: out must not alias x1");
-    MUMPY_REQUIRE(B > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && C % 32 == 0, MUMPY_EINVAL,
+    MUMPY_REQUIRE(B > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && C > 0 && C % 32 == 0, MUMPY_EINVAL,
                   "deform_combine: bad shape (%d,%d,%d)", H, W, C);
     const int nWx = W / WS, nWf = (H / WS) * nWx;
     hipLaunchKernelGGL(deform_combine_kernel, dim3(B * nWf, C / 32), dim3(256), 0, as_stream(stream), x1, Yt, out, H, W,

@@ -973,6 +973,7 @@ extern "C" int mumpy_linear_ws_fwd(const float* x, const float* W, const float* 
                                    void* stream) {
     if (M == 0) return 0;
     if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
+    MUMPY_REQUIRE(workspace_bytes >= 0, MUMPY_EINVAL, "linear_ws: workspace_bytes must not be negative");
     MUMPY_REQUIRE(aligned16(workspace), MUMPY_EALIGN, "linear: workspace must be 16-byte aligned");
     return launch_linear(linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream));
 }
@@ -1025,6 +1026,7 @@ extern "C" int mumpy_linear_wsz_fwd(const float* x, const float* W, const float*
                                     void* stream) {
     if (M == 0) return 0;
     if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
+    MUMPY_REQUIRE(workspace_bytes >= 0, MUMPY_EINVAL, "linear_wsz: workspace_bytes must not be negative");
     MUMPY_REQUIRE(aligned16(workspace), MUMPY_EALIGN, "linear: workspace must be 16-byte aligned");
     LinearArgs a = linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream);
     a.ws_clean = true;
@@ -1059,6 +1061,9 @@ extern "C" int mumpy_linear_lnx_fwd(const float* x, const float* W, const float*
     if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
     MUMPY_REQUIRE((act & ~0xff) == 0, MUMPY_EINVAL, "linear_lnx: fp32 matrix math only");
     MUMPY_REQUIRE(aligned16(workspace) && workspace, MUMPY_EALIGN, "linear_lnx: needs the kept (zeroed) workspace of mumpy_linear_wsz_fwd");
+    MUMPY_REQUIRE(ln_gn >= 0, MUMPY_EINVAL, "linear_lnx: ln_gn must not be negative");
+    MUMPY_REQUIRE(workspace_bytes >= 4096, MUMPY_EINVAL, "linear_lnx: the kept workspace holds at least its 4096-byte flag page (got %lld B)",
+                  (long long)workspace_bytes);
     MUMPY_REQUIRE((stats_out != nullptr) != (ln_stats != nullptr), MUMPY_EINVAL, "linear_lnx: exactly one of stats_out (producer) / ln_stats (consumer)");
     MUMPY_REQUIRE(!ln_stats || (ln_colsum && bias && !residual && ln_gn == (K + 127) / 128 && ln_gn <= 16 && ln_eps > 0.f), MUMPY_EINVAL,
                   "linear_lnx: the consumer takes W gamma, colsum, bias = W beta + b, no residual, and ln_gn = ceil(K / 128) tiles (got %d)", ln_gn);
@@ -1077,8 +1082,9 @@ extern "C" int mumpy_linear_rows_fwd(const float* x, int64_t rows_per_block, int
                                      void* workspace, int64_t workspace_bytes, void* stream) {
     if (M == 0) return 0;
     if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
-    MUMPY_REQUIRE(rows_per_block > 0 && M % rows_per_block == 0 && block_stride % 4 == 0, MUMPY_EINVAL,
-                  "linear_rows: M=%lld must be a multiple of rows_per_block=%lld and block_stride %% 4 == 0",
+    MUMPY_REQUIRE(workspace_bytes >= 0, MUMPY_EINVAL, "linear_rows: workspace_bytes must not be negative");
+    MUMPY_REQUIRE(rows_per_block > 0 && M % rows_per_block == 0 && block_stride >= 0 && block_stride % 4 == 0, MUMPY_EINVAL,
+                  "linear_rows: M=%lld must be a multiple of rows_per_block=%lld and block_stride >= 0, %% 4 == 0",
                   (long long)M, (long long)rows_per_block);
     LinearArgs a = linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream);
     a.rpb = rows_per_block; a.bstride = block_stride;
@@ -1094,8 +1100,9 @@ extern "C" int mumpy_linear_rows_kseg_fwd(const float* x, int64_t rows_per_block
                                           int act, void* workspace, int64_t workspace_bytes, void* stream) {
     if (M == 0) return 0;
     if (int rc = check_linear_args("linear", x, W, residual, y, M, N, K, act)) return rc;
-    MUMPY_REQUIRE(rows_per_block > 0 && M % rows_per_block == 0 && block_stride % 4 == 0, MUMPY_EINVAL,
-                  "linear_rows_kseg: M=%lld must be a multiple of rows_per_block=%lld and block_stride %% 4 == 0",
+    MUMPY_REQUIRE(workspace_bytes >= 0, MUMPY_EINVAL, "linear_rows_kseg: workspace_bytes must not be negative");
+    MUMPY_REQUIRE(rows_per_block > 0 && M % rows_per_block == 0 && block_stride >= 0 && block_stride % 4 == 0, MUMPY_EINVAL,
+                  "linear_rows_kseg: M=%lld must be a multiple of rows_per_block=%lld and block_stride >= 0, %% 4 == 0",
                   (long long)M, (long long)rows_per_block);
     MUMPY_REQUIRE(kseg > 0 && kseg % 32 == 0 && K % kseg == 0 && kstride % 4 == 0 && kstride >= 0, MUMPY_EINVAL,
                   "linear_rows_kseg: need kseg %% 32 == 0, K %% kseg == 0, kstride %% 4 == 0 (got kseg=%d K=%d kstride=%d)", kseg, K, kstride);
@@ -1118,6 +1125,7 @@ extern "C" int mumpy_conv2d_nhwc_fwd(const float* x, const float* w_krsc, const 
     const int64_t M = (int64_t)B * H * W;
     const int K = kh * kw * Cin;
     if (int rc = check_linear_args("linear", x, w_krsc, residual, y, M, Cout, K, act)) return rc;
+    MUMPY_REQUIRE(workspace_bytes >= 0, MUMPY_EINVAL, "conv2d: workspace_bytes must not be negative");
     MUMPY_REQUIRE(aligned16(workspace), MUMPY_EALIGN, "conv2d: workspace must be 16-byte aligned");
     const ConvGeom cg{H, W, Cin, kh, kw, kh / 2, kw / 2, 0, 0};
     LinearArgs a = linear_args(x, w_krsc, bias, residual, y, M, Cout, K, act, workspace, workspace_bytes, stream);

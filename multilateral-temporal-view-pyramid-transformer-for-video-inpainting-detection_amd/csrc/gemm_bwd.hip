@@ -566,7 +566,9 @@ extern "C" int mumpy_conv2d_wgrad_nhwc(const float* x, const float* dy, float* d
                   "conv2d_wgrad: pointers must be 16-byte aligned");
     MUMPY_REQUIRE(B > 0 && H > 0 && W >= 2 && (int64_t)B * H * W < (1ll << 31) - 256, MUMPY_EINVAL, "conv2d_wgrad: bad image batch %dx%dx%d", B, H, W);
     MUMPY_REQUIRE(kh > 0 && kw > 0 && (kh & 1) && (kw & 1), MUMPY_EINVAL, "conv2d_wgrad: kernel %dx%d must be odd (same padding)", kh, kw);
-    MUMPY_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0, MUMPY_EINVAL, "conv2d_wgrad: Cin=%d and Cout=%d must be multiples of 32", Cin, Cout);
+    MUMPY_REQUIRE(Cin > 0 && Cout > 0 && Cin % 32 == 0 && Cout % 32 == 0, MUMPY_EINVAL,
+                  "conv2d_wgrad: Cin=%d and Cout=%d must be positive multiples of 32", Cin, Cout);
+    MUMPY_REQUIRE(workspace_bytes >= 0, MUMPY_EINVAL, "conv2d_wgrad: workspace_bytes must not be negative");
     MUMPY_REQUIRE((accumulate & ~(1 | MUMPY_MATH_BF16)) == 0, MUMPY_EINVAL, "conv2d_wgrad: accumulate is 0 / 1, optionally | MUMPY_MATH_BF16");
     const bool bf16 = (accumulate & MUMPY_MATH_BF16) != 0;
     accumulate &= 1;

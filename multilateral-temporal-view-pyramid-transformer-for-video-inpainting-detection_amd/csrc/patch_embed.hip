@@ -132,7 +132,7 @@ extern "C" int mumpy_patch_embed_fwd(const float* x, const float* Wt, const floa
     MUMPY_REQUIRE(x && Wt && bias && gamma && beta && out, MUMPY_ENULL, "patch_embed: null pointer");
     MUMPY_REQUIRE(aligned16(x) && aligned16(out) && aligned16(gamma) && aligned16(beta), MUMPY_EALIGN,
                   "patch_embed: x, out, gamma and beta must be 16-byte aligned");
-    MUMPY_REQUIRE(B > 0 && T > 0 && t > 0 && t <= T && H % 4 == 0 && W % 4 == 0, MUMPY_EINVAL,
+    MUMPY_REQUIRE(B > 0 && T > 0 && t > 0 && t <= T && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0, MUMPY_EINVAL,
                   "patch_embed: bad clip shape T=%d t=%d H=%d W=%d", T, t, H, W);
     MUMPY_REQUIRE(C % 32 == 0 && C >= 32 && C <= 128, MUMPY_ERANGE, "patch_embed: C=%d must be 32..128, multiple of 32", C);
     const int K = 48 * t;

@@ -207,6 +207,8 @@ extern "C" int mumpy_attention_probs_fwd(const float* q, const float* k, float* 
     MUMPY_REQUIRE(q && k && out, MUMPY_ENULL, "attention_probs: null pointer");
     MUMPY_REQUIRE(outer >= 0 && heads > 0 && nq >= 1 && nq <= 64 && nk >= 1 && nk <= 64 && d >= 1 && d <= 64 && q_mod >= 1, MUMPY_EINVAL,
                   "attention_probs: need 1 <= nq, nk, d <= 64 (got %d, %d, %d)", nq, nk, d);
+    MUMPY_REQUIRE(q_outer_stride >= 0 && q_row_stride >= 0 && k_outer_stride >= 0 && k_row_stride >= 0, MUMPY_EINVAL,
+                  "attention_probs: strides must not be negative");
     if (outer == 0) return 0;
     ProbsArgs a{q, k, out, outer * heads, heads, nq, nk, d, q_outer_stride, q_row_stride, k_outer_stride, k_row_stride, q_mod, scale};
     const int64_t grid = (a.units + 3) / 4;

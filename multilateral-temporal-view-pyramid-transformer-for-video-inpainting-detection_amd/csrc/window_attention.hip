@@ -490,7 +490,7 @@ static int window_attention_launch(SelfKind kind, const float* qkv, float* out, 
                   "window_attention: grid (%d,%d) not divisible by window 7", Hs, W);
     MUMPY_REQUIRE(C > 0 && C % HD == 0, MUMPY_EINVAL, "window_attention: C=%d not a multiple of head width 32", C);
     MUMPY_REQUIRE(shift >= 0 && shift < WS, MUMPY_EINVAL, "window_attention: shift=%d out of [0,7)", shift);
-    MUMPY_REQUIRE(mask_id == nullptr || n_mask > 0, MUMPY_EINVAL, "window_attention: n_mask must be > 0 with a mask");
+    MUMPY_REQUIRE(n_mask >= 0 && (mask_id == nullptr || n_mask > 0), MUMPY_EINVAL, "window_attention: n_mask must be > 0 with a mask (and never negative)");
     SelfArgs a;
     a.qkv = qkv; a.out = out; a.bias = bias; a.mask_tab = mask_tab; a.mask_id = mask_id;
     a.B = B; a.Hs = Hs; a.W = W; a.C = C; a.nH = C / HD; a.shift = shift;

@@ -586,7 +586,7 @@ static int window_attention_bwd_impl(bool mm16, const float* qkv, const float* d
     MUMPY_REQUIRE(B > 0 && Hs > 0 && W > 0 && Hs % WS == 0 && W % WS == 0, MUMPY_EINVAL,
                   "window_attention_bwd: grid (%d,%d) not divisible by window 7", Hs, W);
     MUMPY_REQUIRE(C > 0 && C % HD == 0 && shift >= 0 && shift < WS, MUMPY_EINVAL, "window_attention_bwd: bad C=%d / shift=%d", C, shift);
-    MUMPY_REQUIRE(mask_id == nullptr || n_mask > 0, MUMPY_EINVAL, "window_attention_bwd: n_mask must be > 0 with a mask");
+    MUMPY_REQUIRE(n_mask >= 0 && (mask_id == nullptr || n_mask > 0), MUMPY_EINVAL, "window_attention_bwd: n_mask must be > 0 with a mask (and never negative)");
     MUMPY_REQUIRE(workspace_bytes >= wa_bwd_workspace_bytes(B, Hs, W, C, mm16), MUMPY_EINVAL,
                   "window_attention_bwd: workspace too small");
     BwdArgs a;
