@@ -18,6 +18,7 @@
 // torch.optim.RMSprop (uncentered; 20 B per parameter, 28 B with momentum).
 #include <string.h>
 #include "common.h"
+#include "../../include/mumpy_hip_ext.h"
 using namespace mumpy;
 
 namespace {
@@ -135,6 +136,7 @@ struct AdamArgs {
     AdamHyper h;
     const AdamHyper* hdev;      // if set, the hyper-parameters are read from this DEVICE buffer (hipGraph replay: the launch is
                                 // frozen at capture, the step-dependent constants are not)
+    const unsigned* gate;       // if set and *gate != 0, the update is skipped (mumpy_update_gate): no load of p, g, m or v
 };
 
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, const AdamHyper& a) {
@@ -147,6 +149,7 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
 }
 
 __global__ __launch_bounds__(256) void adamw_kernel(AdamArgs a) {
+    if (a.gate && *a.gate) return;                     // one uniform load; the whole grid takes the same branch
     const AdamHyper hy = a.hdev ? *a.hdev : a.h;
     const int64_t n4 = a.n >> 2;
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -173,6 +176,7 @@ struct SgdArgs {
     int64_t n;
     SgdHyper h;
     const SgdHyper* hdev;                               // as AdamArgs::hdev
+    const unsigned* gate;                               // as AdamArgs::gate
     int nesterov;
 };
 
@@ -192,6 +196,7 @@ __device__ __forceinline__ void sgd_one(float& p, float g, float& b, const SgdHy
 
 template <bool MOM>
 __global__ __launch_bounds__(256) void sgd_kernel(SgdArgs a) {
+    if (a.gate && *a.gate) return;                     // one uniform load; the whole grid takes the same branch
     const SgdHyper hy = a.hdev ? *a.hdev : a.h;
     const bool nest = a.nesterov != 0;
     const int64_t n4 = a.n >> 2;
@@ -225,6 +230,7 @@ struct RmsArgs {
     int64_t n;
     RmsHyper h;
     const RmsHyper* hdev;
+    const unsigned* gate;
 };
 
 // torch.optim.RMSprop, _single_tensor_rmsprop with centered=False, rounded op by op as torch's kernels round (as sgd_one;
@@ -248,6 +254,7 @@ __device__ __forceinline__ void rms_one(float& p, float g, float& sq, float& b, 
 
 template <bool MOM>
 __global__ __launch_bounds__(256) void rmsprop_kernel(RmsArgs a) {
+    if (a.gate && *a.gate) return;                     // one uniform load; the whole grid takes the same branch
     const RmsHyper hy = a.hdev ? *a.hdev : a.h;
     const int64_t n4 = a.n >> 2;
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -322,12 +329,12 @@ static void adam_hyper(AdamHyper& h, double lr, double beta1, double beta2, doub
 }
 
 static int adamw_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const AdamHyper* host,
-                        const float* hyper_dev, void* stream) {
+                        const float* hyper_dev, void* stream, const uint32_t* gate = nullptr) {
     MUMPY_REQUIRE(param && grad && exp_avg && exp_avg_sq, MUMPY_ENULL, "adamw: null pointer");
     MUMPY_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), MUMPY_EALIGN,
                   "adamw: buffers must be 16-byte aligned");
     AdamArgs a;
-    a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n = n;
+    a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq; a.n = n; a.gate = gate;
     a.hdev = reinterpret_cast<const AdamHyper*>(hyper_dev);
     if (host) a.h = *host; else a.h = AdamHyper{1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 1.f, 0.f};
     hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)update_grid(n)), dim3(256), 0, as_stream(stream), a);
@@ -375,12 +382,12 @@ static int sgd_hyper(SgdHyper& h, double lr, double momentum, double dampening, 
 }
 
 static int sgd_launch(float* param, const float* grad, float* momentum_buf, int64_t n, const SgdHyper* host,
-                      const float* hyper_dev, int nesterov, void* stream) {
+                      const float* hyper_dev, int nesterov, void* stream, const uint32_t* gate = nullptr) {
     MUMPY_REQUIRE(param && grad, MUMPY_ENULL, "sgd: null pointer");
     MUMPY_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(momentum_buf), MUMPY_EALIGN, "sgd: buffers must be 16-byte aligned");
     MUMPY_REQUIRE(!nesterov || momentum_buf, MUMPY_EINVAL, "sgd: Nesterov momentum requires a momentum buffer");
     SgdArgs a;
-    a.p = param; a.g = grad; a.buf = momentum_buf; a.n = n; a.nesterov = nesterov;
+    a.p = param; a.g = grad; a.buf = momentum_buf; a.n = n; a.nesterov = nesterov; a.gate = gate;
     a.hdev = reinterpret_cast<const SgdHyper*>(hyper_dev);
     a.h = host ? *host : SgdHyper{0.f, 0.f, 0.f, 0.f};
     if (momentum_buf)
@@ -428,12 +435,12 @@ static int rmsprop_hyper(RmsHyper& h, double lr, double alpha, double eps, doubl
 }
 
 static int rmsprop_launch(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n,
-                          const RmsHyper* host, const float* hyper_dev, void* stream) {
+                          const RmsHyper* host, const float* hyper_dev, void* stream, const uint32_t* gate = nullptr) {
     MUMPY_REQUIRE(param && grad && square_avg, MUMPY_ENULL, "rmsprop: null pointer");
     MUMPY_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(square_avg) && aligned16(momentum_buf), MUMPY_EALIGN,
                   "rmsprop: buffers must be 16-byte aligned");
     RmsArgs a;
-    a.p = param; a.g = grad; a.sq = square_avg; a.buf = momentum_buf; a.n = n;
+    a.p = param; a.g = grad; a.sq = square_avg; a.buf = momentum_buf; a.n = n; a.gate = gate;
     a.hdev = reinterpret_cast<const RmsHyper*>(hyper_dev);
     a.h = host ? *host : RmsHyper{0.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
     if (momentum_buf)
@@ -653,4 +660,116 @@ extern "C" int mumpy_grad_norm_finish(const float* const* partials, const int64_
     hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(GN_THREADS), 0, as_stream(stream), a);
     MUMPY_CHECK_LAUNCH("grad_norm_finish");
     return 0;
+}
+
+// ---- skipping the update of a step whose gradient is non-finite (include/mumpy_hip_ext.h) ----
+// One launch of one workgroup at the head of the update, after the grad_norm finishes: it turns their statistics into ONE decision
+// for the whole step (gate[0]), keeps the skip counters, advances every group's applied-step count unless the step is skipped, and
+// makes AdamW's two bias-correction constants follow that count where it has fallen behind the nominal count the host staged them
+// from.  The gated *_step_dev launches (the kernels above with AdamArgs::gate set) return at once when gate[0] != 0.
+// Everything here is written by thread 0 with ordinary stores, in a fixed order (as grad_norm_finish_kernel's statistics).
+namespace {
+
+constexpr int GATE_MAX = 8;                    // statistics buffers, and groups, per step
+constexpr int GATE_WORDS = 8;
+
+struct UpdateGateArgs {
+    const float* stats[GATE_MAX];
+    AdamHyper* hyper[GATE_MAX];                // the staged constants of the AdamW groups; nullptr for the other kinds
+    unsigned* gate;
+    long long* applied;
+    const double* raw;                         // per group {lr, beta1, beta2, nominal t}
+    int n_stats, groups;
+};
+
+__global__ __launch_bounds__(64) void update_gate_kernel(UpdateGateArgs a) {
+    if (threadIdx.x != 0) return;
+    bool skip = false;
+    for (int s = 0; s < a.n_stats; ++s) {
+        const float norm = a.stats[s][0], bad = a.stats[s][2];
+        skip = skip || bad > 0.f || norm != norm;
+    }
+    const unsigned skipped = a.gate[1] + (skip ? 1u : 0u);
+    const unsigned run = skip ? a.gate[2] + 1u : 0u;
+    const unsigned seen = a.gate[3] + 1u;
+    const unsigned longest = run > a.gate[4] ? run : a.gate[4];
+    a.gate[0] = skip ? 1u : 0u; a.gate[1] = skipped; a.gate[2] = run; a.gate[3] = seen; a.gate[4] = longest;
+    for (int w = 5; w < GATE_WORDS; ++w) a.gate[w] = 0u;
+    if (skip) return;                          // nothing is applied: the counts and the staged constants stay
+    for (int g = 0; g < a.groups; ++g) {
+        const long long t_eff = a.applied[g] + 1;
+        a.applied[g] = t_eff;
+        if (!a.hyper[g]) continue;
+        const double* r = a.raw + 4 * g;
+        if (t_eff == (long long)r[3] || t_eff < 1) continue;      // the host's constants are this step's: leave every bit of them
+        const double bc1 = 1.0 - pow(r[1], (double)t_eff), bc2 = 1.0 - pow(r[2], (double)t_eff);     // as adam_hyper()
+        a.hyper[g]->step_size = (float)(r[0] / bc1);
+        a.hyper[g]->bc2_sqrt = (float)sqrt(bc2);
+    }
+}
+
+bool aligned_to(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1u)) == 0; }
+
+}  // namespace
+
+extern "C" int mumpy_ext_version(void) { return MUMPY_EXT_VERSION; }
+
+extern "C" int mumpy_adamw_gate_hyper(double* out4_host, double lr, double beta1, double beta2, int step) {
+    MUMPY_REQUIRE(out4_host, MUMPY_ENULL, "adamw_gate_hyper: null pointer");
+    MUMPY_REQUIRE(step >= 1 && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., MUMPY_EINVAL, "adamw_gate_hyper: bad arguments");
+    out4_host[0] = lr; out4_host[1] = beta1; out4_host[2] = beta2; out4_host[3] = (double)step;
+    return 0;
+}
+
+extern "C" int mumpy_update_gate(const float* const* stats, int n_stats, uint32_t* gate, float* const* hyper_dev,
+                                 const int* optimizer_kind, int groups, int64_t* applied, const double* adam_raw, void* stream) {
+    MUMPY_REQUIRE(stats && gate && hyper_dev && optimizer_kind && applied && adam_raw, MUMPY_ENULL, "update_gate: null pointer");
+    MUMPY_REQUIRE(n_stats >= 1 && groups >= 1, MUMPY_EINVAL, "update_gate: bad counts (%d statistics buffers, %d groups)", n_stats, groups);
+    MUMPY_REQUIRE(n_stats <= GATE_MAX && groups <= GATE_MAX, MUMPY_ERANGE,
+                  "update_gate: %d statistics buffers, %d groups (at most %d of each)", n_stats, groups, GATE_MAX);
+    MUMPY_REQUIRE(aligned_to(gate, 4), MUMPY_EALIGN, "update_gate: gate must be 4-byte aligned");
+    MUMPY_REQUIRE(aligned_to(applied, 8) && aligned_to(adam_raw, 8), MUMPY_EALIGN, "update_gate: applied and adam_raw must be 8-byte aligned");
+    UpdateGateArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int s = 0; s < n_stats; ++s) {
+        MUMPY_REQUIRE(stats[s], MUMPY_ENULL, "update_gate: null pointer (statistics buffer %d)", s);
+        MUMPY_REQUIRE(aligned_to(stats[s], 4), MUMPY_EALIGN, "update_gate: statistics buffer %d must be 4-byte aligned", s);
+        a.stats[s] = stats[s];
+    }
+    for (int g = 0; g < groups; ++g) {
+        const int k = optimizer_kind[g];
+        MUMPY_REQUIRE(k == MUMPY_OPT_ADAMW || k == MUMPY_OPT_SGD || k == MUMPY_OPT_RMSPROP, MUMPY_EINVAL,
+                      "update_gate: unknown optimizer kind %d (group %d)", k, g);
+        if (k != MUMPY_OPT_ADAMW) continue;
+        MUMPY_REQUIRE(hyper_dev[g], MUMPY_ENULL, "update_gate: null pointer (hyper_dev of AdamW group %d)", g);
+        MUMPY_REQUIRE(aligned_to(hyper_dev[g], 4), MUMPY_EALIGN, "update_gate: hyper_dev must be 4-byte aligned (group %d)", g);
+        a.hyper[g] = reinterpret_cast<AdamHyper*>(hyper_dev[g]);
+    }
+    a.gate = gate; a.applied = reinterpret_cast<long long*>(applied); a.raw = adam_raw; a.n_stats = n_stats; a.groups = groups;
+    hipLaunchKernelGGL(update_gate_kernel, dim3(1), dim3(64), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH("update_gate");
+    return 0;
+}
+
+#define MUMPY_GATED_ARGS(name)                                                                                        \
+    MUMPY_REQUIRE(hyper_dev && gate, MUMPY_ENULL, name ": null pointer");                                             \
+    MUMPY_REQUIRE(n >= 1, MUMPY_EINVAL, name ": bad size n=%lld", (long long)n);                                      \
+    MUMPY_REQUIRE(aligned_to(gate, 4) && aligned_to(hyper_dev, 4), MUMPY_EALIGN, name ": gate and hyper_dev must be 4-byte aligned")
+
+extern "C" int mumpy_adamw_step_gated_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                                          const float* hyper_dev, const uint32_t* gate, void* stream) {
+    MUMPY_GATED_ARGS("adamw_step_gated_dev");
+    return adamw_launch(param, grad, exp_avg, exp_avg_sq, n, nullptr, hyper_dev, stream, gate);
+}
+
+extern "C" int mumpy_sgd_step_gated_dev(float* param, const float* grad, float* momentum_buf, int64_t n, const float* hyper_dev,
+                                        int nesterov, const uint32_t* gate, void* stream) {
+    MUMPY_GATED_ARGS("sgd_step_gated_dev");
+    return sgd_launch(param, grad, momentum_buf, n, nullptr, hyper_dev, nesterov, stream, gate);
+}
+
+extern "C" int mumpy_rmsprop_step_gated_dev(float* param, const float* grad, float* square_avg, float* momentum_buf, int64_t n,
+                                            const float* hyper_dev, const uint32_t* gate, void* stream) {
+    MUMPY_GATED_ARGS("rmsprop_step_gated_dev");
+    return rmsprop_launch(param, grad, square_avg, momentum_buf, n, nullptr, hyper_dev, stream, gate);
 }

@@ -116,6 +116,16 @@ SIGNATURES = {
 }
 ABI_VERSION = 2
 
+# entry points added after that surface was frozen; mirrors include/mumpy_hip_ext.h one to one (tests/test_update_guard.py checks it)
+EXT_SIGNATURES = {
+    "mumpy_adamw_gate_hyper": [ctypes.POINTER(ctypes.c_double), c_d, c_d, c_d, c_i],
+    "mumpy_update_gate": [c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f],       # (stats, hyper_dev, optimizer_kind: HOST tables)
+    "mumpy_adamw_step_gated_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f, c_f],
+    "mumpy_sgd_step_gated_dev": [c_f, c_f, c_f, c_l, c_f, c_i, c_f, c_f],
+    "mumpy_rmsprop_step_gated_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f, c_f],
+}
+EXT_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -158,7 +168,11 @@ def load_library():
     lib.mumpy_last_route.argtypes = []
     if lib.mumpy_abi_version() != ABI_VERSION:
         raise RuntimeError(f"{path}: ABI version {lib.mumpy_abi_version()} != binding {ABI_VERSION}; rebuild")
-    for name, args in SIGNATURES.items():
+    lib.mumpy_ext_version.restype = c_i                 # (AttributeError = stale library, as below)
+    lib.mumpy_ext_version.argtypes = []
+    if lib.mumpy_ext_version() != EXT_VERSION:
+        raise RuntimeError(f"{path}: extension version {lib.mumpy_ext_version()} != binding {EXT_VERSION}; rebuild")
+    for name, args in {**SIGNATURES, **EXT_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

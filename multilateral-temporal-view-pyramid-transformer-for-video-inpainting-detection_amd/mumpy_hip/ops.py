@@ -1353,3 +1353,89 @@ def grad_norm_finish(partials, sizes, hypers, kinds, stats, max_norm=None):
     _call("mumpy_grad_norm_finish", ptrs, ns, hyps, ks, groups, int(max_norm is not None), float(max_norm or 0.0), _p(stats),
           _stream(), work=8.0 * sum(grad_norm_partials(n) for n in sizes))
     return stats
+
+
+# ---- skipping the update of a step whose gradient is non-finite (include/mumpy_hip_ext.h; train.UpdateGuard) ----
+UPDATE_GATE_MAX = 8        # statistics buffers, and groups, behind one gate
+GATE_WORDS = 8             # [skip, skipped, consecutive, updates, longest, 0, 0, 0] (uint32, kept in an int32 tensor)
+
+
+def adamw_gate_hyper(step, lr, betas=(0.9, 0.999)):
+    """The 4 doubles {lr, beta1, beta2, step} mumpy_update_gate re-derives AdamW's bias corrections from, as a pinned host tensor
+    (staged beside adamw_hyper's 8 floats; `step` is the nominal count those were derived from)."""
+    import ctypes
+    out = torch.empty(4, dtype=torch.float64).pin_memory()
+    rc = _lib().mumpy_adamw_gate_hyper(ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double)), lr, betas[0], betas[1], int(step))
+    if rc != 0:
+        raise RuntimeError(f"mumpy_adamw_gate_hyper failed (rc={rc}): {_lib().mumpy_last_error().decode()}")
+    return out
+
+
+def _chk_gate(fn, gate):
+    if not gate.is_cuda or gate.dtype != torch.int32 or gate.numel() != GATE_WORDS or not gate.is_contiguous():
+        raise RuntimeError(f"{fn}: gate must be a contiguous int32 GPU tensor of {GATE_WORDS} words")
+    return gate
+
+
+def update_gate(stats, gate, hypers, kinds, applied, adam_raw):
+    """One launch at the head of an update, after every grad_norm_finish of the step: gate[0] = 1 if any of the `stats` buffers
+    (1 ... 8) reports a non-finite gradient element or a NaN norm, else 0; the skip counters in gate[1 ... 4]; unless skipped,
+    applied[g] += 1 for every group (1 ... 8: `kinds[g]` its _FlatOptimizer.KIND, `hypers[g]` its staged device constants, read
+    for AdamW only), and an AdamW group whose applied count differs from the nominal count in adam_raw[4 g + 3] gets its two
+    bias-correction constants recomputed from adam_raw[4 g : 4 g + 3] = (lr, beta1, beta2).  `applied`: int64, one per group;
+    `adam_raw`: float64, 4 per group.  Capturable: the tables are packed into the launch on the host."""
+    import ctypes
+    groups = len(kinds)
+    if not 1 <= len(stats) <= UPDATE_GATE_MAX:
+        raise ValueError(f"update_gate: {len(stats)} statistics buffers (1 to {UPDATE_GATE_MAX})")
+    if not 1 <= groups <= UPDATE_GATE_MAX:
+        raise ValueError(f"update_gate: {groups} groups (1 to {UPDATE_GATE_MAX})")
+    if len(hypers) != groups:
+        raise RuntimeError("update_gate: one hyper buffer and optimizer kind per group")
+    for s in stats:
+        _chk(s, "stats")
+        if not s.is_contiguous() or s.numel() < 4:
+            raise RuntimeError("update_gate: a statistics buffer must be a contiguous buffer of at least 4 floats")
+    for g, (h, k) in enumerate(zip(hypers, kinds)):
+        if k not in _OPT_KINDS:
+            raise ValueError(f"update_gate: unknown optimizer kind {k!r} (group {g})")
+        _chk(h, "hyper")
+        if not h.is_contiguous() or h.numel() < (4 if k == "SGD" else 8):
+            raise RuntimeError(f"update_gate: hyper buffer of group {g} is too small for {k}")
+    _chk_gate("update_gate", gate)
+    if not applied.is_cuda or applied.dtype != torch.int64 or applied.numel() != groups or not applied.is_contiguous():
+        raise RuntimeError(f"update_gate: applied must be a contiguous int64 GPU tensor of {groups} counts")
+    if not adam_raw.is_cuda or adam_raw.dtype != torch.float64 or adam_raw.numel() != 4 * groups or not adam_raw.is_contiguous():
+        raise RuntimeError(f"update_gate: adam_raw must be a contiguous float64 GPU tensor of {4 * groups} values")
+    sts = (ctypes.c_void_p * len(stats))(*[_p(s) for s in stats])
+    hyps = (ctypes.c_void_p * groups)(*[_p(h) for h in hypers])
+    ks = (ctypes.c_int * groups)(*[_OPT_KINDS[k] for k in kinds])
+    _call("mumpy_update_gate", sts, len(stats), _p(gate), hyps, ks, groups, _p(applied), _p(adam_raw), _stream())
+    return gate
+
+
+def adamw_step_gated_dev(param, grad, exp_avg, exp_avg_sq, hyper_dev, gate):
+    """adamw_step_dev behind `gate` (update_gate): nothing is read or written when gate[0] != 0, the same bits otherwise."""
+    n = param.numel()
+    _flat_bufs("adamw_step_gated_dev", n, param=param, grad=grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
+    _call("mumpy_adamw_step_gated_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(_chk(hyper_dev, "hyper")),
+          _p(_chk_gate("adamw_step_gated_dev", gate)), _stream(), work=28.0 * n)
+    return param
+
+
+def sgd_step_gated_dev(param, grad, momentum_buf, hyper_dev, gate, nesterov=False):
+    """sgd_step_dev behind `gate` (as adamw_step_gated_dev)."""
+    n = param.numel()
+    _flat_bufs("sgd_step_gated_dev", n, param=param, grad=grad, momentum_buf=momentum_buf)
+    _call("mumpy_sgd_step_gated_dev", _p(param), _p(grad), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")), int(bool(nesterov)),
+          _p(_chk_gate("sgd_step_gated_dev", gate)), _stream(), work=(20.0 if momentum_buf is not None else 12.0) * n)
+    return param
+
+
+def rmsprop_step_gated_dev(param, grad, square_avg, momentum_buf, hyper_dev, gate):
+    """rmsprop_step_dev behind `gate` (as adamw_step_gated_dev)."""
+    n = param.numel()
+    _flat_bufs("rmsprop_step_gated_dev", n, param=param, grad=grad, square_avg=square_avg, momentum_buf=momentum_buf)
+    _call("mumpy_rmsprop_step_gated_dev", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")),
+          _p(_chk_gate("rmsprop_step_gated_dev", gate)), _stream(), work=(28.0 if momentum_buf is not None else 20.0) * n)
+    return param

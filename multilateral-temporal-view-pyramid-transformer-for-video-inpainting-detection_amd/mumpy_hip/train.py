@@ -77,8 +77,10 @@ class _FlatOptimizer:
             p.grad = self._slot(self.grad, p, o)
             p._mumpy_flat_grad = p.grad           # marker: the backward kernels may accumulate into this view (autograd._grad_slot)
         self.base_lr = self.lr = lr
-        self.steps = 0            # optimizer steps taken
+        self.steps = 0            # optimizer steps taken (with an UpdateGuard: attempted -- the nominal count)
         self.sched_it = 0         # scheduler steps taken (PolynomialLR.last_epoch)
+        self._guard = None        # the UpdateGuard attached last: step_dev then runs behind its gate
+        self._skipped_host = 0    # steps - applied steps as read from a checkpoint (the guard's device counter takes over from it)
 
     def _zeros(self):
         return torch.zeros(self.offsets[-1], device=self.params[0].device, dtype=torch.float32)
@@ -123,6 +125,20 @@ class _FlatOptimizer:
         self.steps = int(extra.get("steps", steps))          # (one step count per group: every parameter steps together here)
         self.sched_it = int(extra.get("sched_it", self.steps))
         self.base_lr = float(extra.get("base_lr", g.get("initial_lr", self.lr)))
+
+    def _seed_applied(self, applied: int) -> None:
+        """After load_state_dict: `applied` updates were applied of the `self.steps` attempted; an attached guard's device counter
+        is re-seeded with it."""
+        self._skipped_host = max(0, self.steps - int(applied))
+        if self._guard is not None:
+            self._guard.seed(self)
+
+    def applied_steps(self) -> int:
+        """Updates actually applied: `steps` minus the ones an UpdateGuard skipped.  With a guard attached this reads its device
+        counter (a device-to-host copy: it synchronises, which is fine where a checkpoint is written)."""
+        if self._guard is not None:
+            return self._guard.applied_steps(self)
+        return self.steps - self._skipped_host
 
     def _load_slots(self, sd: dict, key: str, buf) -> None:
         """Copy state[i][key] into buf's slots; a parameter without that state (torch omits parameters that never received a
@@ -169,10 +185,15 @@ class _FlatOptimizer:
         advance=False stages the constants of the NEXT step without counting it (used while capturing: nothing executes)."""
         if advance:
             self.steps += 1
-        self._hyper_host = self._hyper(self.steps if advance else self.steps + 1, grad_scale)
+        step = self.steps if advance else self.steps + 1
+        self._hyper_host = self._hyper(step, grad_scale)
         self.hyper_dev.copy_(self._hyper_host, non_blocking=True)
+        if self._guard is not None:
+            self._guard.stage(self, step)
 
     def scheduler_step(self, iter_max: int, power: float = 0.9, min_lr: float = 1e-5):
+        """One scheduler step.  Host-side: under an UpdateGuard it keeps advancing on skipped updates too (torch's behaviour when
+        `scheduler.step()` follows `scaler.step(optimizer)`): the rate follows the updates attempted, not the ones applied."""
         self.sched_it += 1
         self.lr = polynomial_lr(self.base_lr, self.lr, self.sched_it, iter_max, power, min_lr)
         return self.lr
@@ -191,7 +212,8 @@ class FlatAdamW(_FlatOptimizer):
         self.weight_decay, self.betas, self.eps = weight_decay, betas, eps
 
     def state_dict(self) -> dict:
-        state = {i: {"step": torch.tensor(float(self.steps)), "exp_avg": self._state_slot(self.exp_avg, i),
+        applied = float(self.applied_steps())            # what torch holds: the updates applied (== steps unless a guard skipped some)
+        state = {i: {"step": torch.tensor(applied), "exp_avg": self._state_slot(self.exp_avg, i),
                      "exp_avg_sq": self._state_slot(self.exp_avg_sq, i)} for i in range(len(self.params))}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.weight_decay, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None}
@@ -204,6 +226,7 @@ class FlatAdamW(_FlatOptimizer):
         self._load_slots(sd, "exp_avg_sq", self.exp_avg_sq)
         steps = max([int(float(st["step"])) for st in sd["state"].values()], default=0)
         self._load_counters(sd, g, steps)
+        self._seed_applied(steps if sd["state"] else self.steps)
 
     def _launch(self, grad_scale):
         ops.adamw_step(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.steps, self.lr, self.betas, self.eps,
@@ -213,8 +236,11 @@ class FlatAdamW(_FlatOptimizer):
         return ops.adamw_hyper(step, self.lr, self.betas, self.eps, self.weight_decay, grad_scale)
 
     def step_dev(self):
-        """Device side: the update with constants from `hyper_dev` (what gets captured)."""
-        ops.adamw_step_dev(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.hyper_dev)
+        """Device side: the update with constants from `hyper_dev` (what gets captured); behind the gate of an attached UpdateGuard."""
+        if self._guard is not None:
+            ops.adamw_step_gated_dev(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.hyper_dev, self._guard.gate)
+        else:
+            ops.adamw_step_dev(self.param, self.grad, self.exp_avg, self.exp_avg_sq, self.hyper_dev)
 
 
 class FlatSGD(_FlatOptimizer):
@@ -255,6 +281,7 @@ class FlatSGD(_FlatOptimizer):
             self._load_slots(sd, "momentum_buffer", self.momentum_buffer)
         self._loaded_state = self.momentum_buffer is not None and bool(sd["state"])
         self._load_counters(sd, g, 0)
+        self._seed_applied(self.steps)                   # (torch's SGD state has no step count to restore)
 
     def _launch(self, grad_scale):
         ops.sgd_step(self.param, self.grad, self.momentum_buffer, self.lr, self.momentum, self.weight_decay, self.nesterov,
@@ -264,7 +291,10 @@ class FlatSGD(_FlatOptimizer):
         return ops.sgd_hyper(self.lr, self.momentum, self.weight_decay, self.nesterov, grad_scale)
 
     def step_dev(self):
-        ops.sgd_step_dev(self.param, self.grad, self.momentum_buffer, self.hyper_dev, self.nesterov)
+        if self._guard is not None:
+            ops.sgd_step_gated_dev(self.param, self.grad, self.momentum_buffer, self.hyper_dev, self._guard.gate, self.nesterov)
+        else:
+            ops.sgd_step_dev(self.param, self.grad, self.momentum_buffer, self.hyper_dev, self.nesterov)
 
 
 class FlatRMSprop(_FlatOptimizer):
@@ -282,8 +312,9 @@ class FlatRMSprop(_FlatOptimizer):
     def state_dict(self) -> dict:
         state = {}
         if self.steps > 0:
+            applied = float(self.applied_steps())        # as FlatAdamW.state_dict
             for i in range(len(self.params)):
-                state[i] = {"step": torch.tensor(float(self.steps)), "square_avg": self._state_slot(self.square_avg, i)}
+                state[i] = {"step": torch.tensor(applied), "square_avg": self._state_slot(self.square_avg, i)}
                 if self.momentum_buffer is not None:
                     state[i]["momentum_buffer"] = self._state_slot(self.momentum_buffer, i)
         group = {"lr": self.lr, "momentum": self.momentum, "alpha": self.alpha, "eps": self.eps, "centered": False,
@@ -306,6 +337,7 @@ class FlatRMSprop(_FlatOptimizer):
             self.momentum_buffer = None
         steps = max([int(float(st["step"])) for st in sd["state"].values()], default=0)
         self._load_counters(sd, g, steps)
+        self._seed_applied(steps if sd["state"] else self.steps)
 
     def _launch(self, grad_scale):
         ops.rmsprop_step(self.param, self.grad, self.square_avg, self.momentum_buffer, self.lr, self.alpha, self.eps,
@@ -315,7 +347,10 @@ class FlatRMSprop(_FlatOptimizer):
         return ops.rmsprop_hyper(self.lr, self.alpha, self.eps, self.weight_decay, self.momentum, grad_scale)
 
     def step_dev(self):
-        ops.rmsprop_step_dev(self.param, self.grad, self.square_avg, self.momentum_buffer, self.hyper_dev)
+        if self._guard is not None:
+            ops.rmsprop_step_gated_dev(self.param, self.grad, self.square_avg, self.momentum_buffer, self.hyper_dev, self._guard.gate)
+        else:
+            ops.rmsprop_step_dev(self.param, self.grad, self.square_avg, self.momentum_buffer, self.hyper_dev)
 
 
 def get_optimizer(name: str, lr: float, params: Iterable[torch.nn.Parameter], weight_decay: float = 1e-4,
@@ -357,8 +392,10 @@ class GradClip:
     per optimizer is timm's per-optimizer `clip_grad` (the knob of the reference's recipes, train.py:223-273).
     max_norm=None only measures: coef is exactly 1 and the staged constants are left alone.
     `stats` (device, 4 + G floats) = [total_norm, coef, non-finite element count, 0, norm_0 ... norm_{G-1}].
-    Not covered: skipping an update whose gradient is non-finite (coef is then NaN or 0 exactly as torch's is, and the update runs),
-    clip_grad_value_, adaptive clipping, norms other than L2."""
+    skip_nonfinite=True: an update whose gradient holds a NaN or an Inf is skipped on the device, for ALL the optimizers here (what
+    torch's GradScaler.step does when it found an inf): `.guard` is the UpdateGuard, `step()` runs stage -> measure -> gate -> gated
+    updates.  Without it coef is NaN or 0 exactly as torch's is for such a gradient, and the update runs.
+    Not covered: clip_grad_value_, adaptive clipping, norms other than L2, dynamic loss scaling."""
     MAX_GROUPS = ops.GRAD_NORM_MAX_GROUPS
 
     @staticmethod
@@ -373,9 +410,11 @@ class GradClip:
             if getattr(o, "KIND", None) not in ops._OPT_KINDS:
                 raise ValueError(f"GradClip: {type(o).__name__} is not a flat optimizer of this package")
 
-    def __init__(self, optimizers, max_norm: Optional[float] = None):
+    def __init__(self, optimizers, max_norm: Optional[float] = None, skip_nonfinite: bool = False):
         self.opts = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
         self._validate(self.opts, max_norm)
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f"GradClip: skip_nonfinite must be True or False, got {skip_nonfinite!r}")
         self.max_norm = None if max_norm is None else float(max_norm)
         for o in self.opts:
             if not hasattr(o, "hyper_dev"):
@@ -386,6 +425,7 @@ class GradClip:
         self._ws = torch.zeros(sum(counts), device=dev, dtype=torch.float32)
         self.partials = list(self._ws.split(counts))
         self.stats = torch.zeros(4 + len(self.opts), device=dev, dtype=torch.float32)
+        self.guard = UpdateGuard(self.opts, [self]) if skip_nonfinite else None
 
     def measure(self):
         """Enqueue the G partial launches and the finish on the current stream.  Must follow the optimizers' `stage_hyper` in stream
@@ -408,6 +448,8 @@ class GradClip:
         for o, sc in zip(self.opts, scales):
             o.stage_hyper(sc)
         self.measure()
+        if self.guard is not None:
+            self.guard.launch()
         for o in self.opts:
             o.step_dev()
         bump_weights_epoch()
@@ -417,6 +459,88 @@ class GradClip:
         """The statistics of the last measure() on the host.  This is the one call here that synchronises (a device-to-host copy)."""
         s = self.stats.cpu().tolist()
         return {"total_norm": s[0], "coef": s[1], "nonfinite": int(s[2]), "norms": s[4:]}
+
+
+class UpdateGuard:
+    """Skips, on the device, the update of a step whose gradient is non-finite: ONE decision for all `optimizers` (1 ... 8), taken
+    from the statistics of all `clips` (1 ... 8 GradClip, each measuring some of them; optimizers no clip measures are not looked
+    at): a non-finite element or a NaN norm anywhere and nobody is updated, so the groups never go out of step with one another.
+    A finite gradient whose norm overflows to +Inf is not skipped.  Owns the gate words, the raw AdamW constants and the
+    applied-step counters, all on the device; attaches itself to the optimizers, whose `stage_hyper` then calls `stage()` and whose
+    `step_dev()` runs behind the gate.  Order within a step: stage_hyper of every optimizer, measure() of every clip, `launch()`,
+    step_dev() of every optimizer.  No host synchronisation, no allocation per call: capturable.
+
+    `opt.steps` stays the number of updates ATTEMPTED (what the staged constants and the LR schedule follow); AdamW's bias
+    corrections follow the updates APPLIED: the gate launch recomputes them on the device once the two counts differ, and leaves
+    the staged constants untouched while they agree (a run that never skips is bitwise the unguarded one).  `state_dict()["state"]
+    [i]["step"]` of FlatAdamW / FlatRMSprop is the applied count, `load_state_dict` re-seeds it.  The skip statistics (`read()`) are
+    not part of a checkpoint.  The gradient reset stays the caller's zero_grad(): the bad gradient -- the whole accumulated cycle
+    under gradient accumulation -- is dropped whether or not the update ran."""
+    MAX_GROUPS = ops.UPDATE_GATE_MAX
+
+    @staticmethod
+    def _validate(opts, n_clips):
+        if not opts:
+            raise ValueError("UpdateGuard: no optimizers")
+        if len(opts) > UpdateGuard.MAX_GROUPS:
+            raise ValueError(f"UpdateGuard: {len(opts)} optimizers (at most {UpdateGuard.MAX_GROUPS} share one decision)")
+        if not 1 <= n_clips <= UpdateGuard.MAX_GROUPS:
+            raise ValueError(f"UpdateGuard: {n_clips} clips (1 to {UpdateGuard.MAX_GROUPS} statistics buffers feed one decision)")
+        for o in opts:
+            if getattr(o, "KIND", None) not in ops._OPT_KINDS:
+                raise ValueError(f"UpdateGuard: {type(o).__name__} is not a flat optimizer of this package")
+
+    def __init__(self, optimizers, clips):
+        self.opts = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
+        self.clips = list(clips)
+        self._validate(self.opts, len(self.clips))
+        for c in self.clips:
+            if not isinstance(c, GradClip) or any(all(o is not mine for mine in self.opts) for o in c.opts):
+                raise ValueError("UpdateGuard: every clip must be a GradClip over some of the guard's optimizers")
+        dev = self.opts[0].grad.device
+        for o in self.opts:
+            if not hasattr(o, "hyper_dev"):
+                o.enable_device_hyper()
+        g = len(self.opts)
+        self.gate = torch.zeros(ops.GATE_WORDS, device=dev, dtype=torch.int32)
+        self.raw = torch.zeros(4 * g, device=dev, dtype=torch.float64)          # per group: lr, beta1, beta2, nominal step (AdamW)
+        self.applied = torch.tensor([o.steps - o._skipped_host for o in self.opts], dtype=torch.int64).to(dev)
+        self._raw_host = [None] * g
+        for o in self.opts:
+            o._guard = self
+
+    def _index(self, opt) -> int:
+        for g, o in enumerate(self.opts):
+            if o is opt:
+                return g
+        raise ValueError("UpdateGuard: not one of this guard's optimizers")
+
+    def stage(self, opt, step: int) -> None:
+        """Host side, from opt.stage_hyper: the raw constants the gate launch re-derives AdamW's bias corrections from."""
+        if opt.KIND != "AdamW":
+            return
+        g = self._index(opt)
+        self._raw_host[g] = ops.adamw_gate_hyper(step, opt.lr, opt.betas)        # (pinned; kept until the next one replaces it)
+        self.raw[4 * g:4 * g + 4].copy_(self._raw_host[g], non_blocking=True)
+
+    def seed(self, opt) -> None:
+        """Set opt's applied-step counter from the host (after load_state_dict)."""
+        self.applied[self._index(opt)] = opt.steps - opt._skipped_host
+
+    def applied_steps(self, opt) -> int:
+        return int(self.applied[self._index(opt)].item())
+
+    def launch(self):
+        """Enqueue the gate launch on the current stream: after the clips' measure(), before the optimizers' step_dev()."""
+        ops.update_gate([c.stats for c in self.clips], self.gate, [o.hyper_dev for o in self.opts], [o.KIND for o in self.opts],
+                        self.applied, self.raw)
+        return self.gate
+
+    def read(self) -> dict:
+        """The skip counters on the host.  The one call here that synchronises (a device-to-host copy), like GradClip.read(): poll it
+        where the loss is read back."""
+        w = self.gate.cpu().tolist()
+        return {"skipped": w[1], "consecutive": w[2], "longest": w[4], "updates": w[3], "last_skipped": bool(w[0])}
 
 
 class GraphedTrainStep:
@@ -431,10 +555,15 @@ class GraphedTrainStep:
     a dict keyed like the `optimizers` dict clips each named optimizer by its own norm (a missing key leaves that optimizer
     unclipped).  The norm is measured at the head of the update -- after the all-reduce, with the 1/world factor staged, once per
     update under accumulation -- and `.grad_stats` is the device statistics tensor (a dict of them for the dict form; GradClip.stats
-    gives the layout).  The `.grad` buffers keep the unclipped sum until the update zeroes them.  None: nothing is launched."""
+    gives the layout).  The `.grad` buffers keep the unclipped sum until the update zeroes them.  None: nothing is launched.
+    skip_nonfinite=True: the replayed update is skipped, for every optimizer at once, when a gradient holds a NaN or an Inf
+    (UpdateGuard; `.guard`, poll `.guard.read()` next to the loss read-back -- a replay never raises).  It gates on all the step's
+    clips together; optimizers that no clip_grad entry covers (all of them when clip_grad is None) get one measure-only GradClip, so
+    every gradient is looked at.  The norm is measured after the all-reduce, so every rank takes the same decision; under
+    accumulation the whole cycle's gradient is dropped.  The gradient reset runs either way.  False: nothing new is launched."""
 
     def __init__(self, forward_fn, optimizers, x, target, warmup: int = 3, loss_scale: float = 1.0, all_reduce: bool = False,
-                 accumulation_steps: int = 1, clip_grad=None):
+                 accumulation_steps: int = 1, clip_grad=None, skip_nonfinite: bool = False):
         """all_reduce=True (data-parallel ranks): TWO graphs -- forward + loss + backward, and update + gradient reset -- with
         the bucketed gradient all-reduce (RCCL) issued eagerly between their replays.
         accumulation_steps=k > 1 (train.py:115-120): every step() is one micro-batch whose loss gradient is scaled by
@@ -442,6 +571,8 @@ class GraphedTrainStep:
         one) then runs the update graph (two graphs, as with all_reduce).  The warm-up covers at least one whole cycle."""
         if accumulation_steps < 1:
             raise ValueError(f"GraphedTrainStep: accumulation_steps must be >= 1, got {accumulation_steps}")
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f"GraphedTrainStep: skip_nonfinite must be True or False, got {skip_nonfinite!r}")
         self.opts = list(optimizers.values()) if isinstance(optimizers, dict) else list(optimizers)
         clip_plan = []                    # [(key or None, optimizers, max_norm)], checked before anything touches the GPU
         if isinstance(clip_grad, dict):
@@ -457,6 +588,13 @@ class GraphedTrainStep:
             if c is None or isinstance(c, bool) or not isinstance(c, (int, float)):
                 raise ValueError(f"GraphedTrainStep: clip_grad must be a positive number, got {c!r}")
             GradClip._validate(group, c)
+        if skip_nonfinite:
+            covered = [o for _, group, _ in clip_plan for o in group]
+            rest = [o for o in self.opts if all(o is not c for c in covered)]
+            if rest:
+                GradClip._validate(rest, None)
+                clip_plan.append((None, rest, None))         # measure only: the guard must see every gradient
+            UpdateGuard._validate(self.opts, len(clip_plan))
         self.x, self.target = x.clone(), target.clone()
         self.all_reduce = all_reduce
         self.accumulation_steps = k = int(accumulation_steps)
@@ -465,9 +603,10 @@ class GraphedTrainStep:
         for o in self.opts:
             o.enable_device_hyper()
         self.clips = [GradClip(group, c) for _, group, c in clip_plan]
+        self.guard = UpdateGuard(self.opts, self.clips) if skip_nonfinite else None
         self.grad_stats = None
         if isinstance(clip_grad, dict):
-            self.grad_stats = {key: clip.stats for (key, _, _), clip in zip(clip_plan, self.clips)}
+            self.grad_stats = {key: clip.stats for (key, _, _), clip in zip(clip_plan, self.clips) if key is not None}
         elif self.clips:
             self.grad_stats = self.clips[0].stats
 
@@ -480,6 +619,8 @@ class GraphedTrainStep:
         def update():
             for clip in self.clips:               # reads the staged gradient scales and folds the clip coefficient into them
                 clip.measure()
+            if self.guard is not None:            # one decision for all the optimizers, from all the clips' statistics
+                self.guard.launch()
             for o in self.opts:
                 o.step_dev()
                 o.zero_grad()

@@ -1,0 +1,653 @@
+"""Skipping the update of a step whose gradient is non-finite (include/mumpy_hip_ext.h: mumpy_update_gate and the gated *_step_dev;
+train.UpdateGuard, GradClip(skip_nonfinite=True), GraphedTrainStep(skip_nonfinite=True)).
+
+CPU tests: the second public header against its binding table and both libraries' exports, the host checks of its launching entry
+points (swept in a child process without a GPU, as tests/test_abi_refusals.py sweeps the first header), the host helper, the Python
+argument errors.  `gpu` tests: the gated kernels against the ungated ones bitwise, a skipped update inside guard bands
+(tests/guarded_alloc.py), AdamW's device-side step count against torch.optim.AdamW, the replayed step in its three forms against the
+eager loop that leaves the bad update out, two clips under one decision, the switch off, and checkpoint resume.
+
+The sweep's child is this file run as a script (`python tests/test_update_guard.py`): it prints one JSON line per probe BEFORE the
+call and never calls anything where a GPU is visible (a valid tuple of fake addresses would really launch there)."""
+import ctypes
+import functools
+import json
+import os
+import re
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "multilateral-temporal-view-pyramid-transformer-for-video-inpainting-detection_amd")
+LAUNCHING = ["mumpy_adamw_step_gated_dev", "mumpy_rmsprop_step_gated_dev", "mumpy_sgd_step_gated_dev", "mumpy_update_gate"]
+
+
+def _decls(header):
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    out = {}
+    for m in re.finditer(r"\b(?:int64_t|int|const char\*)\s+(mumpy_\w+)\s*\(([^)]*)\)\s*;", src):
+        out[m.group(1)] = [a.strip() for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------ the child
+A = 0x100000                     # fake device addresses: 16-byte aligned, never dereferenced
+
+
+def _probes():
+    """-> [(entry, mutation, expectation, argument builder)]; expectation "pos" (every host check passed: the launch reached a runtime
+    that has no device) or "neg" (refused with a message of the call's own).  The host tables are real host arrays."""
+    probes = []
+
+    def step_args(entry, **over):
+        a = dict(param=A, grad=2 * A, s1=3 * A, s2=4 * A, n=16, hyper_dev=5 * A, nesterov=0, gate=6 * A)
+        a.update(over)
+        if entry == "mumpy_adamw_step_gated_dev":
+            return [a["param"], a["grad"], a["s1"], a["s2"], a["n"], a["hyper_dev"], a["gate"], None]
+        if entry == "mumpy_sgd_step_gated_dev":
+            return [a["param"], a["grad"], a["s1"], a["n"], a["hyper_dev"], a["nesterov"], a["gate"], None]
+        return [a["param"], a["grad"], a["s1"], a["s2"], a["n"], a["hyper_dev"], a["gate"], None]
+
+    # (s2 of RMSprop and s1 of SGD are the optional momentum buffer: NULL <=> momentum 0, a valid call)
+    slots = {"mumpy_adamw_step_gated_dev": ["param", "grad", "s1", "s2", "hyper_dev", "gate"],
+             "mumpy_sgd_step_gated_dev": ["param", "grad", "hyper_dev", "gate"],
+             "mumpy_rmsprop_step_gated_dev": ["param", "grad", "s1", "hyper_dev", "gate"]}
+    bufs = {"mumpy_adamw_step_gated_dev": ["param", "grad", "s1", "s2"], "mumpy_sgd_step_gated_dev": ["param", "grad", "s1"],
+            "mumpy_rmsprop_step_gated_dev": ["param", "grad", "s1", "s2"]}
+    for entry, ptrs in slots.items():
+        probes.append((entry, "valid", "pos", step_args(entry)))
+        for p in ptrs:
+            probes.append((entry, f"{p}=NULL", "neg", step_args(entry, **{p: None})))
+        for n in (0, -1):
+            probes.append((entry, f"n={n}", "neg", step_args(entry, n=n)))
+        for p in bufs[entry]:
+            probes.append((entry, f"{p} not 16-byte aligned", "neg", step_args(entry, **{p: A + 4})))
+        probes.append((entry, "gate not 4-byte aligned", "neg", step_args(entry, gate=6 * A + 2)))
+    probes.append(("mumpy_sgd_step_gated_dev", "valid, no momentum buffer", "pos", step_args("mumpy_sgd_step_gated_dev", s1=None)))
+    probes.append(("mumpy_rmsprop_step_gated_dev", "valid, no momentum buffer", "pos", step_args("mumpy_rmsprop_step_gated_dev", s2=None)))
+
+    def gate_args(n_stats=1, groups=1, stats="ok", gate=A, hyper="ok", kinds="ok", applied=2 * A, raw=3 * A, stat_ptr=4 * A,
+                  hyper_ptr=5 * A, kind=0):
+        m, g = max(1, min(n_stats, 16)), max(1, min(groups, 16))
+        st = (ctypes.c_void_p * m)(*[stat_ptr] * m) if stats == "ok" else None
+        hy = (ctypes.c_void_p * g)(*[hyper_ptr] * g) if hyper == "ok" else None
+        ks = (ctypes.c_int * g)(*[kind] * g) if kinds == "ok" else None
+        return [st, n_stats, gate, hy, ks, groups, applied, raw, None]
+
+    e = "mumpy_update_gate"
+    probes.append((e, "valid", "pos", gate_args()))
+    probes.append((e, "valid, 8 statistics buffers and 8 groups", "pos", gate_args(n_stats=8, groups=8)))
+    probes.append((e, "valid, an SGD group without hyper_dev", "pos", gate_args(kind=1, hyper_ptr=None)))
+    for name, kw in (("stats", dict(stats=None)), ("gate", dict(gate=None)), ("hyper_dev", dict(hyper=None)),
+                     ("optimizer_kind", dict(kinds=None)), ("applied", dict(applied=None)), ("adam_raw", dict(raw=None)),
+                     ("stats[0]", dict(stat_ptr=None)), ("hyper_dev[0] of an AdamW group", dict(hyper_ptr=None))):
+        probes.append((e, f"{name}=NULL", "neg", gate_args(**kw)))
+    for name, kw in (("n_stats=0", dict(n_stats=0)), ("n_stats=9", dict(n_stats=9)), ("n_stats=-1", dict(n_stats=-1)),
+                     ("groups=0", dict(groups=0)), ("groups=9", dict(groups=9)), ("groups=-1", dict(groups=-1)),
+                     ("gate not 4-byte aligned", dict(gate=A + 2)), ("stats[0] not 4-byte aligned", dict(stat_ptr=4 * A + 2)),
+                     ("hyper_dev[0] not 4-byte aligned", dict(hyper_ptr=5 * A + 2)), ("applied not 8-byte aligned", dict(applied=2 * A + 4)),
+                     ("adam_raw not 8-byte aligned", dict(raw=3 * A + 4)), ("unknown optimizer kind", dict(kind=3))):
+        probes.append((e, name, "neg", gate_args(**kw)))
+    return probes
+
+
+def child():
+    import torch
+    if torch.cuda.is_available():                                         # a valid tuple of fake addresses would really launch
+        print(json.dumps({"refused": "a GPU is visible"}), flush=True)
+        return 3
+    sys.path.insert(0, PKG)
+    from mumpy_hip.lib import load_library
+    lib = load_library()
+    probes = _probes()
+    for entry, mutation, expect, args in probes:
+        print(json.dumps({"entry": entry, "mutation": mutation, "expect": expect}), flush=True)      # BEFORE the call
+        assert lib.mumpy_adamw_gate_hyper(None, 1e-3, 0.9, 0.999, 1) < 0  # the message is sticky per thread: leave a known one first
+        stale = lib.mumpy_last_error()
+        rc = int(getattr(lib, entry)(*args))
+        err = lib.mumpy_last_error()
+        print(json.dumps({"rc": rc, "err": "" if (not rc or err == stale) else err.decode(errors="replace")}), flush=True)
+    print(json.dumps({"done": len(probes)}), flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(child())
+
+
+# ------------------------------------------------------------------------------------------------------------ CPU tests
+import pytest  # noqa: E402
+import torch  # noqa: E402
+
+from conftest import have_gpu, rel_err  # noqa: E402
+from weight_fill import seeded_randn  # noqa: E402
+
+needs_no_gpu = pytest.mark.skipif(have_gpu(), reason="with a device present a valid tuple of fake addresses would really launch")
+
+
+def _lib():
+    from mumpy_hip.lib import load_library
+    return load_library()
+
+
+def test_ext_header_binding_and_exports_agree():
+    """Every declaration of mumpy_hip_ext.h is exported by the shipped and the tuning library and bound in EXT_SIGNATURES with the
+    arity and the argument kinds of its C declaration; nothing is bound that the header lacks; no name lives in both headers; the
+    frozen surface keeps its version."""
+    from mumpy_hip.lib import ABI_VERSION, EXT_SIGNATURES, EXT_VERSION, SIGNATURES, tuning_library_path
+    ext, old = _decls("mumpy_hip_ext.h"), _decls("mumpy_hip.h")
+    assert set(LAUNCHING) | {"mumpy_ext_version", "mumpy_adamw_gate_hyper"} == set(ext)
+    assert not set(ext) & set(old) and not set(EXT_SIGNATURES) & set(SIGNATURES)
+    assert set(EXT_SIGNATURES) == set(ext) - {"mumpy_ext_version"}
+    assert sorted(n for n, a in ext.items() if a and a[-1].replace(" ", "") == "void*stream") == LAUNCHING
+    shipped, tuning = _lib(), ctypes.CDLL(tuning_library_path())
+    for name in ext:
+        assert hasattr(shipped, name) and hasattr(tuning, name), f"{name} declared in the header but not exported"
+
+    def kind(carg):
+        if "*" in carg:
+            return "ptr"
+        return {"int": "int", "int64_t": "i64", "float": "f32", "double": "f64"}[carg.rsplit(None, 1)[0].replace("const ", "").strip()]
+
+    def ckind(t):
+        if t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+            return "ptr"
+        return {ctypes.c_int: "int", ctypes.c_int64: "i64", ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
+
+    for name, args in EXT_SIGNATURES.items():
+        assert [ckind(t) for t in args] == [kind(a) for a in ext[name]], name
+    tuning.mumpy_ext_version.restype = ctypes.c_int
+    assert shipped.mumpy_ext_version() == tuning.mumpy_ext_version() == EXT_VERSION == 1
+    assert shipped.mumpy_abi_version() == ABI_VERSION == 2
+
+
+def test_adamw_gate_hyper_writes_the_doubles_it_was_given():
+    lib = _lib()
+    out = (ctypes.c_double * 4)(-1.0, -1.0, -1.0, -1.0)
+    lr, b1, b2 = 1e-3 / 3.0, 0.9, 0.999                                  # (doubles that fp32 cannot hold)
+    assert lib.mumpy_adamw_gate_hyper(out, lr, b1, b2, 7) == 0
+    assert list(out) == [lr, b1, b2, 7.0]
+    assert lib.mumpy_adamw_gate_hyper(None, lr, b1, b2, 7) == -3 and b"null" in lib.mumpy_last_error()
+    for bad in ((lr, b1, b2, 0), (lr, 1.0, b2, 1), (lr, b1, -0.1, 1)):
+        assert lib.mumpy_adamw_gate_hyper(out, *bad) == -1
+    assert list(out) == [lr, b1, b2, 7.0]                                # a refused call writes nothing
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep():
+    r = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=600)
+    lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+    results, pending, done = [], None, False
+    for ln in lines:
+        if "entry" in ln:
+            pending = ln
+        elif "rc" in ln:
+            results.append((pending["entry"], pending["mutation"], pending["expect"], ln["rc"], ln["err"]))
+            pending = None
+        elif "done" in ln:
+            done = True
+    end = "finished" if done and r.returncode == 0 else (
+        f"died (exit {r.returncode}) at entry {pending['entry']}, mutation {pending['mutation']}" if pending else
+        f"ended early (exit {r.returncode}): {r.stdout[-300:]} {r.stderr[-600:]}")
+    return results, end
+
+
+@needs_no_gpu
+@pytest.mark.parametrize("entry", LAUNCHING)
+def test_ext_entry_point_refuses_bad_arguments_before_launch(entry):
+    """A valid tuple passes every host check (rc > 0: the launch reached a runtime without a device); each mutation alone -- a NULL in
+    each pointer slot, n < 1, a misaligned buffer or gate, 0 or 9 statistics buffers or groups -- gives a negative code and a
+    message of that call's own."""
+    results, end = _sweep()
+    assert end == "finished", end
+    mine = [r for r in results if r[0] == entry]
+    assert mine and mine[0][1] == "valid"
+    assert sum(r[2] == "neg" for r in mine) >= 9
+    bad = [f"{m}: rc = {rc} ({err!r}), expected {expect}" for _, m, expect, rc, err in mine
+           if not (rc > 0 if expect == "pos" else (rc < 0 and bool(err)))]
+    assert not bad, "\n".join(bad)
+
+
+def _cpu_opts(count):
+    from mumpy_hip.train import FlatSGD
+    return {f"g{i}": FlatSGD(torch.nn.Linear(3, 2).parameters(), lr=0.1) for i in range(count)}
+
+
+def test_skip_nonfinite_argument_errors():
+    """Raised before anything touches the GPU (CPU optimizers and tensors here): optimizers that are not flat ones, more than 8
+    groups, a skip_nonfinite that is not a bool -- for UpdateGuard, GradClip and GraphedTrainStep."""
+    from mumpy_hip.train import GradClip, GraphedTrainStep, UpdateGuard
+    opts = _cpu_opts(9)
+    two = {k: opts[k] for k in ("g0", "g1")}
+    foreign = torch.optim.SGD(torch.nn.Linear(3, 2).parameters(), lr=0.1)
+    x = torch.zeros(1, 3)
+
+    def make(o, **kw):
+        return GraphedTrainStep(lambda t: t, o, x, x, **kw)
+
+    for bad in (1, 0, "yes", None, 1.0):
+        with pytest.raises(ValueError, match="skip_nonfinite"):
+            make(two, skip_nonfinite=bad)
+        with pytest.raises(ValueError, match="skip_nonfinite"):
+            GradClip(two, 1.0, skip_nonfinite=bad)
+    with pytest.raises(ValueError, match="9 optimizers"):
+        make(opts, skip_nonfinite=True)
+    with pytest.raises(ValueError, match="9 optimizers"):
+        make(opts, skip_nonfinite=True, clip_grad={"g0": 1.0})
+    with pytest.raises(ValueError, match="9 optimizers"):
+        GradClip(opts, None, skip_nonfinite=True)
+    with pytest.raises(ValueError, match="9 optimizers"):
+        UpdateGuard(opts, [object()])
+    with pytest.raises(ValueError, match="not a flat optimizer"):
+        make([foreign], skip_nonfinite=True)
+    with pytest.raises(ValueError, match="not a flat optimizer"):
+        GradClip([foreign], None, skip_nonfinite=True)
+    with pytest.raises(ValueError, match="not a flat optimizer"):
+        UpdateGuard([foreign], [object()])
+    with pytest.raises(ValueError, match="no optimizers"):
+        UpdateGuard([], [object()])
+    with pytest.raises(ValueError, match="0 clips"):
+        UpdateGuard(two, [])
+    with pytest.raises(ValueError, match="9 clips"):
+        UpdateGuard(two, [object()] * 9)
+    with pytest.raises(ValueError, match="must be a GradClip"):
+        UpdateGuard(two, [object()])
+    assert not any(hasattr(o, "hyper_dev") or o._guard is not None for o in opts.values())       # refused before anything was allocated
+
+
+# ------------------------------------------------------------------------------------------------------------ GPU, kernels
+KINDS = ["adamw", "sgd_m0", "sgd_m09", "sgd_nesterov", "rmsprop_m0", "rmsprop_m09"]
+FULL_SWEEP = 4096 * 256 * 4              # elements one grid-stride sweep of the capped update grid covers
+BIG = FULL_SWEEP + 1029                  # 4 195 333: one element past a full sweep + 1028, so a second sweep AND a 1-element tail
+
+
+def _randn(seed, n):
+    return torch.randn(n, generator=torch.Generator().manual_seed(seed), dtype=torch.float32)
+
+
+def _kind_case(kind, n, seed):
+    """-> (opt kind for the gate, host hyper tensor, [param, state...] CPU tensors, launcher(bufs, grad, hyper_dev, gate or None))."""
+    from mumpy_hip import ops
+    param = _randn(seed, n)
+    if kind == "adamw":
+        state = [_randn(seed + 1, n) * 0.1, _randn(seed + 2, n).square() * 0.01]
+        hyper = ops.adamw_hyper(3, 1e-3, grad_scale=0.5).clone()
+
+        def run(b, g, h, gate):
+            if gate is None:
+                ops.adamw_step_dev(b[0], g, b[1], b[2], h)
+            else:
+                ops.adamw_step_gated_dev(b[0], g, b[1], b[2], h, gate)
+        return "AdamW", hyper, [param] + state, run
+    if kind.startswith("sgd"):
+        mom = 0.0 if kind == "sgd_m0" else 0.9
+        nest = kind == "sgd_nesterov"
+        state = [] if mom == 0.0 else [_randn(seed + 1, n) * 0.1]
+        hyper = ops.sgd_hyper(1e-2, momentum=mom, weight_decay=1e-4, nesterov=nest, grad_scale=0.5).clone()
+
+        def run(b, g, h, gate):
+            buf = b[1] if len(b) > 1 else None
+            if gate is None:
+                ops.sgd_step_dev(b[0], g, buf, h, nest)
+            else:
+                ops.sgd_step_gated_dev(b[0], g, buf, h, gate, nest)
+        return "SGD", hyper, [param] + state, run
+    mom = 0.0 if kind == "rmsprop_m0" else 0.9
+    state = [_randn(seed + 1, n).square() * 0.01] + ([] if mom == 0.0 else [_randn(seed + 2, n) * 0.1])
+    hyper = ops.rmsprop_hyper(1e-2, weight_decay=1e-4, momentum=mom, grad_scale=0.5).clone()
+
+    def run(b, g, h, gate):
+        buf = b[2] if len(b) > 2 else None
+        if gate is None:
+            ops.rmsprop_step_dev(b[0], g, b[1], buf, h)
+        else:
+            ops.rmsprop_step_gated_dev(b[0], g, b[1], buf, h, gate)
+    return "RMSprop", hyper, [param] + state, run
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1, 5, 1027, BIG])
+@pytest.mark.parametrize("kind", KINDS)
+def test_hip_gated_update_with_a_clean_gate_is_bitwise_the_ungated_update(kind, n):
+    """3 gated steps behind a gate whose word 0 is 0 == 3 *_step_dev steps, bit for bit.  n: the scalar tail alone, one vector + tail,
+    several workgroups, one full grid-stride sweep of the capped grid + a second one + a 1-element tail."""
+    assert BIG == 4195333 and BIG % 4 == 1
+    _, hyper, bufs, run = _kind_case(kind, n, 900)
+    h = hyper.cuda()
+    gate = torch.zeros(8, dtype=torch.int32, device="cuda")
+    a, b = [t.cuda() for t in bufs], [t.cuda() for t in bufs]
+    for it in range(3):
+        g = _randn(910 + it, n).cuda()
+        run(a, g, h, gate)
+        run(b, g, h, None)
+    torch.cuda.synchronize()
+    assert not torch.equal(a[0].cpu(), bufs[0])                          # it did update
+    assert all(torch.equal(_bits(x), _bits(y)) for x, y in zip(a, b))
+    assert gate.tolist() == [0] * 8                                      # the update kernels only read the gate
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [5, BIG])
+@pytest.mark.parametrize("kind", KINDS)
+def test_hip_skipped_update_leaves_parameters_and_state_alone(kind, n):
+    """One gradient element NaN / +Inf / -Inf at index 0, at n - 1 (the scalar tail) and at 4 194 304 (the second sweep): after
+    measure -> gate -> gated update, param and every state buffer are bitwise what they were, the guard bands around them intact, the
+    gate reads skip = 1, skipped = 1, consecutive = 1.  A finite gradient whose square overflows (count 0, norm +Inf) is NOT skipped and
+    gives the bits of the ungated update."""
+    from guarded_alloc import Guard, same_bits
+    from mumpy_hip import ops
+    okind, hyper, bufs, run = _kind_case(kind, n, 920)
+    guard = Guard(0xFF, "cuda")
+    dev = [guard.tensor(t) for t in bufs]
+    grad_host = _randn(930, n)
+    grad = guard.tensor(grad_host)
+    h = guard.tensor(hyper)
+    part = guard.torch.empty(2 * ops.grad_norm_partials(n), device="cuda", dtype=torch.float32)
+    stats = guard.torch.empty(5, device="cuda", dtype=torch.float32)
+    gate = guard.torch.zeros(8, device="cuda", dtype=torch.int32)
+    applied = guard.torch.zeros(1, device="cuda", dtype=torch.int64)
+    applied.fill_(2)                         # two updates applied so far: the next one is the nominal step 3 the constants were staged for
+    raw = guard.tensor(ops.adamw_gate_hyper(3, 1e-3).clone())
+
+    def step(bufs_):
+        ops.grad_norm_partial(grad, part)
+        ops.grad_norm_finish([part], [n], [h], [okind], stats, None)
+        ops.update_gate([stats], gate, [h], [okind], applied, raw)
+        run(bufs_, grad, h, gate)
+        torch.cuda.synchronize()
+
+    where = [0, n - 1] + ([FULL_SWEEP] if n > FULL_SWEEP else [])
+    for value in (float("nan"), float("inf"), float("-inf")):
+        for i in where:
+            gate.zero_()
+            grad[i] = value
+            step(dev)
+            guard.check({}, inplace=[grad, gate])                        # bands intact; param, state, hyper, raw, applied bitwise unchanged
+            assert gate.tolist() == [1, 1, 1, 1, 1, 0, 0, 0], (value, i)
+            assert float(stats[2]) == 1.0 and applied.tolist() == [2]
+            grad[i] = grad_host[i]
+    assert all(same_bits(d.cpu(), t) for d, t in zip(dev, bufs)) and same_bits(h.cpu(), hyper)
+
+    grad[n - 1] = 3.0e38                     # finite, its square is not: count 0, norm +Inf -> the update runs, as it does today
+    twin = [t.cuda() for t in bufs]
+    run(twin, grad, h, None)
+    gate.zero_()
+    step(dev)
+    guard.check({}, inplace=[grad, gate, applied] + dev)
+    assert float(stats[2]) == 0.0 and float(stats[0]) == float("inf")
+    assert gate.tolist() == [0, 0, 0, 1, 0, 0, 0, 0] and applied.tolist() == [3]
+    assert all(same_bits(d, t) for d, t in zip(dev, twin)) and not same_bits(dev[0].cpu(), bufs[0])
+    assert same_bits(h.cpu(), hyper)                                     # applied == nominal: the staged constants were left alone
+
+
+# ------------------------------------------------------------------------------------------------------------ GPU, optimizers
+def _mlp():
+    return torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Tanh(), torch.nn.Linear(5, 3))
+
+
+def _flat(kind, params, lr):
+    from mumpy_hip.train import FlatAdamW, FlatRMSprop, FlatSGD
+    if kind == "adamw":
+        return FlatAdamW(params, lr=lr, weight_decay=1e-2)
+    if kind == "sgd":
+        return FlatSGD(params, lr=lr, weight_decay=1e-4, momentum=0.9)
+    return FlatRMSprop(params, lr=lr, weight_decay=1e-4)
+
+
+def _torch_opt(kind, params, lr):
+    if kind == "adamw":
+        return torch.optim.AdamW(params, lr=lr, weight_decay=1e-2, foreach=False)
+    if kind == "sgd":
+        return torch.optim.SGD(params, lr=lr, weight_decay=1e-4, momentum=0.9, foreach=False)
+    return torch.optim.RMSprop(params, lr=lr, weight_decay=1e-4, foreach=False)
+
+
+def _state_bufs(o):
+    names = ("exp_avg", "exp_avg_sq", "momentum_buffer", "square_avg")
+    return [getattr(o, k) for k in names if getattr(o, k, None) is not None]
+
+
+def _poisoned(g, value=float("nan"), index=3):
+    g = g.clone()
+    g[index] = value
+    return g
+
+
+@pytest.mark.gpu
+def test_adamw_bias_correction_follows_the_applied_step_count():
+    """Clean, clean, poisoned, clean, clean through GradClip(skip_nonfinite=True).step(): parameters and both moments match
+    torch.optim.AdamW stepped on the four clean gradients only; after the skip the two constants the gate launch rewrote equal
+    ops.adamw_hyper(t_eff)'s to within one fp32 ulp (double pow is good to a couple of double ulps, so only a rounding tie can move the
+    fp32 value) and the six others are bitwise the staged ones; the consecutive counter is back to 0."""
+    from mumpy_hip import ops
+    from mumpy_hip.train import GradClip
+    torch.manual_seed(21)
+    net = _mlp().cuda()
+    opt = _flat("adamw", net.parameters(), 1e-3)
+    n = opt.param.numel()
+    twin = torch.nn.Parameter(opt.param.detach().clone())                # the flat buffer as ONE torch parameter (AdamW is elementwise)
+    ref = _torch_opt("adamw", [twin], 1e-3)
+    clip = GradClip([opt], None, skip_nonfinite=True)
+    lrs = [1e-3, 8e-4, 6e-4, 4e-4, 2e-4]                                 # the schedule follows the updates attempted
+    for it in range(5):
+        g = seeded_randn(70 + it, n).cuda()
+        opt.lr = ref.param_groups[0]["lr"] = lrs[it]
+        opt.grad.copy_(_poisoned(g, float("inf") if it == 2 else g[3].item()))
+        clip.step()
+        r = clip.guard.read()
+        assert r["last_skipped"] == (it == 2) and r["consecutive"] == int(it == 2) and r["updates"] == it + 1
+        if it != 2:
+            twin.grad = g.clone()
+            ref.step()
+        if it >= 2:                                                      # from the skip on the applied count trails the nominal one
+            t_eff = it                                                   # updates applied, this one included: one fewer than it + 1
+            staged = ops.adamw_hyper(it + 1, lrs[it], weight_decay=1e-2)
+            got = opt.hyper_dev.cpu()
+            if it == 2:
+                assert torch.equal(_bits(got), _bits(staged))            # a skipped step leaves the staged constants alone
+            else:
+                want = ops.adamw_hyper(t_eff, lrs[it], weight_decay=1e-2)
+                moved = (_bits(staged) != _bits(want)).nonzero().flatten().tolist()
+                assert moved == [5, 6]                                   # step_size and bc2_sqrt are what depends on t
+                assert int((_bits(got)[5:7] - _bits(want)[5:7]).abs().max()) <= 1
+                keep = [0, 1, 2, 3, 4, 7]
+                assert torch.equal(_bits(got)[keep], _bits(staged)[keep])
+        else:
+            assert torch.equal(_bits(opt.hyper_dev), _bits(ops.adamw_hyper(it + 1, lrs[it], weight_decay=1e-2)))
+    assert clip.guard.read() == {"skipped": 1, "consecutive": 0, "longest": 1, "updates": 5, "last_skipped": False}
+    assert opt.steps == 5 and opt.applied_steps() == 4
+    assert float(opt.state_dict()["state"][0]["step"]) == 4.0 == float(ref.state_dict()["state"][0]["step"])
+    st = ref.state[twin]
+    assert rel_err(opt.param.cpu(), twin.detach().cpu()) < 1e-5
+    assert rel_err(opt.exp_avg.cpu(), st["exp_avg"].cpu()) < 1e-5
+    assert rel_err(opt.exp_avg_sq.cpu(), st["exp_avg_sq"].cpu()) < 1e-5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,guard_first", [("adamw", False), ("rmsprop", True)])
+def test_checkpoint_resume_after_a_skipped_update_is_bitwise_the_uninterrupted_run(kind, guard_first):
+    """Clean, poisoned, [state_dict], clean, clean.  The file holds the applied count (1) as torch's `step` and the attempted count
+    (2) beside it; fresh optimizers with a fresh guard (attached before or after load_state_dict) continue bitwise like the run that
+    was never interrupted."""
+    from mumpy_hip.train import GradClip
+    torch.manual_seed(22)
+    net_a, net_b = _mlp().cuda(), _mlp().cuda()
+    oa = _flat(kind, net_a.parameters(), 1e-3)
+    n = oa.param.numel()
+    for p in oa.params:                                  # 1 in the parameters' slots, 0 in the padding between them: a checkpoint
+        p.grad.fill_(1.0)                                # holds no state for the padding, so the test puts no gradient there
+    mask = oa.grad.clone()
+    oa.zero_grad()
+    assert 0 < int(mask.sum()) < n
+    grads = [seeded_randn(80 + it, n).cuda() * mask for it in range(4)]
+    grads[1] = _poisoned(grads[1])
+    clip_a = GradClip([oa], 0.5, skip_nonfinite=True)
+
+    def run(clip, o, its):
+        for it in its:
+            o.grad.copy_(grads[it])
+            clip.step()
+            o.zero_grad()
+
+    run(clip_a, oa, (0, 1))
+    sd = oa.state_dict()
+    assert sd["mumpy"]["steps"] == 2 and all(float(s["step"]) == 1.0 for s in sd["state"].values())
+    saved_param = oa.param.clone()
+    ob = _flat(kind, net_b.parameters(), 1e-3)
+    ob.param.copy_(saved_param)
+    if guard_first:
+        clip_b = GradClip([ob], 0.5, skip_nonfinite=True)
+        ob.load_state_dict(sd)
+    else:
+        ob.load_state_dict(sd)
+        assert ob.steps == 2 and ob.applied_steps() == 1                 # known on the host before any guard exists
+        clip_b = GradClip([ob], 0.5, skip_nonfinite=True)
+    assert ob.steps == 2 and ob.applied_steps() == 1
+    run(clip_a, oa, (2, 3))
+    run(clip_b, ob, (2, 3))
+    torch.cuda.synchronize()
+    assert oa.steps == ob.steps == 4 and oa.applied_steps() == ob.applied_steps() == 3
+    assert not torch.equal(oa.param, saved_param)
+    assert torch.equal(_bits(oa.param), _bits(ob.param))
+    assert all(torch.equal(_bits(x), _bits(y)) for x, y in zip(_state_bufs(oa), _state_bufs(ob)))
+    assert clip_b.guard.read()["skipped"] == 0 and clip_a.guard.read()["skipped"] == 1      # the statistics are not checkpointed
+
+
+# ------------------------------------------------------------------------------------------------------------ GPU, graphed
+def _decoder_case(kind, lr):
+    from weight_fill import fill_module_
+    from models.decoder.decoder import BaselineDecoder
+    dev = torch.device("cuda:0")
+    dec = fill_module_(BaselineDecoder(in_channels=64, features=[128] * 5)).eval().to(dev)
+    return dec, _flat(kind, dec.parameters(), lr)
+
+
+def _decoder_target():
+    return (seeded_randn(401, 2, 1, 224, 224) > 1.0).float().cuda()
+
+
+def _micro_batch(dec, x, target, k):
+    from mumpy_hip import ops
+    from mumpy_hip.autograd import baseline_decoder_train
+    logits = baseline_decoder_train(dec, x)
+    loss3, dl = ops.mask_loss(logits.detach(), target, loss_scale=1.0 / k)
+    logits.backward(dl)
+    return loss3
+
+
+def _with_one_inf(x):
+    x = x.clone()
+    x[1, 17, 3, 4] = float("inf")
+    return x
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,kind", [("single_graph", "adamw"), ("all_reduce", "sgd"), ("accumulate", "rmsprop")])
+def test_graphed_train_step_skips_a_non_finite_update_and_recovers(mode, kind):
+    """GraphedTrainStep(skip_nonfinite=True): one replayed micro-batch gets an x with a single Inf, so its gradients come out NaN
+    through the model (no buffer is poisoned by hand).  That replay changes neither parameters nor state; after two more clean updates
+    everything matches the eager loop that simply leaves the bad update out (under accumulation: the whole cycle, its clean
+    micro-batch included), the gradients are zero and the guard reports exactly one skip.  The rate changes with every update
+    ATTEMPTED, in both loops.  (That the skipped replay itself leaves parameters and state bitwise alone is the kernel test's and
+    test_two_clips_take_one_decision's business.)"""
+    from mumpy_hip.autograd import baseline_decoder_train
+    from mumpy_hip.state import bump_weights_epoch
+    from mumpy_hip.train import GraphedTrainStep
+    k = 2 if mode == "accumulate" else 1
+    warmup = 3
+    total = 7 if k == 1 else 10
+    bad = 4                                              # micro-batch index; k = 2: the first of the cycle (4, 5), update 2
+    target = _decoder_target()
+    xs = [seeded_randn(500 + i, 2, 64, 7, 7).cuda() for i in range(total)]
+    xs[:warmup] = [xs[0]] * warmup                       # the warm-up micro-batches replay the constructor's x
+    xs[bad] = _with_one_inf(xs[bad])
+    lrs = [1e-3, 1e-3, 1e-3, 5e-4, 2.5e-4, 1e-4, 5e-5]   # one rate per update attempted
+
+    dec_e, opt_e = _decoder_case(kind, lrs[0])           # eager reference, no guard: the bad cycle is left out altogether
+    opt_e.enable_device_hyper()
+    for i, x in enumerate(xs):
+        if i // k == bad // k:
+            continue
+        _micro_batch(dec_e, x, target, k)
+        if (i + 1) % k == 0:
+            opt_e.lr = lrs[i // k]
+            opt_e.stage_hyper()
+            opt_e.step_dev()
+            bump_weights_epoch()                         # (what opt.step() and GradClip.step() do: weight-derived caches are stale)
+            opt_e.zero_grad()
+
+    dec_g, opt_g = _decoder_case(kind, lrs[0])
+    gs = GraphedTrainStep(lambda xx: baseline_decoder_train(dec_g, xx), [opt_g], xs[0], target, warmup=warmup,
+                          all_reduce=(mode == "all_reduce"), accumulation_steps=k, skip_nonfinite=True)
+    assert (gs.graph_update is None) == (mode == "single_graph")
+    assert gs.guard is not None and len(gs.clips) == 1 and gs.clips[0].max_norm is None
+    for i in range(warmup, total):                       # (as in test_grad_clip: nothing but step() between the replays)
+        opt_g.lr = lrs[i // k]
+        gs.step(xs[i])
+    torch.cuda.synchronize()
+    attempted = total // k
+    assert gs.guard.read() == {"skipped": 1, "consecutive": 0, "longest": 1, "updates": attempted, "last_skipped": False}
+    assert opt_g.steps == attempted == opt_e.steps + 1 and opt_g.applied_steps() == opt_e.steps
+    assert bool(torch.isfinite(opt_g.param).all())
+    assert rel_err(opt_g.param.cpu(), opt_e.param.cpu()) < 1e-5
+    for a, b in zip(_state_bufs(opt_g), _state_bufs(opt_e)):
+        assert rel_err(a.cpu(), b.cpu()) < 1e-5
+    assert float(opt_g.grad.abs().max()) == 0.0
+
+
+@pytest.mark.gpu
+def test_two_clips_take_one_decision():
+    """Dict-form clip_grad over two optimizers, a non-finite gradient in one group only: the decoder's gradients are NaN, the second
+    optimizer's parameters are no part of the forward and its gradient stays zero and finite -- its own clip reports nothing, and
+    its weight decay alone would move it.  Neither group moves on the bad replay; both move on the clean one after it."""
+    from mumpy_hip.autograd import baseline_decoder_train
+    from mumpy_hip.train import GraphedTrainStep
+    target = _decoder_target()
+    x = seeded_randn(400, 2, 64, 7, 7).cuda()
+    dec, opt = _decoder_case("adamw", 1e-3)
+    torch.manual_seed(23)
+    aux = _flat("sgd", _mlp().cuda().parameters(), 1e-2)
+    opts = {"dec": opt, "aux": aux}
+    gs = GraphedTrainStep(lambda xx: baseline_decoder_train(dec, xx), opts, x, target, warmup=3, clip_grad={"dec": 1.0, "aux": 1.0},
+                          skip_nonfinite=True)
+    assert len(gs.clips) == 2 and set(gs.grad_stats) == {"dec", "aux"}
+    gs.step(x)
+    torch.cuda.synchronize()
+    snap = {k: [o.param.clone()] + [b.clone() for b in _state_bufs(o)] for k, o in opts.items()}
+    gs.step(_with_one_inf(x))
+    torch.cuda.synchronize()
+    assert gs.grad_stats["dec"][2].item() > 0 and gs.grad_stats["aux"].tolist()[:3] == [0.0, 1.0, 0.0]
+    assert gs.guard.read()["last_skipped"]
+    for k, o in opts.items():
+        assert all(torch.equal(_bits(a), _bits(b)) for a, b in zip([o.param] + _state_bufs(o), snap[k])), k
+    gs.step(x)
+    torch.cuda.synchronize()
+    assert gs.guard.read() == {"skipped": 1, "consecutive": 0, "longest": 1, "updates": 6, "last_skipped": False}
+    for k, o in opts.items():
+        assert not torch.equal(o.param, snap[k][0]), k
+        assert bool(torch.isfinite(o.param).all())
+
+
+@pytest.mark.gpu
+def test_skip_nonfinite_false_is_bitwise_the_step_without_the_argument():
+    from mumpy_hip.autograd import baseline_decoder_train
+    from mumpy_hip.train import GraphedTrainStep
+    target = _decoder_target()
+    x = seeded_randn(400, 2, 64, 7, 7).cuda()
+    runs = []
+    for kw in ({}, {"skip_nonfinite": False}):
+        dec, opt = _decoder_case("sgd", 1e-3)
+        gs = GraphedTrainStep(lambda xx, d=dec: baseline_decoder_train(d, xx), {"dec": opt}, x, target, warmup=3, **kw)
+        for _ in range(2):
+            gs.step()
+        torch.cuda.synchronize()
+        runs.append((gs, opt))
+    gs, opt = runs[1]
+    assert gs.guard is None and not gs.clips and gs.grad_stats is None and opt._guard is None
+    assert torch.equal(_bits(opt.param), _bits(runs[0][1].param))
+    assert torch.equal(_bits(opt.momentum_buffer), _bits(runs[0][1].momentum_buffer))

@@ -30,6 +30,7 @@ def main():
     ap.add_argument("--optim", choices=["adam", "sgd", "rmsprop"], default="adam", help="the reference's -optim / -optim_cnn (utils/utils.py:252-261)")
     ap.add_argument("--accumulation-steps", type=int, default=1, help="micro-batches per update (train.py:115-120); --steps counts micro-batches")
     ap.add_argument("--clip-grad", type=float, default=None, help="clip all groups by one global L2 norm (GradClip; after the all-reduce, on the averaged gradient)")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="skip the update of a step whose gradient is non-finite (UpdateGuard; on the device)")
     args = ap.parse_args()
     world, rank, local = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))
     backend = os.environ.get("MUMPY_BENCH_BACKEND", "nccl")
@@ -53,7 +54,7 @@ def main():
     opts = build_optimizers(enc, dec, lr_cnn=1e-6, lr=1e-5, lr_cva=1e-6, weight_decay=1e-4, weight_decay_cnn=1e-4,
                             optim=args.optim, optim_cnn=args.optim)
     k = args.accumulation_steps
-    clip = GradClip(opts, args.clip_grad) if args.clip_grad is not None and not args.graph else None
+    clip = GradClip(opts, args.clip_grad, skip_nonfinite=args.skip_nonfinite) if (args.clip_grad is not None or args.skip_nonfinite) and not args.graph else None
     micro = [0]                                                                   # micro-batches run (the reference's `iteration`)
     x = seeded_randn(100 + rank, args.batch, args.frames, 3, 224, 224).to(dev)
     target = (torch.rand(args.batch, 1, 224, 224, generator=torch.Generator().manual_seed(7 + rank)) < 0.1).float().to(dev)
@@ -78,7 +79,7 @@ def main():
         from mumpy_hip.train import GraphedTrainStep
         gs = GraphedTrainStep(lambda xx: decoder_train(dec, *encoder_train(enc, xx))[0], opts, x, target, warmup=max(args.warmup, 2),
                               all_reduce=world > 1 or os.environ.get("MUMPY_FORCE_DIST", "0") == "1", accumulation_steps=k,
-                              clip_grad=args.clip_grad)
+                              clip_grad=args.clip_grad, skip_nonfinite=args.skip_nonfinite)
 
         def step():
             micro[0] += 1
@@ -116,7 +117,8 @@ def main():
                           "optim": args.optim, "accumulation_steps": k, "graph": bool(args.graph), "micro_batch": args.batch,
                           "frames": args.frames, "math": args.math, "train_mode": bool(args.train_mode), "backend": backend, "loss": [round(float(v), 5) for v in loss3],
                           "replicas_identical_after_steps": same,
-                          **({"clip_grad": args.clip_grad, "total_norm": gstat[0], "coef": gstat[1]} if gstat else {})}))
+                          **({"clip_grad": args.clip_grad, "total_norm": gstat[0], "coef": gstat[1]} if gstat else {}),
+                          **({"skip_nonfinite": (gs.guard if args.graph else clip.guard).read()} if args.skip_nonfinite else {})}))
     if dist.is_initialized():
         dist.destroy_process_group()
 
