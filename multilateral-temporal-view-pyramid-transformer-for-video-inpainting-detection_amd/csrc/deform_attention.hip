@@ -27,9 +27,14 @@
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950; VGPRs + AGPRs / SGPRs / LDS per block / waves per SIMD; no scratch):
 //   win_attn_cross_kernel<false> 229 + 0 / 47 / 1,024 B / 2;   win_attn_cross_kernel<true> 194 + 0 / 50 / 1,024 B / 2 (no spills);
 //   win_attn_cross_mm16_kernel 160 + 0 / 46 / 3,072 B / 3;
-//   deform_attn_bwd_q_kernel 180 + 80 / 40 / 0 / 1;   deform_attn_bwd_kv_kernel 256 + 62 / 44 / 0 / 1
+//   deform_attn_bwd_q_kernel 180 + 80 / 40 / 0 / 1;   deform_attn_bwd_kv_kernel 256 + 62 / 44 / 0 / 1;
+//   deform_attn_bwd_q_bf16mm_kernel 147 + 0 / 71 / 1,024 B / 3;   deform_attn_bwd_kv_bf16mm_kernel 199 + 0 / 48 / 5,120 B / 2
+//
+// deform_attn_bwd_{q,kv}_bf16mm_kernel (mumpy_deform_attention_mm16_bwd, include/mumpy_hip_ext2.h; opt-in through the same switch on the
+// training tape) are the backward of win_attn_cross_mm16_kernel on the bf16 MFMA; their form, arithmetic and measurements are above them.
 #include <stdlib.h>
 #include "win_attn_unit.h"
+#include "../../include/mumpy_hip_ext2.h"
 
 namespace {
 
@@ -342,6 +347,235 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// The backward on the bf16 MFMA (mumpy_deform_attention_mm16_bwd): the pair of win_attn_cross_mm16_kernel, built like
+// win_attn_bwd_{q,kv}_bf16mm_kernel without the bias table, the mask, the dBias sum and the persistent walk.  Rows are window-major, so
+// the "token tables" are the row tables slot * pitch (4C bytes for q / dO, 8C for kv; padded slots 49..63 clamped to row 48), the same
+// for every unit.  Arithmetic, r(x) = bf16 rounding (nearest even), everything else fp32:
+//   S = scale (r(q) r(k)^T),  P = softmax(S) over the 49 real keys,  dP = r(dO) r(v)^T,  D = rowsum(P o dP),  dS = P o (dP - D)
+//   dV = r(P)^T r(dO),  dK = scale r(dS)^T r(q),  dQ[qw] = sum over m = 0 .. r-1, in that order, of scale r(dS_b2) r(k_b2), b2 = qw + m B1w
+// P and dS are exactly 0 on padded keys / queries BEFORE they are rounded, so the finite duplicates of row 48 are multiplied by 0.
+// Shipped form: the preferred one.  The q kernel's unit is (q window, head, 32-query tile), one wave each (tile = unit & 1, so the two
+// tiles of a (window, head) sit in neighbouring waves and share their K / V rows through L1 / L2): the wave rounds its Q tile once and
+// walks the r members b2 = qw + m B1w, reloading K, V, the permuted K and the dO tile of output window b2 / r, and adds each member's
+// scale * (dS K) to dQ in registers in the order m = 0 .. r-1.  dq comes out final: no per-member partials, no reduce launch, and the
+// order is fixed, so the result is deterministic.  With one query tile per wave both dP^T tiles are kept (not computed twice as in
+// the W-MSA q kernel) and the kernel still holds 2 waves per SIMD without scratch.  The q kernel writes the record {m, 1/l, D} of every
+// (b2, head) (192 floats; each tile's wave its own queries); the kv kernel's unit is (b2, head), one query tile at a time straight into
+// dV / dK.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): q kernel 147 VGPRs / 71 SGPRs / 1,024 B of LDS per block, 3 waves per
+// SIMD; kv kernel 199 / 48 / 5,120 B, 2 waves per SIMD; 0 AGPRs and no scratch in both (the fp32 pair: 180 + 80 and 256 + 62 registers,
+// 1 wave per SIMD).
+// Measured against the fp32 entry on the same input (tools/kernel_micro.py cva_attn_bwd16; profiles/bf16_cva_train.md): the eight
+// (B1w, r, C) launches of the B=2, T=5 training step, us on one MI355X, medians of 12 alternating replays of 20 captured calls; the
+// backward is the whole entry -- fp32: q kernel, kv kernel and the r - 1 add launches of ops.deform_attention_bwd; bf16: two launches:
+//   (B1w, r, C)     backward: fp32 -> bf16 MFMA      forward: fp32 -> bf16 MFMA
+//   (128, 1,  96)   25.2 -> 14.0 (1.80x)             6.9 ->  6.0
+//   (128, 5,  96)   65.7 -> 31.6 (2.08x)            22.0 -> 18.8
+//   ( 32, 1, 192)   24.7 -> 13.1 (1.89x)             6.8 ->  5.8
+//   ( 32, 5, 192)   38.6 -> 26.8 (1.44x)            21.0 -> 16.8
+//   (  8, 1, 384)   24.3 -> 12.8 (1.89x)             6.6 ->  5.7
+//   (  8, 5, 384)   34.3 -> 24.0 (1.43x)            21.7 -> 16.7
+//   (  2, 1, 768)   24.1 -> 12.7 (1.90x)             6.7 ->  5.8
+//   (  2, 5, 768)   32.1 -> 22.0 (1.46x)            21.6 -> 16.2
+// No shape is slower.  The graphed B=2 step, switch off -> on, alternating: 33.64 -> 33.53 ms under bf16 matrix math, 40.38 -> 40.28 ms
+// under fp32 (eight such launches per step).  Not measured: the two kernels separately (no kernel trace was taken), and the fallback form.
+struct CrossBwd16Args {
+    const float* q; const float* kv; const float* dout;
+    float* dq; float* dkv; float* stats;
+    int C, nH, r, B1w;
+    float scale;
+    int64_t units_q, units_kv;      // B1w nH 2 and B1w r nH
+};
+
+__global__ __launch_bounds__(256, 2) void deform_attn_bwd_q_bf16mm_kernel(CrossBwd16Args a) {
+    __shared__ __attribute__((aligned(16))) uint32_t row_k[4][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t u = (int64_t)blockIdx.x * 4 + wave;
+    if (u >= a.units_q) return;
+    const int it = (int)(u & 1);                                          // this wave's query tile
+    const int head = (int)((u >> 1) % a.nH);
+    const int64_t qw = (u >> 1) / a.nH;
+    const uint32_t rq = 4u * a.C, rk = 8u * a.C;                          // row pitches in bytes
+    uint32_t* tk = row_k[wave];
+    tk[lane] = (uint32_t)(lane < WT ? lane : WT - 1) * rk;
+    __builtin_amdgcn_wave_barrier();
+    const int qi = 32 * it + c;
+    const bool qvalid = qi < WT;
+    const uint32_t qoff = (uint32_t)(qvalid ? qi : WT - 1) * rq + 32u * h;
+    bf16x8 qf[2];
+    load_frag_bf16(qf, reinterpret_cast<const char*>(a.q + qw * WT * a.C + head * HD), qoff);
+    f32x16 dq = {};
+
+    for (int m = 0; m < a.r; ++m) {
+        const int64_t b2 = qw + (int64_t)m * a.B1w;                       // kv windows qw + m B1w pair with q window qw (deform:330)
+        const int64_t b1 = b2 / a.r;                                      // ... and take dO of output window b2 / r (deform:394-395)
+        const char* kb = reinterpret_cast<const char*>(a.kv + b2 * WT * 2 * a.C + head * HD);
+        const char* vb = kb + 4 * a.C;
+        const char* dob = reinterpret_cast<const char*>(a.dout + b1 * WT * a.C + head * HD);
+        bf16x8 kf[2][2], vkf[2][2], dof[2];                               // [tile][k-step]
+        bf16x8 kp[2][2];                                                  // K in the permuted key order of the dS operand, lane = channel
+#pragma unroll
+        for (int t = 0; t < 2; ++t) load_frag_bf16(kf[t], kb, tk[32 * t + c] + 32u * h);
+        load_frag_bf16(dof, dob, qoff);
+        __builtin_amdgcn_sched_barrier(0);   // fp32 rows are twice their fragments: a batch is rounded before the next is issued
+#pragma unroll
+        for (int t = 0; t < 2; ++t) load_frag_bf16(vkf[t], vb, tk[32 * t + c] + 32u * h);
+        load_perm_bf16(kp, kb, tk, c, h);
+        __builtin_amdgcn_sched_barrier(0);
+        float* st = a.stats + (b2 * a.nH + head) * 192;                   // {m[64], inv[64], D[64]} of the unit (b2, head)
+
+        f32x16 s[2] = {}, dp[2] = {};
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int jt = 0; jt < 2; ++jt) {
+                s[jt] = mfma16(kf[jt][ks], qf[ks], s[jt]);                // S^T = K Q^T
+                dp[jt] = mfma16(vkf[jt][ks], dof[ks], dp[jt]);            // dP^T = V dO^T
+            }
+        float mx, inv;
+        bias_softmax<false>(s, [&](int jt, int g) { return pad_bias(jt, g, h); }, nullptr, qi, h, a.scale, &mx, &inv);
+        float d = 0.f;
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (jt == 1 && r >= 9) continue;                          // P == 0 on padded keys
+                d += s[jt][r] * dp[jt][r];
+            }
+        d += __shfl_xor(d, 32);
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if (jt == 1 && r >= 9) { s[jt][r] = 0.f; continue; }
+                s[jt][r] = qvalid ? s[jt][r] * (dp[jt][r] - d) : 0.f;     // padded queries contribute nothing
+            }
+        if (h == 0 && qvalid) { st[qi] = mx; st[64 + qi] = inv; st[128 + qi] = d; }
+        f32x16 o = {};
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt)
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) o = mfma16(acc_frag(s[jt], ks), kp[jt][ks], o);   // dS K   (rows = queries, lanes = channels)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dq[r] += o[r] * a.scale;             // the members in the order m = 0 .. r-1
+        __builtin_amdgcn_sched_barrier(0);   // one member at a time: the next one's rows are not loaded over this one's live tiles
+    }
+    char* dqb = reinterpret_cast<char*>(a.dq + qw * WT * a.C + head * HD);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int i = 32 * it + (r & 3) + 8 * (r >> 2) + 4 * h;           // (the tile is a run-time value here: no static padding skip)
+        if (i < WT) *reinterpret_cast<float*>(dqb + ((uint32_t)i * rq + 4u * c)) = dq[r];
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void deform_attn_bwd_kv_bf16mm_kernel(CrossBwd16Args a) {
+    __shared__ __attribute__((aligned(16))) uint32_t row_q[4][64];
+    __shared__ __attribute__((aligned(16))) uint32_t row_k[4][64];
+    __shared__ __attribute__((aligned(16))) float stat_s[4][192];         // the unit's {m, 1/l, D}: one coalesced read, then 16-byte LDS reads
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const int64_t u = (int64_t)blockIdx.x * 4 + wave;
+    if (u >= a.units_kv) return;
+    const int head = (int)(u % a.nH);
+    const int64_t b2 = u / a.nH;
+    const int64_t qw = b2 % a.B1w, b1 = b2 / a.r;
+    const uint32_t rq = 4u * a.C, rk = 8u * a.C;
+    uint32_t* tq = row_q[wave];
+    uint32_t* tk = row_k[wave];
+    float* st = stat_s[wave];
+    {
+        const uint32_t slot = (uint32_t)(lane < WT ? lane : WT - 1);
+        tq[lane] = slot * rq;
+        tk[lane] = slot * rk;
+        // query slots 49..63 were never written by the q kernel: finite filler (their P / dS are forced to 0 below)
+        const float* sg = a.stats + u * 192;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) st[64 * k + lane] = lane < WT ? sg[64 * k + lane] : 0.f;
+    }
+    __builtin_amdgcn_wave_barrier();
+    const char* qb = reinterpret_cast<const char*>(a.q + qw * WT * a.C + head * HD);
+    const char* kb = reinterpret_cast<const char*>(a.kv + b2 * WT * 2 * a.C + head * HD);
+    const char* vb = kb + 4 * a.C;
+    const char* dob = reinterpret_cast<const char*>(a.dout + b1 * WT * a.C + head * HD);
+    bf16x8 qf[2][2], kf[2][2], vkf[2][2], dof[2][2];                      // [tile][k-step]
+    bf16x8 qp[2][2], dop[2][2];                                           // q / dO in the permuted query order of the P / dS operand
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        load_frag_bf16(qf[t], qb, tq[32 * t + c] + 32u * h);
+        load_frag_bf16(kf[t], kb, tk[32 * t + c] + 32u * h);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // fp32 rows are twice their fragments: a batch is rounded before the next is issued
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        load_frag_bf16(vkf[t], vb, tk[32 * t + c] + 32u * h);
+        load_frag_bf16(dof[t], dob, tq[32 * t + c] + 32u * h);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_perm_bf16(qp, qb, tq, c, h);
+    load_perm_bf16(dop, dob, tq, c, h);
+    __builtin_amdgcn_sched_barrier(0);
+    char* dkb = reinterpret_cast<char*>(a.dkv + b2 * WT * 2 * a.C + head * HD);
+    char* dvb = dkb + 4 * a.C;
+#pragma unroll
+    for (int jt = 0; jt < 2; ++jt) {
+        const int kj = 32 * jt + c;                                       // lane = key 32jt+c, accumulator rows = queries
+        f32x16 ov = {}, ok = {};
+        // one query tile at a time, straight into dV / dK: S and dP of one tile are live (32 registers), not of both
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            f32x16 s = {}, dp = {};
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                s = mfma16(qf[it][ks], kf[jt][ks], s);                    // S = Q K^T   (A = q rows, B = k rows)
+                dp = mfma16(dof[it][ks], vkf[jt][ks], dp);                // dP = dO V^T
+            }
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (it == 1 && g == 3) {                                  // queries 56..63: padding
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) { s[4 * g + e] = 0.f; dp[4 * g + e] = 0.f; }
+                    continue;
+                }
+                const int i0 = 32 * it + 8 * g + 4 * h;                   // this lane's 4 consecutive queries i0 .. i0+3
+                const f32x4 mv = *reinterpret_cast<const f32x4*>(st + i0);
+                const f32x4 iv = *reinterpret_cast<const f32x4*>(st + 64 + i0);
+                const f32x4 dv = *reinterpret_cast<const f32x4*>(st + 128 + i0);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool valid = (i0 + e < WT) && (kj < WT);
+                    const float pr = valid ? __expf(s[4 * g + e] * a.scale - mv[e]) * iv[e] : 0.f;   // the operation order of bias_softmax
+                    s[4 * g + e] = pr;                                                     // P
+                    dp[4 * g + e] = valid ? pr * (dp[4 * g + e] - dv[e]) : 0.f;            // dS
+                }
+            }
+#pragma unroll
+            for (int ks = 0; ks < 2; ++ks) {
+                ov = mfma16(acc_frag(s, ks), dop[it][ks], ov);            // dV = P^T dO   (sum over all 64 query slots)
+                ok = mfma16(acc_frag(dp, ks), qp[it][ks], ok);            // dK = dS^T Q
+            }
+            __builtin_amdgcn_sched_barrier(0);   // the tiles one after the other: interleaved, their accumulators are all live at once
+        }
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            if (acc_pad(jt, g)) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                if (acc_pad(jt, g, e)) continue;
+                const int j = acc_row(jt, g, e, h);
+                if (j < WT) {
+                    *reinterpret_cast<float*>(dvb + ((uint32_t)j * rk + 4u * c)) = ov[4 * g + e];
+                    *reinterpret_cast<float*>(dkb + ((uint32_t)j * rk + 4u * c)) = ok[4 * g + e] * a.scale;
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 }  // namespace
 
 // Which form a launch of the fp32 forward takes: bit 0 = split (win_attn_cross_kernel<true>: one unit on two waves), bit 1 = ring
@@ -420,5 +654,45 @@ extern "C" int mumpy_deform_attention_bwd(const float* q, const float* kv, const
     MUMPY_CHECK_LAUNCH("deform_attention_bwd(q)");
     hipLaunchKernelGGL(deform_attn_bwd_kv_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     MUMPY_CHECK_LAUNCH("deform_attention_bwd(kv)");
+    return 0;
+}
+
+// ---- include/mumpy_hip_ext2.h ----
+extern "C" int mumpy_ext2_version(void) { return MUMPY_EXT2_VERSION; }
+
+// 0 when (B1w, r, C) is a shape mumpy_deform_attention_mm16_bwd takes, else the code it refuses it with.  The range limits: the grids
+// (B1w r C/32 kv units, 2 B1w C/32 q units, four to a block) and the 32-bit byte offset of a row inside a kv window (49 rows of 8C bytes).
+static int mm16_bwd_shape(int64_t B1w, int r, int C) {
+    if (!(B1w > 0 && r >= 1 && C > 0 && C % HD == 0)) return MUMPY_EINVAL;
+    if (B1w >= (1ll << 31) || B1w * r >= (1ll << 31)) return MUMPY_ERANGE;
+    const int64_t nH = C / HD;
+    if ((B1w * r * nH + 3) / 4 >= (1ll << 31) || (B1w * nH * 2 + 3) / 4 >= (1ll << 31)) return MUMPY_ERANGE;
+    if ((int64_t)WT * 2 * C * 4 >= (1ll << 32)) return MUMPY_ERANGE;
+    return 0;
+}
+
+extern "C" int64_t mumpy_deform_attention_mm16_bwd_workspace_bytes(int64_t B1w, int r, int C) {
+    return mm16_bwd_shape(B1w, r, C) ? 0 : B1w * r * (C / HD) * 192 * (int64_t)sizeof(float);
+}
+
+extern "C" int mumpy_deform_attention_mm16_bwd(const float* q, const float* kv, const float* dout, float* dq, float* dkv,
+                                               void* workspace, int64_t workspace_bytes, int64_t B1w, int r, int C, float scale,
+                                               void* stream) {
+    MUMPY_REQUIRE(q && kv && dout && dq && dkv && workspace, MUMPY_ENULL, "deform_attention_mm16_bwd: null pointer");
+    MUMPY_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(dout) && aligned16(dq) && aligned16(dkv) && aligned16(workspace),
+                  MUMPY_EALIGN, "deform_attention_mm16_bwd: pointers must be 16-byte aligned");
+    const int bad = mm16_bwd_shape(B1w, r, C);
+    MUMPY_REQUIRE(bad != MUMPY_EINVAL, MUMPY_EINVAL, "deform_attention_mm16_bwd: bad shape (B1w=%lld, r=%d, C=%d)", (long long)B1w, r, C);
+    MUMPY_REQUIRE(bad == 0, MUMPY_ERANGE, "deform_attention_mm16_bwd: too many windows or C=%d too wide for 32-bit row offsets", C);
+    MUMPY_REQUIRE(workspace_bytes >= mumpy_deform_attention_mm16_bwd_workspace_bytes(B1w, r, C), MUMPY_EINVAL,
+                  "deform_attention_mm16_bwd: workspace too small");
+    CrossBwd16Args a;
+    a.q = q; a.kv = kv; a.dout = dout; a.dq = dq; a.dkv = dkv; a.stats = static_cast<float*>(workspace);
+    a.C = C; a.nH = C / HD; a.r = r; a.B1w = (int)B1w; a.scale = scale;
+    a.units_q = B1w * a.nH * 2; a.units_kv = B1w * r * a.nH;
+    hipLaunchKernelGGL(deform_attn_bwd_q_bf16mm_kernel, dim3((unsigned)((a.units_q + 3) / 4)), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH("deform_attention_mm16_bwd(q)");
+    hipLaunchKernelGGL(deform_attn_bwd_kv_bf16mm_kernel, dim3((unsigned)((a.units_kv + 3) / 4)), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH("deform_attention_mm16_bwd(kv)");
     return 0;
 }

@@ -569,7 +569,9 @@ class DeformSampleFn(torch.autograd.Function):
 
 class DeformAttentionFn(torch.autograd.Function):
     """softmax(q k^T * scale) v per kv window with the reference's pairing (q window = kv window mod B1, deform:330) and the sum
-    over adjacent r-tuples (deform:394-395), window form: q (B1,49,C), kv (B1*r,49,2C) -> (B1,49,C)."""
+    over adjacent r-tuples (deform:394-395), window form: q (B1,49,C), kv (B1*r,49,2C) -> (B1,49,C).  The arithmetic is
+    ops.cva_math() AT THE FORWARD: "bf16" runs the bf16-MFMA forward and, whatever the switch says by then, its own backward.  The
+    saved tensors are the fp32 q and kv either way."""
 
     @staticmethod
     def forward(ctx, q, kv, scale):
@@ -577,12 +579,13 @@ class DeformAttentionFn(torch.autograd.Function):
         r = kv.shape[0] // b1
         ctx.save_for_backward(q, kv)
         ctx.cfg = (r, scale)
-        return ops.deform_attention(q, kv, ops.pad_mask(q.device), b1, 7, 7, c, r, scale)
+        ctx.math = ops.cva_math()
+        return ops.deform_attention(q, kv, ops.pad_mask(q.device), b1, 7, 7, c, r, scale, math=ctx.math)
 
     @staticmethod
     def backward(ctx, dout):
         q, kv = ctx.saved_tensors
-        dq, dkv = ops.deform_attention_bwd(q, kv, dout.contiguous(), *ctx.cfg)
+        dq, dkv = ops.deform_attention_bwd(q, kv, dout.contiguous(), *ctx.cfg, math=ctx.math)
         return dq, dkv, None
 
 

@@ -126,6 +126,13 @@ EXT_SIGNATURES = {
 }
 EXT_VERSION = 1
 
+# ... and after that one was; mirrors include/mumpy_hip_ext2.h one to one (tests/test_cva_bf16mm_train.py checks it)
+EXT2_SIGNATURES = {
+    "mumpy_deform_attention_mm16_bwd_workspace_bytes": [c_l, c_i, c_i],
+    "mumpy_deform_attention_mm16_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_f],
+}
+EXT2_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -172,7 +179,11 @@ def load_library():
     lib.mumpy_ext_version.argtypes = []
     if lib.mumpy_ext_version() != EXT_VERSION:
         raise RuntimeError(f"{path}: extension version {lib.mumpy_ext_version()} != binding {EXT_VERSION}; rebuild")
-    for name, args in {**SIGNATURES, **EXT_SIGNATURES}.items():
+    lib.mumpy_ext2_version.restype = c_i
+    lib.mumpy_ext2_version.argtypes = []
+    if lib.mumpy_ext2_version() != EXT2_VERSION:
+        raise RuntimeError(f"{path}: second extension version {lib.mumpy_ext2_version()} != binding {EXT2_VERSION}; rebuild")
+    for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

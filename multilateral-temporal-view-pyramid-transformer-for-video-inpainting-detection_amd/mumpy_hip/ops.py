@@ -184,15 +184,19 @@ _CVA_MATH = _cva_math_from_env()         # read once, at import
 
 
 def set_cva_math(mode: str) -> None:
-    """Arithmetic of the cross-view attention module (SwinDAttention) in its inference forward.  "fp32" (default): the module's
-    existing routes.  "bf16": sample -> [k|v], the attention core and (in the cross block) proj_out -> combine run their bf16-MFMA
-    kernels (deform_sample_kv / deform_attention / deform_out_combine with math="bf16"): all tensors stay fp32 in memory, the matrix
-    operands are rounded to bf16 (nearest even) in registers or while staged, multiplied on v_mfma_f32_32x32x16_bf16 and accumulated
-    in fp32; the bilinear sum, softmax, bias adds and residual terms stay fp32.  Independent of set_matrix_math, set_storage and
-    set_attention_math: none of them touches it and it touches none of them.  The three ops never follow the switch by themselves
-    (their math= defaults to "fp32"), so the training tape, whose backward is fp32, keeps the fp32 forward.  The initial value is the
-    environment variable MUMPY_CVA_MATH, read when this module is imported.  Read at launch time: set it BEFORE a GraphedForward is
-    captured -- a captured graph keeps the kernels it was captured with."""
+    """Arithmetic of the cross-view attention module (SwinDAttention).  "fp32" (default): the module's existing routes.  "bf16":
+      * in the INFERENCE forward sample -> [k|v], the attention core and (in the cross block) proj_out -> combine run their bf16-MFMA
+        kernels (deform_sample_kv / deform_attention / deform_out_combine with math="bf16");
+      * on the TRAINING TAPE (autograd.DeformAttentionFn, so swin_dattention_train and the full training step) the attention core runs
+        deform_attention(..., math="bf16") in the forward and deform_attention_bwd(..., math="bf16") in the backward.  The mode is read
+        in the tape's forward and carried to its backward.  The tape's GEMMs (proj_q, k|v, proj_out) keep following set_matrix_math;
+        the offset network and the sampling are untouched.
+    All tensors stay fp32 in memory, the matrix operands are rounded to bf16 (nearest even) in registers or while staged, multiplied
+    on v_mfma_f32_32x32x16_bf16 and accumulated in fp32; the bilinear sum, softmax, bias adds and residual terms stay fp32.
+    Independent of set_matrix_math, set_storage and set_attention_math: none of them touches it and it touches none of them.  The ops
+    never follow the switch by themselves (their math= defaults to "fp32").  The initial value is the environment variable
+    MUMPY_CVA_MATH, read when this module is imported.  Read at launch time: set it BEFORE a GraphedForward or a graphed training step
+    is captured -- a captured graph keeps the kernels it was captured with."""
     global _CVA_MATH
     if mode not in ("fp32", "bf16"):
         raise ValueError(f"unknown cross-view attention math mode {mode!r}")
@@ -720,9 +724,10 @@ def deform_out_combine(o, wout, bout, x1, b, h, w, c, math="fp32"):
 
 
 def deform_attention(q, kv, padmask, b, h, w, c, r, scale, math="fp32"):
-    """Cross-view attention core + r-tuple sum.  math is explicit and defaults to "fp32" whatever set_cva_math says: the training tape
-    (DeformAttentionFn) calls this and has an fp32 backward.  math="bf16": q / k / v rounded to bf16 in registers, both products on the
-    bf16 MFMA, fp32 softmax and accumulation."""
+    """Cross-view attention core + r-tuple sum.  math is explicit and defaults to "fp32" whatever set_cva_math says: the callers that
+    follow the switch (the module's inference forward, and the training tape's DeformAttentionFn, which carries the mode to its
+    backward) pass it.  math="bf16": q / k / v rounded to bf16 in registers, both products on the bf16 MFMA, fp32 softmax and
+    accumulation; its backward is deform_attention_bwd(..., math="bf16")."""
     entry = _mm16("mumpy_deform_attention_fwd", math)
     q, kv = _chk(q, "q"), _chk(kv, "kv")
     b1w = b * (h // 7) * (w // 7)
@@ -1189,11 +1194,25 @@ def deform_sample_bwd(x2w, pos, dsampled):
     return dx2, part.view(b2 // nq, nq, 3, 49, 2).sum(0)
 
 
-def deform_attention_bwd(q, kv, dout, r, scale):
-    """window form: q (B1,49,C), kv (B1*r,49,2C), dout (B1,49,C) -> (dq (B1,49,C), dkv (B1*r,49,2C))."""
+def deform_attention_bwd(q, kv, dout, r, scale, math="fp32"):
+    """window form: q (B1,49,C), kv (B1*r,49,2C), dout (B1,49,C) -> (dq (B1,49,C), dkv (B1*r,49,2C)).  math: "fp32" (default; it does
+    NOT follow set_cva_math) or "bf16", the backward of deform_attention(..., math="bf16") (mumpy_deform_attention_mm16_bwd): the
+    operands rounded to bf16 in registers, every product on the bf16 MFMA, softmax / D / dS and accumulation in fp32, and dq summed
+    over its r kv windows on the device in a fixed order (no partial slices, no add launches)."""
+    if math not in ("fp32", "bf16"):
+        raise ValueError(f"unknown cross-view attention math mode {math!r}")
     q, kv, dout = _chk(q, "q"), _chk(kv, "kv"), _chk(dout, "dout")
     b1, _, c = q.shape
     b2 = b1 * r
+    if math == "bf16":
+        if kv.numel() != b2 * 49 * 2 * c or dout.numel() != q.numel():
+            raise RuntimeError("deform_attention_bwd: shape mismatch")
+        dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+        wsb = _ws_bytes(("cvabwd16", b1, r, c), "mumpy_deform_attention_mm16_bwd_workspace_bytes", b1, r, c)
+        ws = _ws(wsb, q.device)
+        _call("mumpy_deform_attention_mm16_bwd", _p(q), _p(kv), _p(dout), _p(dq), _p(dkv), _p(ws), wsb, b1, r, c, scale, _stream(),
+              work=5 * 153664.0 * b2 * (c // 32))
+        return dq, dkv
     part = torch.empty(b2, 49, c, device=q.device, dtype=torch.float32)
     dkv = torch.empty_like(kv)
     wsb = int(_lib().mumpy_deform_attention_bwd_workspace_bytes(b2, c))

@@ -16,7 +16,11 @@
                                                 variant's launches are issued).  Each variant's REPS launches are captured in one graph (an
                                                 eager loop of ~10 us kernels measures the launch rate, not the kernel); the graphs replay
                                                 alternately for ROUNDS rounds; prints median [min..max] us per launch and whether every
-                                                variant's output is bitwise the first one's"""
+                                                variant's output is bitwise the first one's
+  | kernel_micro.py cva_attn_bwd16 B1w r C        window form: the fp32 cross-view attention backward (deform_attention_bwd math="fp32",
+                                                its r - 1 add launches included) against the bf16-MFMA pair (math="bf16"), and the two
+                                                forwards, on the same input; each one's REPS calls captured in one graph, the four graphs
+                                                replayed alternately for ROUNDS rounds"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "multilateral-temporal-view-pyramid-transformer-for-video-inpainting-detection_amd")]
@@ -112,6 +116,41 @@ if op in ("winattn_ab", "cva_attn"):
     print(f"{op} {a}: " + ", ".join(f"{n} {sorted(t)[len(t) // 2]:.2f} us [{min(t):.2f}..{max(t):.2f}]" for n, t in times.items())
           + f"  (median of {rounds} alternating replays of {reps} captured launches); bitwise equal to {first}: "
           + ", ".join(f"{n} {bool(torch.equal(outs[n], outs[first]))}" for n in outs if n != first))
+    sys.exit(0)
+if op == "cva_attn_bwd16":
+    b1w, r, c = a
+    torch.manual_seed(0)
+    q = torch.randn(b1w, 49, c, device=dev); kv = torch.randn(b1w * r, 49, 2 * c, device=dev); dout = torch.randn(b1w, 49, c, device=dev)
+    pad = ops.pad_mask(dev)
+    run = {}
+    for m in ("fp32", "bf16"):
+        run["bwd " + m] = lambda m=m: ops.deform_attention_bwd(q, kv, dout, r, 32 ** -0.5, math=m)      # fp32: with its r - 1 adds
+        run["fwd " + m] = lambda m=m: ops.deform_attention(q, kv, pad, b1w, 7, 7, c, r, 32 ** -0.5, math=m)
+    rounds = int(os.environ.get("ROUNDS", "12"))
+    graphs = {}
+    for name, fn in run.items():
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                fn()
+        side.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name], stream=side):
+            for _ in range(reps):
+                fn()
+        graphs[name].replay()
+    torch.cuda.synchronize()
+    times = {name: [] for name in run}
+    for _ in range(rounds):
+        for name in run:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); graphs[name].replay(); e1.record(); torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    print(f"{op} {a}: " + ", ".join(f"{n} {med[n]:.2f} us [{min(t):.2f}..{max(t):.2f}]" for n, t in times.items())
+          + f"; bwd fp32/bf16 = {med['bwd fp32'] / med['bwd bf16']:.2f}, fwd fp32/bf16 = {med['fwd fp32'] / med['fwd bf16']:.2f}"
+          + f"  (median of {rounds} alternating replays of {reps} captured launches)")
     sys.exit(0)
 if op in ("winattn_mm16", "winattn_bwd16"):
     b, hs, w, c, shift = a
