@@ -1,6 +1,7 @@
 // abi.cpp — version / error plumbing of the C ABI (include/mumpy_hip.h).
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 #include "common.h"
 
 namespace mumpy {
@@ -36,6 +37,11 @@ static const char* format_route() {
         break;
     }
     default: snprintf(t, n, "none");
+    }
+    // the dual-output forward (z beside a = gelu(z)) / the backward whose dX carries gelu'(z): a marker behind the sibling's text
+    if (r.dual && r.family != Route::NONE) {
+        const size_t len = strlen(t);
+        snprintf(t + len, n - len, r.family == Route::XGEMM ? " gate=gelu" : " dual=z");
     }
     return t;
 }

@@ -148,12 +148,6 @@ __global__ __launch_bounds__(1024) void ln_param_reduce_kernel(const float* __re
     }
 }
 
-__device__ __forceinline__ float gelu_grad(float x) {          // d/dx [0.5 x (1 + erf(x / sqrt 2))]
-    const float cdf = 0.5f * (1.0f + erf_fast(x * 0.70710678118654752440f));
-    const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
-    return cdf + x * pdf;
-}
-
 __global__ __launch_bounds__(256) void gelu_fwd_kernel(const f32x4* __restrict__ x, f32x4* __restrict__ y, int64_t n4) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const f32x4 v = x[i];

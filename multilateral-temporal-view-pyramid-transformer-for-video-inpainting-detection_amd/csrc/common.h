@@ -43,6 +43,7 @@ struct Route {
     uint8_t passes = 0;      // ws / ws64 / ws16: epilogue passes per chunk (the P of the instantiation)
     uint8_t ln = 0;          // ws: 0 none, 1 LayerNorm producer, 2 consumer
     uint8_t reduce = R_NONE; // xgemm
+    uint8_t dual = 0;        // forward: the pre-activation is stored as well (mumpy_linear_gelu_dual_fwd); xgemm: dX is gated by gelu'(z)
     int ks = 1;              // tiled: split-K factor actually launched
     struct { int wt, ks; } prod[2] = {{0, 0}, {0, 0}};      // xgemm: wave tile and split of the dX (0) and dW (1) products; wt 0 = not run
 };
@@ -172,6 +173,12 @@ __device__ __forceinline__ float erf_fast(float x) {
 }
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752440f)); }
+
+__device__ __forceinline__ float gelu_grad(float x) {          // d/dx [0.5 x (1 + erf(x / sqrt 2))]
+    const float cdf = 0.5f * (1.0f + erf_fast(x * 0.70710678118654752440f));
+    const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
+    return cdf + x * pdf;
+}
 
 // raster token of in-window position p of window (wy,wx) on a (Hs,W) grid after roll(-shift)
 // (swin:54-66 + 273): shifted[y][x] = src[(y+shift)%Hs][(x+shift)%W].

@@ -43,6 +43,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "../../include/mumpy_hip_ext2.h"
 #include "gemm_ws.h"
 #include "gemm_ws64.h"
 using namespace mumpy;
@@ -118,7 +119,9 @@ __device__ __forceinline__ ConvTap conv_tap(const ConvGeom& cg, int k0) {
 // row: 5-15 % of a short-K tile.)  ksplit > 1: raw partial sums -> slab[ks][M][N]; bias/act/residual happen in
 // splitk_reduce_kernel.
 // OUT16: y is bf16 (config 3's activation storage); bias / residual / partial slabs stay fp32.
-template <int TM, int TN, int WM, int WN, bool OUT16 = false>
+// DUAL (mumpy_linear_gelu_dual_fwd: fc1 of an MLP on the training tape): the pre-activation z = acc + bias is stored as well, fp32,
+// to the buffer that travels in the `residual` argument (such a launch has no residual; the kernels' signature stays as it is).
+template <int TM, int TN, int WM, int WN, bool OUT16 = false, bool DUAL = false>
 __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][TN], int64_t m0, int n0, int wm, int wn, int c, int h,
                                            int64_t M, int N, const float* __restrict__ bias, const float* residual,
                                            float* Y, int act, int ksplit, int ks, float* slab) {
@@ -158,8 +161,9 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][TN], int64_t 
                 if (row + 4 * h >= rows_left) continue;
                 const uint32_t off = (uint32_t)row * nb + lane_off + 128u * j;
                 float v = acc[i][j][r] + bv;
+                if (DUAL) *reinterpret_cast<float*>(const_cast<char*>(Rw) + off) = v;
                 if (act == MUMPY_ACT_GELU) v = gelu_erf(v);
-                if (Rw) v += *reinterpret_cast<const float*>(Rw + off);
+                if (!DUAL && Rw) v += *reinterpret_cast<const float*>(Rw + off);
                 if (OUT16) *reinterpret_cast<__bf16*>(Yw + (off >> 1)) = (__bf16)v;      // round to nearest even
                 else *reinterpret_cast<float*>(Yw + off) = v;
             }
@@ -168,7 +172,7 @@ __device__ __forceinline__ void store_tile(const f32x16 (&acc)[TM][TN], int64_t 
 
 // PIPE: double-buffer the MFMA fragments in registers (read chunk k+1 while chunk k is in the MFMAs).  PIPE = false
 // (with GLDS) is the big-wave-tile variant: one fragment set, the DMA runs two chunks ahead, two barriers per chunk.
-template <int BM, int BN, int WM, int WN, bool CONV, bool GLDS, bool PIPE = true>
+template <int BM, int BN, int WM, int WN, bool CONV, bool GLDS, bool PIPE = true, bool DUAL = false>
 __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM * BN > 64 * 64) ? 2 : (CONV ? 3 : 4)) void linear_kernel(const float* __restrict__ X, const float* __restrict__ Wt,
                                                      const float* __restrict__ bias, const float* residual,
                                                      float* Y, int64_t M, int N, int K, int act, unsigned gn,
@@ -389,7 +393,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM * BN > 64 * 64) ? 2
     }
     if (kc < nk) mma(afA, bfA);                                   // odd last chunk: its fragments are already in set A
     }
-    store_tile<TM, TN, WM, WN>(acc, m0, n0, wm, wn, c, h, M, N, bias, residual, Y, act, ksplit, ks, slab);
+    store_tile<TM, TN, WM, WN, false, DUAL>(acc, m0, n0, wm, wn, c, h, M, N, bias, residual, Y, act, ksplit, ks, slab);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -439,7 +443,7 @@ constexpr int LDH = 20;
 
 // IN16: x and W are bf16 in memory (bf16 STORAGE, config 3 as written: the staging traffic halves and there is nothing to
 // convert); OUT16: y is written as bf16.  Both only with NP == 1 and dense rows.
-template <int BM, int BN, int WM, int WN, bool CONV, int NP = 1, int NBUF = 2, bool IN16 = false, bool OUT16 = false>
+template <int BM, int BN, int WM, int WN, bool CONV, int NP = 1, int NBUF = 2, bool IN16 = false, bool OUT16 = false, bool DUAL = false>
 __global__ __launch_bounds__(256, 2) void linear_bf16_kernel(const float* __restrict__ X, const float* __restrict__ Wt,
                                                             const float* __restrict__ bias, const float* residual,
                                                             float* Y, int64_t M, int N, int K, int act, unsigned gn,
@@ -628,10 +632,12 @@ __global__ __launch_bounds__(256, 2) void linear_bf16_kernel(const float* __rest
         fread(0);
         mma();
     }
-    store_tile<TM, TN, WM, WN, OUT16>(acc, m0, n0, wm, wn, c, h, M, N, bias, residual, Y, act, ksplit, ks, slab);
+    store_tile<TM, TN, WM, WN, OUT16, DUAL>(acc, m0, n0, wm, wn, c, h, M, N, bias, residual, Y, act, ksplit, ks, slab);
 }
 
 // split-K combine: y = act(sum_s slab[s] + bias) + residual, slices summed in fixed order (bitwise reproducible)
+// DUAL: no residual; the buffer in its place receives the pre-activation (store_tile)
+template <bool DUAL = false>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slab, const float* __restrict__ bias,
                                                             const float* residual, float* Y, int64_t MN4, int N,
                                                             int ksplit, int act) {
@@ -639,11 +645,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         f32x4 v = ordered_sum(reinterpret_cast<const f32x4*>(slab)[i], reinterpret_cast<const f32x4*>(slab) + MN4 + i, MN4, ksplit - 1);
         const int n = (int)((i * 4) % N);
         if (bias) v += *reinterpret_cast<const f32x4*>(bias + n);
+        if (DUAL) reinterpret_cast<f32x4*>(const_cast<float*>(residual))[i] = v;
         if (act == MUMPY_ACT_GELU) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
         }
-        if (residual) v += reinterpret_cast<const f32x4*>(residual)[i];
+        if (!DUAL && residual) v += reinterpret_cast<const f32x4*>(residual)[i];
         reinterpret_cast<f32x4*>(Y)[i] = v;
     }
 }
@@ -778,6 +785,7 @@ struct LinearArgs {
     int kseg = 0, kstride = 0;              // rows mode with a segmented contraction index (ConvGeom)
     const ConvGeom* conv = nullptr;         // implicit-GEMM convolution
     const gemm_ws::LnArgs* ln = nullptr;    // LayerNorm folding (mumpy_linear_lnx_fwd)
+    float* z = nullptr;                     // dual output (mumpy_linear_gelu_dual_fwd): the pre-activation; no residual then
 };
 
 // What every tiled kernel is launched with.
@@ -822,6 +830,17 @@ void launch_tiled_fp32(int tile, bool conv, bool glds, const TiledArgs& t) {
     });
 }
 
+// the dual-output variants (dense rows, GELU, no residual; t.residual carries z): the tiles the planner hands out -- 0, 2 and 3;
+// 1 and the LDS-DMA staging of 0 / 2 exist for tuning runs only and are not built in this form
+void launch_tiled_dual(int tile, bool bf16, const TiledArgs& t) {
+    if (bf16) {
+        if (tile == 0) launch_tiled(linear_bf16_kernel<128, 128, 64, 64, false, 1, 2, false, false, true>, 256, t);
+        else launch_tiled(linear_bf16_kernel<64, 64, 32, 32, false, 1, 2, false, false, true>, 256, t);
+    } else if (tile == 3) launch_tiled(linear_kernel<128, 128, 64, 64, false, true, false, true>, 256, t);
+    else if (tile == 0) launch_tiled(linear_kernel<128, 128, 64, 32, false, false, true, true>, 512, t);
+    else launch_tiled(linear_kernel<64, 64, 32, 32, false, false, true, true>, 256, t);
+}
+
 // bf16 products of NP pieces per operand on the 128x128 (wide; one LDS buffer when NP > 1) or the 64x64 tile.
 // flag: a convolution, or -- IN16, bf16 storage, dense rows only -- a bf16 output.
 template <int NP, bool IN16 = false>
@@ -864,7 +883,7 @@ int launch_linear(const LinearArgs& a) {
         // short-K shapes (<= 12 chunks) in between; deeper K wants the tiled kernels' split-K, a GELU epilogue is bound by the
         // epilogue waves (two matrix waves per SIMD leave them even fewer issue slots).  =0 disables it, =2 forces it.
         static const int ws64_mode = tune_int("MUMPY_GEMM_WS64", 1);
-        if (!how && !conv && ws64_mode) {
+        if (!how && !conv && ws64_mode && !a.z) {       // (a GELU launch gets here only when forced: no dual form of it)
             const int64_t t64 = ((M + 63) / 64) * ((N + 63) / 64);
             const double r64 = (double)t64 / (2.0 * num_cu);
             const bool fits = ws64_mode == 2 || (act != MUMPY_ACT_GELU && nk <= 32 && t64 >= 64 && (r64 <= 1.0 || r64 >= 2.5 || nk <= 12));
@@ -876,7 +895,7 @@ int launch_linear(const LinearArgs& a) {
         }
         if (how) {
             if (int rc = gemm_ws::launch(a.x, a.W, a.bias, a.residual, a.y, M, N, K, act, num_cu, a.s, ws, ws_bytes, how == 2 ? 1 : 0, nullptr,
-                                         a.ws_clean, conv ? &cvd : nullptr, a.ln)) return rc;
+                                         a.ws_clean, conv ? &cvd : nullptr, a.ln, a.z)) return rc;
             MUMPY_CHECK_LAUNCH("linear(ws)");
             return 0;
         }
@@ -893,16 +912,19 @@ int launch_linear(const LinearArgs& a) {
         if (p.tile == 3) p.tile = 0;
         if (p.tile == 1) { p.tile = 2; p.gn = (unsigned)((N + 63) / 64); }
     }
+    if (a.z && p.tile == 1) { p.tile = 2; p.gn = (unsigned)((N + 63) / 64); }      // (forced only; see launch_tiled_dual)
     const int64_t grid = p.gm * p.gn * p.ksplit;
     MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "linear: too many tiles");
     static const bool use_glds = tune_int("MUMPY_GEMM_GLDS", 0) != 0;
     const bool wide = (p.tile == 0 || p.tile == 3);
-    const TiledArgs t{a.x, a.W, a.bias, a.residual, a.y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg, grid, a.s};
+    const TiledArgs t{a.x, a.W, a.bias, a.z ? a.z : a.residual, a.y, M, N, K, act, p.gn, p.ksplit, ws, rpb, bstride, cg, grid, a.s};
     g_route = Route{};
     g_route.family = Route::TILED; g_route.tile = (uint8_t)p.tile; g_route.ks = p.ksplit;
     g_route.np = math_x2 ? 2 : math_x3 ? 3 : math_bf16 ? 1 : 0;
     g_route.addr = conv ? Route::CONV : a.kseg ? Route::KSEG : rpb < M ? Route::ROWS : Route::DENSE;
-    if (math_x2) launch_tiled_bf16<2>(wide, conv != nullptr, t);
+    g_route.dual = a.z ? 1 : 0;
+    if (a.z) launch_tiled_dual(p.tile, math_bf16, t);
+    else if (math_x2) launch_tiled_bf16<2>(wide, conv != nullptr, t);
     else if (math_x3) launch_tiled_bf16<3>(wide, conv != nullptr, t);
     else if (math_bf16) launch_tiled_bf16<1>(wide, conv != nullptr, t);
     else launch_tiled_fp32(p.tile, conv != nullptr, use_glds, t);
@@ -911,8 +933,9 @@ int launch_linear(const LinearArgs& a) {
         const int64_t mn4 = M * N / 4;
         int64_t g = (mn4 + 255) / 256;
         if (g > 2048) g = 2048;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)g), dim3(256), 0, a.s, ws, a.bias, a.residual, a.y, mn4, N,
-                           p.ksplit, act);
+        if (a.z) hipLaunchKernelGGL(splitk_reduce_kernel<true>, dim3((unsigned)g), dim3(256), 0, a.s, ws, a.bias, a.z, a.y, mn4, N, p.ksplit, act);
+        else hipLaunchKernelGGL(splitk_reduce_kernel<false>, dim3((unsigned)g), dim3(256), 0, a.s, ws, a.bias, a.residual, a.y, mn4, N,
+                                p.ksplit, act);
         MUMPY_CHECK_LAUNCH("linear(split-K reduce)");
     }
     return 0;
@@ -1031,6 +1054,27 @@ extern "C" int mumpy_linear_wsz_fwd(const float* x, const float* W, const float*
     LinearArgs a = linear_args(x, W, bias, residual, y, M, N, K, act, workspace, workspace_bytes, stream);
     a.ws_clean = true;
     return launch_linear(a);
+}
+
+// ---- fc1 of an MLP on the training tape: z = x W^T + b AND a = gelu(z) from one launch (include/mumpy_hip_ext2.h) -------------
+// The same plan, kernels and epilogue arithmetic as mumpy_linear_wsz_fwd with act = GELU | math -- the epilogue stores its value
+// once more, before the activation -- so `a` is bit for bit what that launch writes and z what the launch without GELU writes.
+extern "C" int mumpy_linear_gelu_dual_fwd(const float* x, const float* W, const float* bias, float* z, float* a, int64_t M, int N,
+                                          int K, int math, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (M == 0) return 0;
+    MUMPY_REQUIRE(math == 0 || math == MUMPY_MATH_BF16, MUMPY_EINVAL,
+                  "linear_gelu_dual: math is 0 or MUMPY_MATH_BF16 (the split-precision modes have no dual-output form; got 0x%x)", math);
+    MUMPY_REQUIRE(z, MUMPY_ENULL, "linear_gelu_dual: null pointer");
+    if (int rc = check_linear_args("linear_gelu_dual", x, W, z, a, M, N, K, MUMPY_ACT_GELU | math)) return rc;
+    MUMPY_REQUIRE(z != a, MUMPY_EINVAL, "linear_gelu_dual: z and a must be two buffers");
+    MUMPY_REQUIRE(workspace_bytes >= 0, MUMPY_EINVAL, "linear_gelu_dual: workspace_bytes must not be negative");
+    MUMPY_REQUIRE(aligned16(workspace) && aligned16(bias), MUMPY_EALIGN, "linear_gelu_dual: bias and workspace must be 16-byte aligned");
+    MUMPY_REQUIRE(!workspace || workspace_bytes >= mumpy_linear_workspace_bytes(M, N, K), MUMPY_EINVAL,
+                  "linear_gelu_dual: workspace too small (mumpy_linear_workspace_bytes)");
+    LinearArgs la = linear_args(x, W, bias, nullptr, a, M, N, K, MUMPY_ACT_GELU | math, workspace, workspace_bytes, stream);
+    la.ws_clean = true;
+    la.z = z;
+    return launch_linear(la);
 }
 
 // Sticky status of a kept workspace (blocking: copies one word back).  0 = fine; b + 1 = the owner of a split tile gave up waiting

@@ -18,6 +18,7 @@
 // p + (r - ph) W + (s - pw) or zeros -- decided per staged 16-byte piece by two magic-number divisions; decoder.py:9,24-31).
 #include <type_traits>
 #include "common.h"
+#include "../../include/mumpy_hip_ext2.h"
 #include "colsum.h"      // col_sum_partial_kernel, partial_reduce_kernel
 using namespace mumpy;
 
@@ -50,6 +51,9 @@ struct XArgs {
     // zeros otherwise; the tap's product lands at column offset tap * C of the (Cout, kh, kw, Cin) gradient
     int cvH, cvW, cv_kw, cv_ph, cv_pw;
     unsigned cv_mhw, cv_shw, cv_mw, cv_sw;      // p / (H W) and rem / W as mulhi + shift
+    // GATE only (the dX product of an fc2 whose input is a = gelu(z), mumpy_linear_gelu_bwd): z, [R][ldo] like out; an unsplit
+    // product stores acc * gelu'(z), a split one leaves the gate to its reduce.  Last, so that no other field moves.
+    const float* gate;
 };
 
 // ---- bf16 OPERAND mode (MUMPY_MATH_BF16 OR-ed into `accumulate`; config 5's arithmetic, train.py:94-138 under bf16) --------
@@ -68,8 +72,9 @@ struct XArgs {
 // the slow one.  What the two forms share is written once -- the index preamble, the loads with their bounds and border tests, the
 // software pipeline, the bias-gradient finish and the choice of destination; the LDS images, the transposing stager, the
 // fragment reads, the MFMA and the store permutation are each form's own.
-template <bool BF16, int WT, bool A_T, bool CONV = false>
+template <bool BF16, int WT, bool A_T, bool CONV = false, bool GATE = false>
 __global__ __launch_bounds__(256) void xgemm_kernel(XArgs a) {
+    static_assert(!GATE || (!A_T && !CONV), "the GELU gate belongs to a dX product");
     constexpr int BT = 2 * WT, NB = WT / 32;
     constexpr int LDN = BK + 4;                  // fp32 [row][k] image: 36-dword rows (conflict-free ds_read_b128 down the rows)
     constexpr int LDT = BT + 4;                  // fp32 [k][col] image
@@ -266,6 +271,29 @@ __global__ __launch_bounds__(256) void xgemm_kernel(XArgs a) {
     if (a.ks > 1) { dst = a.slabs + ((int64_t)z * gridDim.z + tap) * a.R * a.C; ldd = a.C; }      // [split][tap][R][C]
     else { dst = a.out + (int64_t)tap * a.C; ldd = a.ldo; }
     const bool accum = a.ks == 1 && a.accum;
+    if (GATE && a.ks == 1) {
+        // dz = product o gelu'(z), on the accumulators.  z has out's shape and pitch, so the bounds of the stores below hold for it.
+        // All the loads of the tile first: they depend on nothing, while inside the store loops each would have to wait behind the
+        // store before it (out may alias z as far as the compiler knows).  Accumulator (i, j)[r] is wave row 32 i + rho; its column
+        // is 32 j + c in the bf16 form and 2 c + j / c in the fp32 form (see the stores).
+        float g[NB][NB][16];
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = row0 + wm * WT + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int col = col0 + wn * WT + (BF16 ? 32 * j + c : NB == 2 ? 2 * c + j : c);
+                    g[i][j][r] = (row < a.R && col < a.C) ? a.gate[(int64_t)row * a.ldo + col] : 0.f;
+                }
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] *= gelu_grad(g[i][j][r]);
+    }
     if constexpr (!BF16) {
         // accumulator (i, j)[r] -> row rho = (r&3) + 8 (r>>2) + 4 h, column gamma = c of the 32x32 block; block (i, j) holds
         // wave rows 32 i + rho (A row-major) or 2 rho + i (A contraction-slow), wave columns 2 gamma + j (NB == 2) / gamma
@@ -322,13 +350,20 @@ __device__ __forceinline__ void reduce_rowsum(const RowSumArgs& rs, int ks, unsi
 
 // up to two reductions in ONE launch (the dX and the dW product of a Linear backward, both split): blocks [0, j0.blocks) take job 0,
 // the rest job 1; a job with blocks == 0 does not exist.  Saves a launch per nn.Linear of the training step (~250 of them).
+// GATE: job 0 is the dX product of mumpy_linear_gelu_bwd that ran split -- its sum, once complete, is multiplied by gelu'(z)
+// (gate: z, the shape of job 0's out)
 struct ReduceJob { const f32x4* slabs; f32x4* out; int64_t n4; int ks, accum; unsigned blocks; };
-__global__ __launch_bounds__(256) void xgemm_reduce_kernel(ReduceJob j0, ReduceJob j1, RowSumArgs rs) {
+template <bool GATE = false>
+__global__ __launch_bounds__(256) void xgemm_reduce_kernel(ReduceJob j0, ReduceJob j1, RowSumArgs rs, const f32x4* gate) {
     const bool second = blockIdx.x >= j0.blocks;
     const ReduceJob& j = second ? j1 : j0;
     const unsigned bid = second ? blockIdx.x - j0.blocks : blockIdx.x;
     for (int64_t i = (int64_t)bid * 256 + threadIdx.x; i < j.n4; i += (int64_t)j.blocks * 256) {
         f32x4 s = ordered_sum(j.slabs[i], j.slabs + j.n4 + i, j.n4, j.ks - 1);
+        if (GATE && !second) {
+            const f32x4 g = gate[i];
+            s = f32x4{s.x * gelu_grad(g.x), s.y * gelu_grad(g.y), s.z * gelu_grad(g.z), s.w * gelu_grad(g.w)};
+        }
         if (j.accum) s += j.out[i];
         j.out[i] = s;
     }
@@ -468,8 +503,12 @@ void launch_product(bool bf16, bool a_t, bool conv, const XPlan& p, unsigned tap
          {xgemm_kernel<false, 64, false>, xgemm_kernel<false, 64, true>, xgemm_kernel<false, 64, true, true>}},
         {{xgemm_kernel<true, 32, false>, xgemm_kernel<true, 32, true>, xgemm_kernel<true, 32, true, true>},
          {xgemm_kernel<true, 64, false>, xgemm_kernel<true, 64, true>, xgemm_kernel<true, 64, true, true>}}};
+    // a.gate: the dX product of mumpy_linear_gelu_bwd (never a_t, never a convolution)
+    static const Kernel gated[2][2] = {{xgemm_kernel<false, 32, false, false, true>, xgemm_kernel<false, 64, false, false, true>},
+                                       {xgemm_kernel<true, 32, false, false, true>, xgemm_kernel<true, 64, false, false, true>}};
     g_route.prod[a_t ? 1 : 0] = {p.wt, p.ks};
-    hipLaunchKernelGGL(kernels[bf16][p.wt == 64][conv ? 2 : a_t], dim3((unsigned)(p.gr * p.gc), (unsigned)p.ks, taps), dim3(256), 0, s, a);
+    const Kernel k = a.gate ? gated[bf16][p.wt == 64] : kernels[bf16][p.wt == 64][conv ? 2 : a_t];
+    hipLaunchKernelGGL(k, dim3((unsigned)(p.gr * p.gc), (unsigned)p.ks, taps), dim3(256), 0, s, a);
 }
 
 // the reduce a dense product leaves to do (blocks == 0: none, it ran unsplit)
@@ -486,21 +525,24 @@ extern "C" int64_t mumpy_linear_bwd_workspace_bytes(int64_t M, int N, int K) {
     return linear_bwd_layout(M, N, K, true, true, INT64_MAX).bytes;
 }
 
-extern "C" int mumpy_linear_bwd(const float* x, const float* W, const float* dy, float* dx, float* dW, float* db, int64_t M,
-                                int N, int K, int accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
-    if (M == 0) return 0;
-    MUMPY_REQUIRE(dy && (dx || dW || db), MUMPY_ENULL, "linear_bwd: null pointer");
-    MUMPY_REQUIRE((!dx || W) && (!dW || x), MUMPY_ENULL, "linear_bwd: dx needs W, dW needs x");
+// the body of mumpy_linear_bwd and mumpy_linear_gelu_bwd (who: the message prefix).  gate: null, or the z of x = gelu(z) -- dx is
+// then dz = (dy W) o gelu'(z), applied where the complete product is first held: the store of an unsplit product, the reduce of a
+// split one.  Everything else -- plans, workspace layout, launches -- is the same.
+static int linear_bwd_run(const char* who, const float* x, const float* W, const float* dy, float* dx, float* dW, float* db,
+                          const float* gate, int64_t M, int N, int K, int accumulate, void* workspace, int64_t workspace_bytes,
+                          void* stream) {
+    MUMPY_REQUIRE(dy && (dx || dW || db), MUMPY_ENULL, "%s: null pointer", who);
+    MUMPY_REQUIRE((!dx || W) && (!dW || x), MUMPY_ENULL, "%s: dx needs W, dW needs x", who);
     MUMPY_REQUIRE(M > 0 && M < (1ll << 31) - 256 && N > 0 && K > 0 && N % 32 == 0 && K % 32 == 0, MUMPY_EINVAL,
-                  "linear_bwd: need N %% 32 == 0 and K %% 32 == 0 (got M=%lld N=%d K=%d)", (long long)M, N, K);
+                  "%s: need N %% 32 == 0 and K %% 32 == 0 (got M=%lld N=%d K=%d)", who, (long long)M, N, K);
     MUMPY_REQUIRE(aligned16(x) && aligned16(W) && aligned16(dy) && aligned16(dx) && aligned16(dW) && aligned16(db) && aligned16(workspace),
-                  MUMPY_EALIGN, "linear_bwd: pointers must be 16-byte aligned");
-    MUMPY_REQUIRE((accumulate & ~(3 | MUMPY_MATH_BF16)) == 0, MUMPY_EINVAL, "linear_bwd: unknown accumulate bits 0x%x", accumulate);
+                  MUMPY_EALIGN, "%s: pointers must be 16-byte aligned", who);
+    MUMPY_REQUIRE((accumulate & ~(3 | MUMPY_MATH_BF16)) == 0, MUMPY_EINVAL, "%s: unknown accumulate bits 0x%x", who, accumulate);
     const bool bf16 = (accumulate & MUMPY_MATH_BF16) != 0;
     const int db_accum = (accumulate >> 1) & 1;
     const LinearBwdLayout l = linear_bwd_layout(M, N, K, dx != nullptr, dW != nullptr, workspace ? workspace_bytes : 0);
-    MUMPY_REQUIRE(!workspace || workspace_bytes >= l.bytes, MUMPY_EINVAL, "linear_bwd: workspace too small");
-    MUMPY_REQUIRE(!db || dW || workspace, MUMPY_ENULL, "linear_bwd: db without dW needs the workspace");
+    MUMPY_REQUIRE(!workspace || workspace_bytes >= l.bytes, MUMPY_EINVAL, "%s: workspace too small", who);
+    MUMPY_REQUIRE(!db || dW || workspace, MUMPY_ENULL, "%s: db without dW needs the workspace", who);
     hipStream_t s = as_stream(stream);
     float* ws = static_cast<float*>(workspace);
     const unsigned nblk = (unsigned)((N + 63) / 64);
@@ -519,11 +561,12 @@ extern "C" int mumpy_linear_bwd(const float* x, const float* W, const float* dy,
         MUMPY_CHECK_LAUNCH("linear_bwd(bias)");
     }
     g_route = Route{};
-    g_route.family = Route::XGEMM; g_route.np = bf16 ? 1 : 0;
+    g_route.family = Route::XGEMM; g_route.np = bf16 ? 1 : 0; g_route.dual = gate && dx ? 1 : 0;
     ReduceJob jx{}, jw{};
     RowSumArgs rs{};
     if (dx) {        // dX[M,K] = dY[M,N] W[N,K]
-        const XArgs a = product_args(dy, N, W, K, dx, K, (int)M, K, N, l.px, 0, ws ? ws + l.dx_slabs : nullptr);
+        XArgs a = product_args(dy, N, W, K, dx, K, (int)M, K, N, l.px, 0, ws ? ws + l.dx_slabs : nullptr);
+        a.gate = gate;
         launch_product(bf16, false, false, l.px, 1, a, s);
         MUMPY_CHECK_LAUNCH("linear_bwd(product)");
         jx = reduce_job(a);
@@ -540,10 +583,43 @@ extern "C" int mumpy_linear_bwd(const float* x, const float* W, const float* dy,
     const int jobs = (jx.blocks != 0) + (jw.blocks != 0);
     g_route.reduce = jobs == 2 ? Route::R_TWO_IN_ONE : jobs == 1 ? Route::R_ONE : Route::R_NONE;
     if (jobs) {
-        hipLaunchKernelGGL(xgemm_reduce_kernel, dim3(jx.blocks + jw.blocks), dim3(256), 0, s, jx, jw, rs);
+        const f32x4* g4 = reinterpret_cast<const f32x4*>(gate);
+        if (gate && jx.blocks) hipLaunchKernelGGL(xgemm_reduce_kernel<true>, dim3(jx.blocks + jw.blocks), dim3(256), 0, s, jx, jw, rs, g4);
+        else hipLaunchKernelGGL(xgemm_reduce_kernel<false>, dim3(jx.blocks + jw.blocks), dim3(256), 0, s, jx, jw, rs, g4);
         MUMPY_CHECK_LAUNCH("linear_bwd(reduce)");
     }
     return 0;
+}
+
+extern "C" int mumpy_linear_bwd(const float* x, const float* W, const float* dy, float* dx, float* dW, float* db, int64_t M,
+                                int N, int K, int accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (M == 0) return 0;
+    return linear_bwd_run("linear_bwd", x, W, dy, dx, dW, db, nullptr, M, N, K, accumulate, workspace, workspace_bytes, stream);
+}
+
+// ---- backward of fc2 of an MLP whose hidden activation is a = gelu(z): mumpy_linear_bwd for y = a W^T + b with the GELU derivative
+// taken into the dX product, dz = (dy W) o gelu'(z) -- the separate gelu_bwd launch (read z, read da, write dz) is gone.  dW and
+// db are those of mumpy_linear_bwd (operand: a); the workspace and its layout are the same.
+extern "C" int64_t mumpy_linear_gelu_bwd_workspace_bytes(int64_t M, int N, int K) { return mumpy_linear_bwd_workspace_bytes(M, N, K); }
+
+// half-open byte ranges [p, p + n) and [q, q + m) share a byte (null: no range)
+static bool overlaps(const void* p, int64_t n, const void* q, int64_t m) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+    return p && q && a < b + (uintptr_t)m && b < a + (uintptr_t)n;
+}
+
+extern "C" int mumpy_linear_gelu_bwd(const float* a, const float* z, const float* W, const float* dy, float* dz, float* dW, float* db,
+                                     int64_t M, int N, int K, int accumulate, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (M == 0) return 0;
+    MUMPY_REQUIRE(!dz || z, MUMPY_ENULL, "linear_gelu_bwd: dz needs z");
+    MUMPY_REQUIRE(aligned16(z), MUMPY_EALIGN, "linear_gelu_bwd: pointers must be 16-byte aligned");
+    if (M > 0 && N > 0 && K > 0) {
+        const int64_t mk = M * (int64_t)K * 4, mn = M * (int64_t)N * 4;
+        MUMPY_REQUIRE(!(z && z == a), MUMPY_EINVAL, "linear_gelu_bwd: z and a are the same buffer (a = gelu(z) is saved beside z)");
+        MUMPY_REQUIRE(!overlaps(dz, mk, z, mk) && !overlaps(dz, mk, a, mk) && !overlaps(dz, mk, dy, mn), MUMPY_EINVAL,
+                      "linear_gelu_bwd: dz must not alias z, a or dy");
+    }
+    return linear_bwd_run("linear_gelu_bwd", a, W, dy, dz, dW, db, dz ? z : nullptr, M, N, K, accumulate, workspace, workspace_bytes, stream);
 }
 
 // n / d for every n < 2^31 as mulhi(n, magic) >> shift (round-up method, 31-bit dividends; d >= 2)

@@ -471,7 +471,9 @@ __device__ __forceinline__ void loader_role(const Params& p, float* lds, unsigne
 // one ds_swizzle (common.h)
 __device__ __forceinline__ float half_sum32(float x) { return wave_sum(x, 32); }
 
-template <int P, bool OUT16 = false, int LN = 0>
+// DUAL (mumpy_linear_gelu_dual_fwd): no residual; p.residual is a second OUTPUT of y's shape that receives image + bias, the value
+// before the activation, through the residual's descriptor and row offsets (the same range check drops rows past M).
+template <int P, bool OUT16 = false, int LN = 0, bool DUAL = false>
 __device__ __forceinline__ void epilogue_role(const Params& p, float* lds, unsigned b, unsigned G, unsigned u0, unsigned u1, int hl) {
     constexpr uint32_t OSZ = OUT16 ? 2u : 4u;
     const float* const E = lds + E_OFF_DW;
@@ -509,7 +511,7 @@ __device__ __forceinline__ void epilogue_role(const Params& p, float* lds, unsig
 #pragma unroll
         for (int e = 0; e < PASSES; ++e) {
             yo[e] = ybase + (uint32_t)e * row8;
-            rv[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_r, yo[e], 0, 0));
+            if (!DUAL) rv[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_r, yo[e], 0, 0));
         }
         bias4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs_b, n < p.N ? (uint32_t)n * 4u : OOB, 0, 0));
         if (LN == 1) {
@@ -554,11 +556,12 @@ __device__ __forceinline__ void epilogue_role(const Params& p, float* lds, unsig
             v = rstd * (v - mean * cs4);
         }
         v += bias4;
+        if (DUAL) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs_r, yo[e], 0, MUMPY_WS_STORE_AUX);
         if (p.act == MUMPY_ACT_GELU) {
 #pragma unroll
             for (int x = 0; x < 4; ++x) v[x] = gelu_erf(v[x]);
         }
-        v += rv[e];
+        if (!DUAL) v += rv[e];
         if (LN == 1) {                              // statistics of the stored values: mean over the tile's columns, then M2
             const float mean_t = half_sum32(st_valid ? (v[0] + v[1]) + (v[2] + v[3]) : 0.f) * st_inv;
             const f32x4 d = v - mean_t;
@@ -700,7 +703,7 @@ __device__ __forceinline__ void epilogue_role(const Params& p, float* lds, unsig
 }
 
 // IO: 0 = fp32 operands and output; 1 = bf16 operands, bf16 output; 2 = bf16 operands, fp32 output (+ fp32 residual)
-template <int P, bool CONV = false, int IO = 0, int LN = 0>
+template <int P, bool CONV = false, int IO = 0, int LN = 0, bool DUAL = false>
 __global__ __launch_bounds__(768, 3) void gemm_ws_kernel(Params p) {
     extern __shared__ __attribute__((aligned(1024))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -730,7 +733,7 @@ __global__ __launch_bounds__(768, 3) void gemm_ws_kernel(Params p) {
         // the few instructions of these roles are not additionally delayed by arbitration)
         if (!(DBG & 8)) __builtin_amdgcn_s_setprio(3);
         if (wave < 8) loader_role<CONV, IO != 0>(p, lds, t0, kc0, n_chunks, tid - 256);
-        else epilogue_role<P, IO == 1, LN>(p, lds, b, G, u0, u1, tid - 512);
+        else epilogue_role<P, IO == 1, LN, DUAL>(p, lds, b, G, u0, u1, tid - 512);
     }
 }
 
@@ -815,9 +818,10 @@ inline int launch_ws(unsigned grid, int lds_bytes, int max_lds, hipStream_t s, c
 
 inline int launch(const float* x, const float* W, const float* bias, const float* residual, float* y, int64_t M, int N,
                   int K, int act, int num_cu, hipStream_t s, void* ws = nullptr, int64_t ws_bytes = 0, int force_split = -1,
-                  void* stamps = nullptr, bool ws_clean = false, const Conv* cv = nullptr, const LnArgs* ln = nullptr) {
+                  void* stamps = nullptr, bool ws_clean = false, const Conv* cv = nullptr, const LnArgs* ln = nullptr,
+                  float* dual_z = nullptr) {
     Params p;
-    unsigned grid = base_params(p, x, W, bias, residual, y, M, N, K, act, BM, BK, (unsigned)num_cu);
+    unsigned grid = base_params(p, x, W, bias, dual_z ? dual_z : residual, y, M, N, K, act, BM, BK, (unsigned)num_cu);
     if (ln) {
         p.stats_out = ln->stats_out; p.ln_stats = ln->ln_stats; p.ln_colsum = ln->ln_colsum;
         p.ln_gn = ln->ln_gn; p.ln_C = ln->ln_C; p.ln_eps = ln->ln_eps;
@@ -858,9 +862,10 @@ inline int launch(const float* x, const float* W, const float* bias, const float
     }
     g_route = Route{};
     g_route.family = Route::WS; g_route.addr = cv ? Route::CONV : Route::DENSE;
-    g_route.split = split; g_route.passes = (uint8_t)P; g_route.ln = (uint8_t)ln_mode;
+    g_route.split = split; g_route.passes = (uint8_t)P; g_route.ln = (uint8_t)ln_mode; g_route.dual = dual_z ? 1 : 0;
     return with_passes(P, [&](auto pc) {
         constexpr int PC = decltype(pc)::value;
+        if (dual_z) return launch_ws<gemm_ws_kernel<PC, false, 0, 0, true>>(grid, LDS_BYTES, LDS_BYTES, s, p);
         if (cv) return launch_ws<gemm_ws_kernel<PC, true>>(grid, LDS_BYTES, LDS_BYTES, s, p);
         if (ln_mode == 1) return launch_ws<gemm_ws_kernel<PC, false, 0, 1>>(grid, LDS_BYTES, LDS_BYTES, s, p);
         if (ln_mode == 2) return launch_ws<gemm_ws_kernel<PC, false, 0, 2>>(grid, LDS_BYTES, LDS_BYTES, s, p);

@@ -76,27 +76,34 @@ class LinearFn(torch.autograd.Function):
         weight = weight.reshape(n, k)
         dy2, x2 = dy.reshape(-1, n).contiguous(), x.reshape(-1, k)
         need_dx, need_dw, need_db = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
-        if ops.matrix_math() not in ("fp32", "bf16") or LEGACY_LINEAR_BWD:
-            # split-precision modes: the forward GEMM on transposed copies (its operand modes apply to the backward products too)
-            dx = ops.linear(dy2, ops.transpose(weight)).reshape(x.shape) if need_dx else None
-            dw = ops.linear(ops.transpose(dy2, 32), ops.transpose(x2, 32)).reshape(wshape) if need_dw else None
-            db = ops.col_sum(dy2) if need_db else None
-            return dx, dw, db, (dy if ctx.has_res and ctx.needs_input_grad[3] else None)
-        m = dy2.shape[0]
-        wslot, bslot = _grad_slot(ctx.params[0]), _grad_slot(ctx.params[1])
-        # large token counts: dX on the forward GEMM (the wave-specialised kernel) against a transposed copy of W -- the
-        # copy is weight-sized and the product runs at 100+ TFLOP/s; everything else in one call, no copies
-        big = need_dx and m >= BIG_DGRAD_ROWS
-        dx = dw = db = None
-        if (need_dx and not big) or need_dw or need_db:          # (a frozen Linear with a big input needs only the GEMM below)
-            dx, dw, db = ops.linear_bwd(x2.contiguous(), weight, dy2, need_dx=need_dx and not big, need_dw=need_dw, need_db=need_db,
-                                        dw_out=wslot.reshape(n, k) if (need_dw and wslot is not None) else None,
-                                        db_out=bslot if need_db else None)
-        if big:
-            dx = ops.linear(dy2, ops.transpose(weight))
+        dx, dw, db = _linear_backward(x2, weight, dy2, ctx.params, need_dx, need_dw, need_db)
         if dw is not None:
             dw = dw.reshape(wshape)
         return (dx.reshape(x.shape) if need_dx else None), dw, db, (dy if ctx.has_res and ctx.needs_input_grad[3] else None)
+
+
+def _linear_backward(x2, weight, dy2, params, need_dx, need_dw, need_db):
+    """The backward of a taped Linear on 2-D operands (weight (N, K)) -> (dx, dW, db).  One call; dW / db go into the parameters' flat
+    gradient slots where they have one (the matching value is then None).  The mode is the one set at BACKWARD time."""
+    n, k = weight.shape
+    if ops.matrix_math() not in ("fp32", "bf16") or LEGACY_LINEAR_BWD:
+        # split-precision modes: the forward GEMM on transposed copies (its operand modes apply to the backward products too)
+        dx = ops.linear(dy2, ops.transpose(weight)) if need_dx else None
+        dw = ops.linear(ops.transpose(dy2, 32), ops.transpose(x2, 32)) if need_dw else None
+        return dx, dw, (ops.col_sum(dy2) if need_db else None)
+    m = dy2.shape[0]
+    wslot, bslot = _grad_slot(params[0]), _grad_slot(params[1])
+    # large token counts: dX on the forward GEMM (the wave-specialised kernel) against a transposed copy of W -- the
+    # copy is weight-sized and the product runs at 100+ TFLOP/s; everything else in one call, no copies
+    big = need_dx and m >= BIG_DGRAD_ROWS
+    dx = dw = db = None
+    if (need_dx and not big) or need_dw or need_db:          # (a frozen Linear with a big input needs only the GEMM below)
+        dx, dw, db = ops.linear_bwd(x2.contiguous(), weight, dy2, need_dx=need_dx and not big, need_dw=need_dw, need_db=need_db,
+                                    dw_out=wslot.reshape(n, k) if (need_dw and wslot is not None) else None,
+                                    db_out=bslot if need_db else None)
+    if big:
+        dx = ops.linear(dy2, ops.transpose(weight))
+    return dx, dw, db
 
 
 LEGACY_LINEAR_BWD = os.environ.get("MUMPY_LEGACY_LINEAR_BWD", "0") != "0"   # the first version's route (transposes + forward GEMM), for A/B runs
@@ -163,6 +170,59 @@ class GeluFn(torch.autograd.Function):
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
         return ops.gelu_bwd(x, dy.contiguous())
+
+
+class MlpFn(torch.autograd.Function):
+    """fc2(gelu(fc1(x))) [+ residual] as ONE tape node (ops.set_mlp_fusion): fc1 writes its pre-activation z and a = gelu(z) from one
+    launch, fc2 is the ordinary GEMM (the residual rides in its epilogue, as in LinearFn); the backward of fc2 takes gelu'(z) into
+    its dX product, dz = (dy W2) o gelu'(z), and fc1's backward is LinearFn's with dz.  Against the three nodes it replaces: one
+    launch fewer in the forward, one fewer in the backward, the same values saved (x, z, a).  The matrix mode is read again in the
+    backward, as LinearFn does: under a split-precision mode (or LEGACY_LINEAR_BWD) set after the forward, fc2's backward is
+    LinearFn's there followed by gelu_bwd."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, residual=None):
+        z, a = ops.linear_gelu_dual(x, w1, b1)
+        ctx.save_for_backward(x, w1, z, a, w2)
+        ctx.has_b1, ctx.has_b2, ctx.has_res = b1 is not None, b2 is not None, residual is not None
+        ctx.params = (w1, b1, w2, b2)
+        return ops.linear(a, w2, b2, residual=residual)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, z, a, w2 = ctx.saved_tensors
+        nig = ctx.needs_input_grad
+        n2, hid = w2.shape
+        c = w1.shape[1]
+        need_dx, need_dw1, need_db1 = nig[0], nig[1], ctx.has_b1 and nig[2]
+        need_dw2, need_db2 = nig[3], ctx.has_b2 and nig[4]
+        need_dz = need_dx or need_dw1 or need_db1
+        dy2, a2, z2 = dy.reshape(-1, n2).contiguous(), a.reshape(-1, hid), z.reshape(-1, hid)
+        dz = dw2 = db2 = None
+        if ops.matrix_math() not in ("fp32", "bf16") or LEGACY_LINEAR_BWD:
+            da, dw2, db2 = _linear_backward(a2, w2, dy2, ctx.params[2:], need_dz, need_dw2, need_db2)
+            dz = ops.gelu_bwd(z2, da) if need_dz else None
+        elif need_dz or need_dw2 or need_db2:                    # the one gated call at every M (profiles/mlp_fused_train.md)
+            w2slot, b2slot = _grad_slot(ctx.params[2]), _grad_slot(ctx.params[3])
+            dz, dw2, db2 = ops.linear_gelu_bwd(a2, z2, w2, dy2, need_dz=need_dz, need_dw=need_dw2, need_db=need_db2,
+                                               dw_out=w2slot.reshape(n2, hid) if (need_dw2 and w2slot is not None) else None,
+                                               db_out=b2slot if need_db2 else None)
+        dx = dw1 = db1 = None
+        if need_dz:
+            dx, dw1, db1 = _linear_backward(x.reshape(-1, c), w1, dz, ctx.params[:2], need_dx, need_dw1, need_db1)
+        return (dx.reshape(x.shape) if need_dx else None), dw1, db1, dw2, db2, (dy if ctx.has_res and nig[5] else None)
+
+
+def _mlp_residual(x_res, drop_path, z, fc1, fc2):
+    """x_res + drop_path(fc2(gelu(fc1(z)))), the MLP half of a transformer block.  ops.mlp_fusion() off, a split-precision matrix
+    mode or LEGACY_LINEAR_BWD: three tape nodes (Linear, GELU, Linear with the residual in its epilogue when stochastic depth is
+    inactive).  On: one MlpFn node, with the residual under the same condition."""
+    if not ops.mlp_fusion() or ops.matrix_math() not in ("fp32", "bf16") or LEGACY_LINEAR_BWD:
+        hmid = GeluFn.apply(LinearFn.apply(z, fc1.weight, fc1.bias))
+        return _residual_linear(x_res, drop_path, hmid, fc2.weight, fc2.bias)
+    if not drop_path.training or getattr(drop_path, "drop_prob", 0.0) <= 0.0:
+        return MlpFn.apply(z, fc1.weight, fc1.bias, fc2.weight, fc2.bias, x_res)
+    return AddFn.apply(x_res, drop_path_train(drop_path, MlpFn.apply(z, fc1.weight, fc1.bias, fc2.weight, fc2.bias)))
 
 
 class AddFn(torch.autograd.Function):
@@ -244,8 +304,7 @@ def swin_block_train(block, x):
                                 (b, hs, w, block.dim, block.shift_size, att.scale), tab, ids)
     x = _residual_linear(x, block.drop_path, a, att.proj.weight, att.proj.bias)
     x, z = ResidualLayerNormFn.apply(x, block.norm2.weight, block.norm2.bias, block.norm2.eps)
-    hmid = GeluFn.apply(LinearFn.apply(z, block.mlp.fc1.weight, block.mlp.fc1.bias))
-    return _residual_linear(x, block.drop_path, hmid, block.mlp.fc2.weight, block.mlp.fc2.bias)
+    return _mlp_residual(x, block.drop_path, z, block.mlp.fc1, block.mlp.fc2)
 
 
 class PatchGatherFn(torch.autograd.Function):
@@ -462,8 +521,7 @@ def global_block_train(block, x):
     x = _residual_linear(x, block.drop_path, a, att.proj.weight, att.proj.bias)
     x, z = ResidualLayerNormFn.apply(x, block.norm2.weight, block.norm2.bias, block.norm2.eps)
     mlp = block.mlp.unwrapped
-    hmid = GeluFn.apply(LinearFn.apply(z, mlp.fc1.weight, mlp.fc1.bias))
-    return _residual_linear(x, block.drop_path, hmid, mlp.fc2.weight, mlp.fc2.bias)
+    return _mlp_residual(x, block.drop_path, z, mlp.fc1, mlp.fc2)
 
 
 # ---------------------------------------------------------------------------------------------- pyramid Decoder (row 15)
@@ -670,8 +728,7 @@ def cross_swin_block_train(blk, x1, x2):
         yw = AddFn.apply(x1w, d)                                          # CVAModule: x1 + drop_path(D) (mTVE:138)
         x1 = AddFn.apply(x1, drop_path_train(blk.drop_path, yw.reshape(b, l1, c1)))       # window-major y added to raster x1 (mTVE:285-286)
     x1, z = ResidualLayerNormFn.apply(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-    hmid = GeluFn.apply(LinearFn.apply(z, blk.mlp.fc1.weight, blk.mlp.fc1.bias))
-    return _residual_linear(x1, blk.drop_path, hmid, blk.mlp.fc2.weight, blk.mlp.fc2.bias), out
+    return _mlp_residual(x1, blk.drop_path, z, blk.mlp.fc1, blk.mlp.fc2), out
 
 
 def encoder_train(enc, x):

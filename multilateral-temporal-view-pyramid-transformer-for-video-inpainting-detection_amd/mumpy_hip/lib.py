@@ -130,8 +130,11 @@ EXT_VERSION = 1
 EXT2_SIGNATURES = {
     "mumpy_deform_attention_mm16_bwd_workspace_bytes": [c_l, c_i, c_i],
     "mumpy_deform_attention_mm16_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_f],
+    "mumpy_linear_gelu_dual_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+    "mumpy_linear_gelu_bwd_workspace_bytes": [c_l, c_i, c_i],
+    "mumpy_linear_gelu_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
 }
-EXT2_VERSION = 1
+EXT2_VERSION = 2
 
 
 def library_path() -> str:

@@ -207,6 +207,34 @@ def cva_math() -> str:
     return _CVA_MATH
 
 
+def _mlp_fusion_from_env() -> bool:
+    v = os.environ.get("MUMPY_MLP_FUSED", "") or "0"
+    if v not in ("0", "1"):
+        raise ValueError(f"MUMPY_MLP_FUSED: expected \"0\" or \"1\", got {v!r}")
+    return v == "1"
+
+
+_MLP_FUSED = _mlp_fusion_from_env()      # read once, at import
+
+
+def set_mlp_fusion(on: bool) -> None:
+    """The MLP of a transformer block ON THE TRAINING TAPE (autograd.MlpFn: the Swin, global and cross-view blocks).  Off (default):
+    fc1, GELU, fc2 as three tape nodes -- five launches a step that touch the hidden tensor.  On: fc1 writes z and a = gelu(z) from one
+    launch (linear_gelu_dual) and fc2's backward takes gelu'(z) into its dX product (linear_gelu_bwd): two launches fewer per MLP,
+    the same arithmetic.  Follows set_matrix_math ("fp32" / "bf16"); under a split-precision mode, and under autograd.LEGACY_LINEAR_BWD,
+    the tape keeps its unfused lines.  Independent of set_storage, set_attention_math and set_cva_math; the inference forward is
+    untouched.  The initial value is the environment variable MUMPY_MLP_FUSED ("0" / "1"), read when this module is imported.  Read
+    at launch time in the tape's forward and carried to its backward: set it BEFORE a graphed training step is captured."""
+    global _MLP_FUSED
+    if not isinstance(on, (bool, int)) or on not in (0, 1):
+        raise ValueError(f"set_mlp_fusion: expected a bool, got {on!r}")
+    _MLP_FUSED = bool(on)
+
+
+def mlp_fusion() -> bool:
+    return _MLP_FUSED
+
+
 def _mm16(entry, math):
     """C-ABI entry of a cross-view attention op for math= "fp32" (the entry itself) or "bf16" (its _mm16 form)."""
     if math not in ("fp32", "bf16"):
@@ -978,6 +1006,60 @@ def linear_bwd(x2d, weight, dy2d, need_dx=True, dw_out=None, db_out=None, need_d
     _call("mumpy_linear_bwd", _p(x2d), _p(weight), _p(dy2d), _p(dx), _p(dw), _p(db), m, n, k, acc, _p(ws), wsb, _stream(),
           work=2.0 * m * n * k * (int(need_dx) + int(need_dw)))
     return dx, (None if dw_out is not None else dw), (None if db_out is not None else db)
+
+
+def linear_gelu_dual(x, weight, bias=None):
+    """fc1 of an MLP on the training tape: -> (z, a) with z = x @ weight.T + bias and a = gelu(z), both fp32, from ONE launch
+    (mumpy_linear_gelu_dual_fwd) -- the plan and kernels of linear(x, weight, bias, act=ACT_GELU) with a second store in the
+    epilogue.  Follows set_matrix_math for "fp32" / "bf16"; the split-precision modes have no such kernel (an error, no fallback)."""
+    x, weight = _chk(x, "x"), _chk(weight, "weight")
+    n, k = weight.shape[0], weight.numel() // weight.shape[0]
+    if x.shape[-1] != k:
+        raise RuntimeError(f"linear_gelu_dual: x has {x.shape[-1]} features, weight expects {k}")
+    if _MATH not in (MATH_FP32, MATH_BF16):
+        raise RuntimeError("linear_gelu_dual: the split-precision modes have no dual-output kernel")
+    m = x.numel() // k
+    z = torch.empty(*x.shape[:-1], n, device=x.device, dtype=torch.float32)
+    a = torch.empty_like(z)
+    wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
+    ws = _kept_workspace(wsb, x.device) if wsb else None
+    _call("mumpy_linear_gelu_dual_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(z), _p(a), m, n, k, _MATH, _p(ws),
+          0 if ws is None else ws.numel() * 4, _stream(), work=2.0 * m * n * k)
+    return z, a
+
+
+def linear_gelu_bwd(a2d, z2d, weight, dy2d, need_dz=True, need_dw=True, need_db=False, dw_out=None, db_out=None):
+    """Backward of y = a W^T + b for a = gelu(z) in ONE C-ABI call (mumpy_linear_gelu_bwd): -> (dz, dW, db) with
+    dz = (dy W) o gelu'(z); dW / db and the accumulate-into-slot contract (dw_out / db_out) are linear_bwd's."""
+    dy2d, a2d, z2d, weight = _chk(dy2d, "dy"), _chk(a2d, "a"), _chk(z2d, "z"), _chk(weight, "weight")
+    m, k = a2d.shape
+    n = weight.shape[0]
+    if dy2d.shape != (m, n) or weight.shape[1] != k or z2d.shape != a2d.shape:
+        raise RuntimeError(f"linear_gelu_bwd: a {tuple(a2d.shape)}, z {tuple(z2d.shape)}, weight {tuple(weight.shape)}, "
+                           f"dy {tuple(dy2d.shape)} do not match")
+    dev = dy2d.device
+    dz = torch.empty(m, k, device=dev, dtype=torch.float32) if need_dz else None
+    acc = 0
+    dw = db = None
+    if need_dw:
+        if dw_out is not None:
+            dw, acc = _chk(dw_out, "dw_out"), acc | 1
+        else:
+            dw = torch.empty(n, k, device=dev, dtype=torch.float32)
+    if need_db:
+        if db_out is not None:
+            db, acc = _chk(db_out, "db_out"), acc | 2
+        else:
+            db = torch.empty(n, device=dev, dtype=torch.float32)
+    wsb = _ws_bytes(("lgbwd", m, n, k), "mumpy_linear_gelu_bwd_workspace_bytes", m, n, k)
+    ws = _ws(wsb, dev)
+    if _MATH == MATH_BF16:
+        acc |= MATH_BF16
+    elif _MATH != MATH_FP32:
+        raise RuntimeError("linear_gelu_bwd: the split-precision modes have no one-call backward")
+    _call("mumpy_linear_gelu_bwd", _p(a2d), _p(z2d), _p(weight), _p(dy2d), _p(dz), _p(dw), _p(db), m, n, k, acc, _p(ws), wsb,
+          _stream(), work=2.0 * m * n * k * (int(need_dz) + int(need_dw)))
+    return dz, (None if dw_out is not None else dw), (None if db_out is not None else db)
 
 
 def final_conv_bwd(x, w_krsc, dy):

@@ -20,7 +20,11 @@
   | kernel_micro.py cva_attn_bwd16 B1w r C        window form: the fp32 cross-view attention backward (deform_attention_bwd math="fp32",
                                                 its r - 1 add launches included) against the bf16-MFMA pair (math="bf16"), and the two
                                                 forwards, on the same input; each one's REPS calls captured in one graph, the four graphs
-                                                replayed alternately for ROUNDS rounds"""
+                                                replayed alternately for ROUNDS rounds
+  | kernel_micro.py mlp M C hidden                the launches of one MLP on the training tape, fused (ops.set_mlp_fusion) against the ones
+                                                they replace, MUMPY_MATH=fp32|bf16: fc1 as linear + gelu / linear_gelu_dual; fc2's
+                                                backward (dz, dW2, db2) as linear_bwd + gelu_bwd / the big-M pair (dX on the forward
+                                                GEMM against W^T, linear_bwd for dW2 and db2, gelu_bwd) / linear_gelu_bwd; same protocol"""
 import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "multilateral-temporal-view-pyramid-transformer-for-video-inpainting-detection_amd")]
@@ -151,6 +155,44 @@ if op == "cva_attn_bwd16":
     print(f"{op} {a}: " + ", ".join(f"{n} {med[n]:.2f} us [{min(t):.2f}..{max(t):.2f}]" for n, t in times.items())
           + f"; bwd fp32/bf16 = {med['bwd fp32'] / med['bwd bf16']:.2f}, fwd fp32/bf16 = {med['fwd fp32'] / med['fwd bf16']:.2f}"
           + f"  (median of {rounds} alternating replays of {reps} captured launches)")
+    sys.exit(0)
+if op == "mlp":
+    m, c, hid = a
+    torch.manual_seed(0)
+    x = torch.randn(m, c, device=dev); w1 = torch.randn(hid, c, device=dev) / c ** 0.5; b1 = torch.randn(hid, device=dev)
+    w2 = torch.randn(c, hid, device=dev) / hid ** 0.5; dy = torch.randn(m, c, device=dev)
+    z, act = ops.linear_gelu_dual(x, w1, b1)
+
+    def big_pair():
+        ops.linear_bwd(act, w2, dy, need_dx=False, need_dw=True, need_db=True)
+        return ops.gelu_bwd(z, ops.linear(dy, ops.transpose(w2)))
+    run = {"fwd linear + gelu": lambda: ops.gelu(ops.linear(x, w1, b1)), "fwd dual": lambda: ops.linear_gelu_dual(x, w1, b1),
+           "bwd linear_bwd + gelu_bwd": lambda: ops.gelu_bwd(z, ops.linear_bwd(act, w2, dy, need_dx=True, need_dw=True, need_db=True)[0]),
+           "bwd big pair": big_pair,
+           "bwd gated": lambda: ops.linear_gelu_bwd(act, z, w2, dy, need_dz=True, need_dw=True, need_db=True)}
+    rounds = int(os.environ.get("ROUNDS", "12"))
+    graphs = {}
+    for name, fn in run.items():
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                fn()
+        side.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name], stream=side):
+            for _ in range(reps):
+                fn()
+        graphs[name].replay()
+    torch.cuda.synchronize()
+    times = {name: [] for name in run}
+    for _ in range(rounds):
+        for name in run:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); graphs[name].replay(); e1.record(); torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+    print(f"{op} {a} {ops.matrix_math()}: " + ", ".join(f"{n} {sorted(t)[len(t) // 2]:.2f} us [{min(t):.2f}..{max(t):.2f}]" for n, t in times.items())
+          + f"  (median of {rounds} alternating replays of {reps} captured calls)")
     sys.exit(0)
 if op in ("winattn_mm16", "winattn_bwd16"):
     b, hs, w, c, shift = a
