@@ -880,6 +880,49 @@ def normalize_u8(frames, mean=EVAL_MEAN, std=EVAL_STD, size=None):
     return out
 
 
+def _chk_exact(t, name, dtype, shape):
+    """A buffer the kernel reads or writes where it is: never copied, so anything that would need a copy is an error."""
+    if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError(f"mumpy_hip: augment_stage_u8 needs {name} as a contiguous {dtype} GPU tensor of shape {tuple(shape)}, "
+                           f"got {t.dtype} {tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    return t
+
+
+def augment_stage_u8(frames, tab_a, tab_b, swap, masks=None, out=None, target=None, mean=EVAL_MEAN, std=EVAL_STD):
+    """The training input stage in one launch (mumpy_augment_stage_u8_fwd, include/mumpy_hip_ext3.h): frames (nclips, T, Hs, Ws, 3)
+    uint8 -> (nclips, T, 3, L, L) float32, gathered through the per-clip tables tab_a / tab_b (nclips, L) int32 and swap (nclips)
+    int32 of mumpy_hip.augment.clip_tables (resize + flip / rotation + crop), then ToTensor + Normalize as normalize_u8.
+    masks (nmasks, Hs, Ws) uint8: also -> target (nclips, L * L) float32 = (mask c % nmasks, gathered) > 0; returns (out, target).
+    out= / target= are written in place and must be contiguous float32 of exactly that shape.  Everything lives on the GPU; the
+    tables are read when the kernel runs, so a captured launch follows later uploads into them."""
+    import ctypes
+    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise RuntimeError("mumpy_hip: augment_stage_u8 needs a contiguous uint8 GPU tensor (nclips, T, H, W, 3) (there is no CPU path)")
+    nclips, t, hs, ws = frames.shape[:4]
+    if tab_a.dim() != 2:
+        raise RuntimeError("mumpy_hip: augment_stage_u8 needs tab_a of shape (nclips, L)")
+    L = tab_a.shape[1]
+    _chk_exact(tab_a, "tab_a", torch.int32, (nclips, L))
+    _chk_exact(tab_b, "tab_b", torch.int32, (nclips, L))
+    _chk_exact(swap, "swap", torch.int32, (nclips,))
+    if target is not None and masks is None:
+        raise RuntimeError("mumpy_hip: augment_stage_u8: target= needs masks")
+    nmasks = 0
+    if masks is not None:
+        if masks.dim() != 3:
+            raise RuntimeError("mumpy_hip: augment_stage_u8 needs masks of shape (nmasks, H, W)")
+        nmasks = masks.shape[0]
+        _chk_exact(masks, "masks", torch.uint8, (nmasks, hs, ws))
+        target = torch.empty(nclips, L * L, device=frames.device, dtype=torch.float32) if target is None else \
+            _chk_exact(target, "target", torch.float32, (nclips, L * L))
+    out = torch.empty(nclips, t, 3, L, L, device=frames.device, dtype=torch.float32) if out is None else \
+        _chk_exact(out, "out", torch.float32, (nclips, t, 3, L, L))
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    _call("mumpy_augment_stage_u8_fwd", _p(frames), _p(masks), _p(out), _p(target), _p(tab_a), _p(tab_b), _p(swap), nclips, t, nmasks,
+          hs, ws, L, m3, s3, _stream(), work=float(5 * out.numel() + (5 * target.numel() if masks is not None else 0)))
+    return out if masks is None else (out, target)
+
+
 # ---------------------------------------------------------------------------------------------- training tail (8f-2)
 def mask_loss(logits, target, need_grad=True, eps=0.0, loss_scale=1.0):
     """softIoULoss + WeightedFocalLoss as train.py:107-113 calls them (utils/loss.py:6-55).  logits (B,...) and 0/1 target of the
