@@ -12,7 +12,11 @@ pinned pillow==4.0.0), one augmentation is drawn per sample and applied to every
 With out[y, x] = canvas[u, v] every such pipeline folds into two index tables of L entries and one swap bit per clip (`clip_tables`),
 and the whole stage is one gather launch with the arithmetic of ops.normalize_u8 (`ops.augment_stage_u8`,
 mumpy_augment_stage_u8_fwd of include/mumpy_hip_ext3.h).  RandomRotate (a bilinear warp) and RandomScaleCrop (a CUBIC resize)
-interpolate and are not expressible this way: asking for them raises.
+interpolate and are not expressible this way: `sample_double` refuses them.  They run as modes 2 and 1 of a second kernel that
+interpolates on the canvas those tables describe (`ops.augment_warp_u8`, mumpy_augment_warp_u8_fwd of include/mumpy_hip_ext4.h):
+`sample_double_full` draws from the whole list, `clip_warp_params` builds the kernel's rows, AugmentedInput(warp=True) runs them.
+RandomScaleCrop is Pillow's 8-bit BICUBIC restated in integers, bit for bit; RandomRotate is a plain fp32 bilinear warp, not
+cv2.warpAffine's fixed-point one -- how far the two differ is not measured.
 
 This module is host code (numpy + the library's host helper mumpy_resize_nearest_table) and imports without a GPU; only
 AugmentedInput touches the device.  The samplers follow the reference's distributions, not its RNG stream."""
@@ -182,6 +186,204 @@ def sample_double(rng, src_hw, L, mask_u8=None, shape_ops=None, v_range=(20.0, 2
     return op, random_crop_box(cm, v, L, rng)
 
 
+# ------------------------------------------------------------------------------------------------ the interpolating operations
+# RandomScaleCrop and RandomRotate do not permute pixels; they run on the device as modes 1 and 2 of mumpy_augment_warp_u8_fwd
+# (include/mumpy_hip_ext4.h), which reads the L x L canvas through the tables of clip_tables and interpolates on it.  The rows below
+# are that kernel's per-clip parameters.
+MODE_GATHER, MODE_CUBIC, MODE_AFFINE = 0, 1, 2
+PRECISION_BITS = 22                    # Pillow's 8-bit resample: coefficients in 22-bit fixed point, each pass clip8((2^21 + sum) >> 22)
+
+WarpParams = collections.namedtuple("WarpParams", "tab_a tab_b swap mode pos_y pos_x coef_y coef_x affine")
+# op: the D4 operation drawn first; shape: the entry of SHAPE_LIST; box: the crop box on the canvas (the crops) or on the S x S upscale
+# (RandomScaleCrop; None: no box); S, angle: RandomScaleCrop's side, RandomRotate's angle (None otherwise)
+FullDraw = collections.namedtuple("FullDraw", "op shape box S angle")
+
+
+@functools.lru_cache(maxsize=4096)
+def _cubic(n_in: int, n_out: int):
+    if n_in < 1 or n_out < n_in:
+        raise ValueError(f"augment: cubic_taps restates Pillow's BICUBIC for n_out >= n_in >= 1 only (4 taps), got {n_in} -> {n_out}")
+    scale = float(n_in) / n_out                          # <= 1: the filter is not widened, its support stays 2
+    a = -0.5
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum(np.trunc(center - 2.0 + 0.5), 0.0)
+    hi = np.minimum(np.trunc(center + 2.0 + 0.5), float(n_in))
+    assert (hi - lo <= 4.0).all()
+    pos = lo[:, None] + np.arange(4.0)
+    x = np.abs(pos - center[:, None] + 0.5)
+    w = np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0, np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * a, 0.0))
+    w = np.where(pos < hi[:, None], w, 0.0)                # the taps Pillow drops at the right / bottom edge
+    ww = ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]        # Pillow's own order of summation
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    start = lo.astype(np.int32)
+    coef = np.trunc(np.where(w < 0.0, -0.5, 0.5) + w * (1 << PRECISION_BITS)).astype(np.int32)
+    start.setflags(write=False)
+    coef.setflags(write=False)
+    return start, coef
+
+
+def cubic_taps(n_in, n_out):
+    """Pillow's BICUBIC coefficients of an n_in -> n_out resize of 8-bit images, n_out >= n_in: (start (n_out,), coef (n_out, 4)) int32.
+    Output position i reads input start[i] .. start[i] + 3; a tap Pillow drops at an edge is a zero coefficient.  Centre
+    (i + 0.5) * n_in / n_out, support 2, a = -0.5, weights normalised in double, then trunc(+-0.5 + w * 2^22)."""
+    return _cubic(int(n_in), int(n_out))
+
+
+def _clip8(acc):
+    return np.clip((acc + (1 << (PRECISION_BITS - 1))) >> PRECISION_BITS, 0, 255)
+
+
+def _resample_rows(img, start, coef):
+    """One pass of Pillow's 8-bit resample along axis 0 of img (n_in, ...) integer -> (len(start), ...) int64 in [0, 255]."""
+    n_in = img.shape[0]
+    acc = np.zeros((len(start),) + img.shape[1:], np.int64)
+    tail = (1,) * (img.ndim - 1)
+    for k in range(4):
+        acc += coef[:, k].astype(np.int64).reshape(-1, *tail) * img[np.clip(start.astype(np.int64) + k, 0, n_in - 1)]
+    return _clip8(acc)
+
+
+def cubic_resize(img, out_hw):
+    """Image.resize(BICUBIC) of an 8-bit image (H, W[, C]) to out_hw >= (H, W), restated: the horizontal pass, then the vertical."""
+    img = np.asarray(img).astype(np.int64)
+    oh, ow = (int(v) for v in out_hw)
+    horiz = np.moveaxis(_resample_rows(np.moveaxis(img, 1, 0), *cubic_taps(img.shape[1], ow)), 0, 1)
+    return _resample_rows(horiz, *cubic_taps(img.shape[0], oh)).astype(np.uint8)
+
+
+def upscaled_mask(cmask, S):
+    """The canvas mask (L, L) as RandomScaleCrop's CornerCrop sees it: resized to S x S with CUBIC, in the kernel's integer arithmetic."""
+    return cubic_resize(cmask, (S, S))
+
+
+def _upscaled_part(cmask, S, ys, xs):
+    """upscaled_mask(cmask, S)[ys][:, xs] without forming the rest."""
+    cm = np.asarray(cmask).astype(np.int64)
+    L = cm.shape[0]
+    start, coef = cubic_taps(L, S)
+    rows = np.unique(np.clip(start[ys].astype(np.int64)[:, None] + np.arange(4), 0, L - 1))            # the canvas rows these ys read
+    horiz = np.zeros((L, len(xs)), np.int64)
+    horiz[rows] = np.moveaxis(_resample_rows(np.moveaxis(cm[rows], 1, 0), start[xs], coef[xs]), 0, 1)
+    return _resample_rows(horiz, start[ys], coef[ys])
+
+
+def upscaled_corners(cmask, S, chunk=8):
+    """find_corners(upscaled_mask(cmask, S)) from row and column "any" tests: rows and columns of the upscale are formed a few at a
+    time from each side of the region the mask's bounding box can reach, until one holds a positive pixel."""
+    cm = np.asarray(cmask)
+    rows, cols = np.flatnonzero(cm.any(axis=1)), np.flatnonzero(cm.any(axis=0))
+    if rows.size == 0:
+        return None
+    start, _ = cubic_taps(cm.shape[0], S)
+    reach = lambda lo, hi: np.flatnonzero((start + 3 >= lo) & (start <= hi))          # upscale positions with a tap in [lo, hi]
+    ys, xs = reach(rows[0], rows[-1]), reach(cols[0], cols[-1])
+
+    def first(cand, axis):
+        for k in range(0, len(cand), chunk):
+            c = cand[k:k + chunk]
+            hit = (_upscaled_part(cm, S, c, xs) if axis == 0 else _upscaled_part(cm, S, ys, c)).any(axis=1 - axis)
+            if hit.any():
+                return int(c[np.flatnonzero(hit)[0]])
+        return None
+    top = first(ys, 0)
+    if top is None:
+        return None
+    return first(xs, 1) - 1, top - 1, first(xs[::-1], 1) + 1, first(ys[::-1], 0) + 1
+
+
+def corner_crop_box(up_mask, rng):
+    """CornerCrop (randaugment.py:377-395) on the S x S upscaled mask: random_crop_box's draw with side S; None for an empty mask
+    (the reference then keeps the upscale whole)."""
+    return _corner_box(find_corners(up_mask), np.shape(up_mask)[0], rng)
+
+
+def _corner_box(corners, S, rng):
+    if corners is None:
+        return None
+    left, top, right, bottom = corners
+    S = int(S)
+    l = int(rng.integers(0, left - 1)) if left > 1 else 0
+    r = int(rng.integers(right + 1, S - 1)) if right + 1 < S - 1 else S - 1
+    t = int(rng.integers(0, top - 1)) if top > 1 else 0
+    b = int(rng.integers(bottom + 1, S - 1)) if bottom + 1 < S - 1 else S - 1
+    return check_box((l, t, r, b), S)
+
+
+def scale_crop_params(L, S, box=None):
+    """The mode-1 rows (pos_y, coef_y, pos_x, coef_x) of RandomScaleCrop on an L x L canvas: CUBIC to S x S, CornerCrop's box
+    (l, t, r, b) of the upscale resized back to S x S with NEAREST (None: no crop), the loader's NEAREST to L x L.  The two NEAREST
+    steps pick rows ty = t + near(b - t -> S)[near(S -> L)] of the upscale (columns alike), whose taps are the rows returned."""
+    L, S = int(L), int(S)
+    start, coef = cubic_taps(L, S)
+    back = nearest_table(S, L).astype(np.int64)
+    if box is None:
+        ty = tx = back
+    else:
+        l, t, r, b = check_box(box, S)
+        ty, tx = t + nearest_table(b - t, S).astype(np.int64)[back], l + nearest_table(r - l, S).astype(np.int64)[back]
+    return start[ty].copy(), coef[ty].copy(), start[tx].copy(), coef[tx].copy()
+
+
+def rotate_params(L, angle):
+    """The mode-2 rows (pos_y, pos_x, affine) of RandomRotate (randaugment.py:434-474) by an integer angle in degrees: affine maps
+    the rotated image's pixel (u, w) to the canvas about c = L / 2,
+        sx = cos(u - c) - sin(w - c) + c,    sy = sin(u - c) + cos(w - c) + c       (the inverse of cv2.getRotationMatrix2D's map),
+    and pos_* pick the centre crop of side int(crop_mult * L) resized back to L with NEAREST.  The crop angle is the angle folded
+    into [0, 90] degrees; for 0 .. 179 that is the reference's own expression, which leaves that range for larger angles."""
+    L, angle = int(L), int(angle)
+    th = np.deg2rad(float(angle % 360))
+    al, be, c = np.cos(th), np.sin(th), L / 2
+    fold = angle % 180
+    tc = np.deg2rad(float(180 - fold if fold > 90 else fold))
+    crop_mult = (np.cos(tc) + np.sin(tc) * np.tan(tc)) / (np.tan(tc) + 1.0)
+    side = int(crop_mult * L)
+    if not 1 <= side <= L:
+        raise ValueError(f"augment: rotation by {angle} degrees leaves a crop of side {side} of {L}")
+    pos = (int((L - side) / 2) + nearest_table(side, L)).astype(np.int32)
+    affine = np.array([al, -be, c - al * c + be * c, be, al, c - be * c - al * c, 0.0, 0.0], np.float32)
+    return pos, pos.copy(), affine
+
+
+def sample_double_full(rng, src_hw, L, mask_u8, base_size=512, v_range=(20.0, 220.0)):
+    """DoubleAugmentStrategy with its whole shape list: one of HFlip / VFlip / PsccAug, then one of RandomCrop, RandomRotate,
+    OriginalRandomCrop, RandomScaleCrop with equal probability and v ~ U(v_range) -> FullDraw, which clip_warp_params turns into the
+    kernel's rows.  RandomRotate takes int(v) degrees; 180, where the reference's crop has no extent, is drawn again.  RandomScaleCrop
+    draws its side uniformly in [base_size // 2, 2 * base_size] and its box from the upscaled mask.  mask_u8: the host mask (Hs, Ws)
+    the crops look at (None: an empty mask)."""
+    first = DOUBLE_LIST[int(rng.integers(0, len(DOUBLE_LIST)))]
+    op = PSCC_OPS[int(rng.integers(0, 7))] if first == "pscc" else first
+    shape = SHAPE_LIST[int(rng.integers(0, len(SHAPE_LIST)))]
+    v = float(rng.uniform(*v_range))
+    if shape == "RandomRotate":
+        while int(v) == 180:
+            v = float(rng.uniform(*v_range))
+        return FullDraw(op, shape, None, None, int(v))
+    if shape == "OriginalRandomCrop":
+        return FullDraw(op, shape, original_random_crop_box(v, L, rng), None, None)
+    cm = np.zeros((L, L), np.uint8) if mask_u8 is None else canvas_mask(mask_u8, *clip_tables(src_hw, L, op))
+    if shape == "RandomCrop":
+        return FullDraw(op, shape, random_crop_box(cm, v, L, rng), None, None)
+    S = int(rng.integers(base_size // 2, 2 * base_size + 1))
+    if S < L:
+        raise ValueError(f"augment: RandomScaleCrop drew side {S} below the canvas side {L}; the downscaling cubic is not restated")
+    return FullDraw(op, shape, _corner_box(upscaled_corners(cm, S), S, rng), S, None)
+
+
+def clip_warp_params(src_hw, L, draw) -> WarpParams:
+    """The per-clip arrays of mumpy_augment_warp_u8_fwd for a FullDraw; one record serves every clip of the sample."""
+    L = int(L)
+    zl, zc, za = np.zeros(L, np.int32), np.zeros((L, 4), np.int32), np.zeros(8, np.float32)
+    if draw.shape == "RandomScaleCrop":
+        py, cy, px, cx = scale_crop_params(L, draw.S, draw.box)
+        return WarpParams(*clip_tables(src_hw, L, draw.op), np.int32(MODE_CUBIC), py, px, cy, cx, za)
+    if draw.shape == "RandomRotate":
+        py, px, aff = rotate_params(L, draw.angle)
+        return WarpParams(*clip_tables(src_hw, L, draw.op), np.int32(MODE_AFFINE), py, px, zc, zc, aff)
+    if draw.shape not in FOLDABLE_SHAPE_OPS:
+        raise ValueError(f"augment: unknown shape operation {draw.shape!r}")
+    return WarpParams(*clip_tables(src_hw, L, draw.op, draw.box), np.int32(MODE_GATHER), zl, zl, zc, zc, za)
+
+
 # ------------------------------------------------------------------------------------------------ the device side
 class AugmentedInput:
     """Fills the clip tensor `x` (B, T, 3, L, L) and the `target` tensor (B * L * L elements) of a training step in place from uint8
@@ -195,9 +397,11 @@ class AugmentedInput:
     stacked arrays.  The object owns pinned host staging (two sets, used alternately) and the device buffers for frames, masks,
     tables and swap words; load() allocates nothing, uploads with non_blocking=True and launches once on the current stream.  The
     only wait is the host's, for the upload issued two loads earlier from the same staging set -- long finished in a training loop.
-    The tables live in device memory, so a captured launch (`launch()`) replays with the parameters uploaded last."""
+    The tables live in device memory, so a captured launch (`launch()`) replays with the parameters uploaded last.
+    warp=True: the launch is ops.augment_warp_u8, the parameter block holds every array of that call (still one upload), and a clip's
+    entry of params is either such a triple (a gather) or the WarpParams of clip_warp_params."""
 
-    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None):
+    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None, warp=False):
         import torch
         from . import ops
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5 or x.shape[2] != 3 or x.shape[3] != x.shape[4] or not x.is_contiguous():
@@ -215,11 +419,23 @@ class AugmentedInput:
         dev, u8, i32 = x.device, torch.uint8, torch.int32
         self.frames = torch.empty(b, t, hs, ws, 3, dtype=u8, device=dev)
         self.masks = torch.empty(self.nmasks, hs, ws, dtype=u8, device=dev) if target is not None else None
-        self.params = torch.empty(2 * b * L + b, dtype=i32, device=dev)          # [tab_a | tab_b | swap]: one upload
-        self.tab_a, self.tab_b, self.swap = self.params[:b * L].view(b, L), self.params[b * L:2 * b * L].view(b, L), self.params[2 * b * L:]
+        # one parameter block, one upload: [tab_a | tab_b | swap], or with warp every array of mumpy_augment_warp_u8_fwd -- the ones
+        # loaded 16 bytes at a time first (L % 4 == 0 keeps each of them aligned), affine as the bits of its float32
+        self.warp = bool(warp)
+        shapes = dict(tab_a=(b, L), tab_b=(b, L), pos_y=(b, L), pos_x=(b, L), coef_y=(b, L, 4), coef_x=(b, L, 4), affine=(b, 8), swap=(b,),
+                      mode=(b,))
+        self._fields = tuple(shapes) if self.warp else ("tab_a", "tab_b", "swap")
+        self._where, n = {}, 0
+        for name in self._fields:
+            self._where[name] = (n, n + int(np.prod(shapes[name])), shapes[name])
+            n += int(np.prod(shapes[name]))
+        self.params = torch.empty(n, dtype=i32, device=dev)
+        for name, (lo, hi, shape) in self._where.items():
+            view = self.params[lo:hi]
+            setattr(self, name, (view.view(torch.float32) if name == "affine" else view).view(shape))
         self._stage = [dict(frames=torch.empty(b, t, hs, ws, 3, dtype=u8).pin_memory(),
                             masks=torch.empty(self.nmasks, hs, ws, dtype=u8).pin_memory() if target is not None else None,
-                            params=torch.empty(2 * b * L + b, dtype=i32).pin_memory(), done=torch.cuda.Event()) for _ in range(2)]
+                            params=torch.empty(n, dtype=i32).pin_memory(), done=torch.cuda.Event()) for _ in range(2)]
         self._turn = 0
 
     def _upload(self, dst, src, pinned, what):
@@ -240,14 +456,26 @@ class AugmentedInput:
         self._turn ^= 1
         st["done"].synchronize()                 # host-side only: the upload of two loads ago has left this staging set
         if len(params) == 3 and hasattr(params[0], "ndim") and params[0].ndim == 2:          # the three stacked arrays
-            ta, tb, sw = params
-        else:                                                                                 # one (tab_a, tab_b, swap) per clip
-            ta, tb, sw = (np.stack([np.asarray(p[k]) for p in params]) for k in range(3))
-        ta, tb, sw = np.asarray(ta), np.asarray(tb), np.asarray(sw)
+            cols = dict(zip(("tab_a", "tab_b", "swap"), (np.asarray(p) for p in params)))
+        else:                                                          # one (tab_a, tab_b, swap) or, with warp, one WarpParams per clip
+            if any(len(p) != 3 for p in params) and not self.warp:
+                raise RuntimeError("AugmentedInput.load: a WarpParams record needs an input built with warp=True")
+            fields = WarpParams._fields if any(len(p) != 3 for p in params) else ("tab_a", "tab_b", "swap")
+            gather0 = (np.int32(MODE_GATHER), np.zeros(L, np.int32), np.zeros(L, np.int32), np.zeros((L, 4), np.int32),
+                       np.zeros((L, 4), np.int32), np.zeros(8, np.float32))
+            rows = [tuple(p) + gather0 if len(p) == 3 and len(fields) != 3 else p for p in params]
+            cols = {name: np.stack([np.asarray(r[k]) for r in rows]) for k, name in enumerate(fields)}
+        ta, tb, sw = cols["tab_a"], cols["tab_b"], cols["swap"]
         if ta.shape != (b, L) or tb.shape != (b, L) or sw.shape != (b,):
             raise RuntimeError(f"AugmentedInput.load: the tables must be ({b}, {L}) and the swap words ({b},), got {ta.shape}, {tb.shape}, {sw.shape}")
         host = st["params"].numpy()
-        host[:b * L], host[b * L:2 * b * L], host[2 * b * L:] = ta.reshape(-1), tb.reshape(-1), sw
+        for name, (lo, hi, shape) in self._where.items():
+            if name not in cols:                                       # triples only: every clip is a gather
+                host[lo:hi] = 0
+            elif cols[name].shape != shape:
+                raise RuntimeError(f"AugmentedInput.load: {name} must be {shape}, got {cols[name].shape}")
+            else:
+                (host[lo:hi].view(np.float32) if name == "affine" else host[lo:hi])[:] = cols[name].reshape(-1)
         self.params.copy_(st["params"], non_blocking=True)
         self._upload(self.frames, frames_u8, st["frames"], "frames")
         if self.target is not None:
@@ -262,6 +490,10 @@ class AugmentedInput:
     def launch(self):
         """The one kernel launch on the current stream, reading the device-resident parameters (capturable)."""
         from . import ops
-        ops.augment_stage_u8(self.frames, self.tab_a, self.tab_b, self.swap, masks=self.masks, out=self.x,
-                             target=None if self.target is None else self.target.view(self.nclips, self.L * self.L),
-                             mean=self.mean, std=self.std)
+        target = None if self.target is None else self.target.view(self.nclips, self.L * self.L)
+        if self.warp:
+            ops.augment_warp_u8(self.frames, self.tab_a, self.tab_b, self.swap, self.mode, self.pos_y, self.pos_x, self.coef_y, self.coef_x,
+                                self.affine, masks=self.masks, out=self.x, target=target, mean=self.mean, std=self.std)
+        else:
+            ops.augment_stage_u8(self.frames, self.tab_a, self.tab_b, self.swap, masks=self.masks, out=self.x, target=target,
+                                 mean=self.mean, std=self.std)

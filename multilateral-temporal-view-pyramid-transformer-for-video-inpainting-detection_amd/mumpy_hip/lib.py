@@ -143,6 +143,13 @@ EXT3_SIGNATURES = {
 }
 EXT3_VERSION = 1
 
+# ... and after that one; mirrors include/mumpy_hip_ext4.h one to one (tests/test_augment_warp_host.py checks it).  mean3 / std3: HOST
+EXT4_SIGNATURES = {
+    "mumpy_augment_warp_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i,
+                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f],
+}
+EXT4_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -197,7 +204,11 @@ def load_library():
     lib.mumpy_ext3_version.argtypes = []
     if lib.mumpy_ext3_version() != EXT3_VERSION:
         raise RuntimeError(f"{path}: third extension version {lib.mumpy_ext3_version()} != binding {EXT3_VERSION}; rebuild")
-    for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES}.items():
+    lib.mumpy_ext4_version.restype = c_i
+    lib.mumpy_ext4_version.argtypes = []
+    if lib.mumpy_ext4_version() != EXT4_VERSION:
+        raise RuntimeError(f"{path}: fourth extension version {lib.mumpy_ext4_version()} != binding {EXT4_VERSION}; rebuild")
+    for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

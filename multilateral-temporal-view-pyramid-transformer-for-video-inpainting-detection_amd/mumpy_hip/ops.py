@@ -880,10 +880,10 @@ def normalize_u8(frames, mean=EVAL_MEAN, std=EVAL_STD, size=None):
     return out
 
 
-def _chk_exact(t, name, dtype, shape):
+def _chk_exact(t, name, dtype, shape, who="augment_stage_u8"):
     """A buffer the kernel reads or writes where it is: never copied, so anything that would need a copy is an error."""
     if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise RuntimeError(f"mumpy_hip: augment_stage_u8 needs {name} as a contiguous {dtype} GPU tensor of shape {tuple(shape)}, "
+        raise RuntimeError(f"mumpy_hip: {who} needs {name} as a contiguous {dtype} GPU tensor of shape {tuple(shape)}, "
                            f"got {t.dtype} {tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (not contiguous)'}")
     return t
 
@@ -920,6 +920,45 @@ def augment_stage_u8(frames, tab_a, tab_b, swap, masks=None, out=None, target=No
     m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
     _call("mumpy_augment_stage_u8_fwd", _p(frames), _p(masks), _p(out), _p(target), _p(tab_a), _p(tab_b), _p(swap), nclips, t, nmasks,
           hs, ws, L, m3, s3, _stream(), work=float(5 * out.numel() + (5 * target.numel() if masks is not None else 0)))
+    return out if masks is None else (out, target)
+
+
+def augment_warp_u8(frames, tab_a, tab_b, swap, mode, pos_y, pos_x, coef_y, coef_x, affine, masks=None, out=None, target=None,
+                    mean=EVAL_MEAN, std=EVAL_STD):
+    """augment_stage_u8 with the interpolating augmentations (mumpy_augment_warp_u8_fwd, include/mumpy_hip_ext4.h), one launch for
+    clips of mixed modes: mode (nclips) int32 is 0 for the gather of augment_stage_u8, 1 for the separable 4-tap fixed-point resample
+    through pos_y / pos_x (nclips, L) and coef_y / coef_x (nclips, L, 4) int32 (RandomScaleCrop), 2 for the bilinear warp under affine
+    (nclips, 8) float32 at pos_x / pos_y (RandomRotate); the rows are those of mumpy_hip.augment.clip_warp_params.  Everything else,
+    and what is returned, as augment_stage_u8."""
+    import ctypes
+    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise RuntimeError("mumpy_hip: augment_warp_u8 needs a contiguous uint8 GPU tensor (nclips, T, H, W, 3) (there is no CPU path)")
+    nclips, t, hs, ws = frames.shape[:4]
+    if tab_a.dim() != 2:
+        raise RuntimeError("mumpy_hip: augment_warp_u8 needs tab_a of shape (nclips, L)")
+    L = tab_a.shape[1]
+    for name, buf, dtype, shape in (("tab_a", tab_a, torch.int32, (nclips, L)), ("tab_b", tab_b, torch.int32, (nclips, L)),
+                                    ("swap", swap, torch.int32, (nclips,)), ("mode", mode, torch.int32, (nclips,)),
+                                    ("pos_y", pos_y, torch.int32, (nclips, L)), ("pos_x", pos_x, torch.int32, (nclips, L)),
+                                    ("coef_y", coef_y, torch.int32, (nclips, L, 4)), ("coef_x", coef_x, torch.int32, (nclips, L, 4)),
+                                    ("affine", affine, torch.float32, (nclips, 8))):
+        _chk_exact(buf, name, dtype, shape, "augment_warp_u8")
+    if target is not None and masks is None:
+        raise RuntimeError("mumpy_hip: augment_warp_u8: target= needs masks")
+    nmasks = 0
+    if masks is not None:
+        if masks.dim() != 3:
+            raise RuntimeError("mumpy_hip: augment_warp_u8 needs masks of shape (nmasks, H, W)")
+        nmasks = masks.shape[0]
+        _chk_exact(masks, "masks", torch.uint8, (nmasks, hs, ws), "augment_warp_u8")
+        target = torch.empty(nclips, L * L, device=frames.device, dtype=torch.float32) if target is None else \
+            _chk_exact(target, "target", torch.float32, (nclips, L * L), "augment_warp_u8")
+    out = torch.empty(nclips, t, 3, L, L, device=frames.device, dtype=torch.float32) if out is None else \
+        _chk_exact(out, "out", torch.float32, (nclips, t, 3, L, L), "augment_warp_u8")
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    _call("mumpy_augment_warp_u8_fwd", _p(frames), _p(masks), _p(out), _p(target), _p(tab_a), _p(tab_b), _p(swap), _p(mode), _p(pos_y),
+          _p(pos_x), _p(coef_y), _p(coef_x), _p(affine), nclips, t, nmasks, hs, ws, L, m3, s3, _stream(),
+          work=float(5 * out.numel() + (5 * target.numel() if masks is not None else 0)))
     return out if masks is None else (out, target)
 
 
