@@ -2,6 +2,7 @@
 // rows are split over LPR lanes (a power of two <= 64) with 16-byte accesses, several rows per wave when C is small,
 // the row is held in registers between the statistics pass and the normalise pass (one read, one write).
 #include "common.h"
+#include "u8_pixel.h"
 using namespace mumpy;
 
 namespace {
@@ -233,12 +234,7 @@ __global__ __launch_bounds__(256) void resize_normalize_u8_kernel(const uint8_t*
         const float stdv = ch == 0 ? s0 : (ch == 1 ? s1 : s2);
         const uint8_t* row = src + ((f * Hs + ytab[y]) * (int64_t)Ws) * 3 + ch;
         const int4 xi = *reinterpret_cast<const int4*>(xtab + 4 * x4);
-        f32x4 v;
-        v[0] = ((float)row[3 * (int64_t)xi.x] / 255.0f - mean) / stdv;
-        v[1] = ((float)row[3 * (int64_t)xi.y] / 255.0f - mean) / stdv;
-        v[2] = ((float)row[3 * (int64_t)xi.z] / 255.0f - mean) / stdv;
-        v[3] = ((float)row[3 * (int64_t)xi.w] / 255.0f - mean) / stdv;
-        *reinterpret_cast<f32x4*>(dst + ((f * 3 + ch) * H + y) * (int64_t)W + 4 * x4) = v;
+        *reinterpret_cast<f32x4*>(dst + ((f * 3 + ch) * H + y) * (int64_t)W + 4 * x4) = normalize_u8_gather4(row, xi, mean, stdv);
     }
 }
 }  // namespace

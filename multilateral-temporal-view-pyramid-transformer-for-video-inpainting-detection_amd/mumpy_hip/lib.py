@@ -150,6 +150,15 @@ EXT4_SIGNATURES = {
 }
 EXT4_VERSION = 1
 
+# ... and after that one; mirrors include/mumpy_hip_ext5.h one to one (tests/test_video_host.py checks it).  mean3 / std3: HOST
+EXT5_SIGNATURES = {
+    "mumpy_clip_window_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float),
+                                 ctypes.POINTER(ctypes.c_float), c_f],
+    "mumpy_mask_score_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_l, c_f],
+    "mumpy_frame_metrics_fwd": [c_f, c_l, c_l, c_f, c_i, c_f],
+}
+EXT5_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -208,7 +217,12 @@ def load_library():
     lib.mumpy_ext4_version.argtypes = []
     if lib.mumpy_ext4_version() != EXT4_VERSION:
         raise RuntimeError(f"{path}: fourth extension version {lib.mumpy_ext4_version()} != binding {EXT4_VERSION}; rebuild")
-    for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES}.items():
+    lib.mumpy_ext5_version.restype = c_i
+    lib.mumpy_ext5_version.argtypes = []
+    if lib.mumpy_ext5_version() != EXT5_VERSION:
+        raise RuntimeError(f"{path}: fifth extension version {lib.mumpy_ext5_version()} != binding {EXT5_VERSION}; rebuild")
+    for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES,
+                       **EXT5_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

@@ -962,6 +962,77 @@ def augment_warp_u8(frames, tab_a, tab_b, swap, mode, pos_y, pos_x, coef_y, coef
     return out if masks is None else (out, target)
 
 
+# ---------------------------------------------------------------------------------------------- whole-video inference
+def clip_window_u8(frames, frame_idx, size, out=None, mean=EVAL_MEAN, std=EVAL_STD):
+    """Sliding clips out of a video that lives on the GPU (mumpy_clip_window_u8_fwd, include/mumpy_hip_ext5.h): frames
+    (nframes, Hs, Ws, 3) uint8 and frame_idx (nclips, T) int32 -> (nclips, T, 3, H, W) float32, size = (H, W): frame (c, t) is
+    normalize_u8(frames[clamp(frame_idx[c, t], 0, nframes - 1)], size=size) bit for bit.  out= is written in place and must be
+    contiguous float32 of exactly that shape.  frame_idx is read when the kernel runs, so a captured launch follows later uploads."""
+    import ctypes
+    who = "clip_window_u8"
+    if not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise RuntimeError("mumpy_hip: clip_window_u8 needs a contiguous uint8 GPU tensor (nframes, H, W, 3) (there is no CPU path)")
+    if frame_idx.dim() != 2:
+        raise RuntimeError("mumpy_hip: clip_window_u8 needs frame_idx of shape (nclips, T)")
+    nframes, hs, ws = frames.shape[:3]
+    nclips, t = frame_idx.shape
+    ho, wo = size
+    _chk_exact(frame_idx, "frame_idx", torch.int32, (nclips, t), who)
+    out = torch.empty(nclips, t, 3, ho, wo, device=frames.device, dtype=torch.float32) if out is None else \
+        _chk_exact(out, "out", torch.float32, (nclips, t, 3, ho, wo), who)
+    m3, s3 = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    ytab, xtab = _nearest_table(hs, ho, frames.device), _nearest_table(ws, wo, frames.device)
+    _call("mumpy_clip_window_u8_fwd", _p(frames), _p(out), _p(frame_idx), _p(ytab), _p(xtab), nclips, t, nframes, hs, ws, ho, wo, m3, s3,
+          _stream(), work=float(5 * out.numel()))
+    return out
+
+
+def mask_score_u8(mask, dest, bank, gt=None, counts=None):
+    """The masks of a batch of clips into the per-frame bank (mumpy_mask_score_u8_fwd): mask (nclips, ...) uint8 with npix elements per
+    clip (what Decoder.predict_mask emits), dest (nclips) int32, bank (nbank, npix) uint8, written in place: bank[dest[c]] =
+    mask[c] ? 255 : 0 for every clip with 0 <= dest[c] < nbank; the others (the padding of a batch tail) write nothing.
+    gt (nbank, npix) uint8: also counts[dest[c]] = [sum p & g, sum p, sum g, sum p | g] (int32 (nbank, 4), written in place; allocated
+    zeroed when not given).  Returns bank, or (bank, counts) with gt.  dest is read when the kernel runs."""
+    who = "mask_score_u8"
+    if bank.dim() != 2:
+        raise RuntimeError("mumpy_hip: mask_score_u8 needs bank of shape (nbank, npix)")
+    nbank, npix = bank.shape
+    _chk_exact(bank, "bank", torch.uint8, (nbank, npix), who)
+    nclips = dest.shape[0] if dest.dim() == 1 else -1
+    _chk_exact(dest, "dest", torch.int32, (nclips,), who)
+    if not mask.is_cuda or mask.dtype != torch.uint8 or not mask.is_contiguous() or mask.dim() < 1 or mask.shape[0] != nclips or \
+            mask.numel() != nclips * npix:
+        raise RuntimeError(f"mumpy_hip: mask_score_u8 needs mask as a contiguous uint8 GPU tensor ({nclips}, ...) of {npix} elements per "
+                           f"clip, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    if counts is not None and gt is None:
+        raise RuntimeError("mumpy_hip: mask_score_u8: counts= needs gt")
+    if gt is not None:
+        _chk_exact(gt, "gt", torch.uint8, (nbank, npix), who)
+        counts = torch.zeros(nbank, 4, device=bank.device, dtype=torch.int32) if counts is None else \
+            _chk_exact(counts, "counts", torch.int32, (nbank, 4), who)
+    _call("mumpy_mask_score_u8_fwd", _p(mask), _p(gt), _p(dest), _p(bank), _p(counts), nclips, npix, nbank, _stream(),
+          work=float((2 if gt is None else 3) * mask.numel()))
+    return bank if gt is None else (bank, counts)
+
+
+def frame_metrics(counts, nscored, npix, acc=None, accumulate=False):
+    """[sum F1, sum IoU, n] float64 over frames 0 .. nscored - 1 of counts (>= nscored, 4) int32 as mask_score_u8 writes them
+    (mumpy_frame_metrics_fwd; the per-image formulas of measure.py:57-62, 86-89 as distributed.eval_metric_vector states them).
+    acc= (3,) float64 is written in place -- added into with accumulate=True -- and is what evaluate.finalize_metrics takes."""
+    who = "frame_metrics"
+    if counts.dim() != 2 or counts.shape[0] < nscored:
+        raise RuntimeError(f"mumpy_hip: frame_metrics needs counts of shape (>= {nscored}, 4)")
+    _chk_exact(counts, "counts", torch.int32, (counts.shape[0], 4), who)
+    if acc is None:
+        if accumulate:
+            raise RuntimeError("mumpy_hip: frame_metrics: accumulate=True needs acc=")
+        acc = torch.empty(3, device=counts.device, dtype=torch.float64)
+    else:
+        _chk_exact(acc, "acc", torch.float64, (3,), who)
+    _call("mumpy_frame_metrics_fwd", _p(counts), int(nscored), int(npix), _p(acc), int(bool(accumulate)), _stream())
+    return acc
+
+
 # ---------------------------------------------------------------------------------------------- training tail (8f-2)
 def mask_loss(logits, target, need_grad=True, eps=0.0, loss_scale=1.0):
     """softIoULoss + WeightedFocalLoss as train.py:107-113 calls them (utils/loss.py:6-55).  logits (B,...) and 0/1 target of the

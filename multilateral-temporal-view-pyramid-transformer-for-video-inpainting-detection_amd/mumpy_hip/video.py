@@ -1,0 +1,187 @@
+"""Whole-video inference on the device: sliding clips, the per-frame mask bank, F1 / IoU.
+
+The reference takes a video of N frames and produces one forgery mask per frame: it builds one clip per frame -- the frame plus its
+k = T // 2 neighbours on each side, clamped at the ends (dataloaders/universaldataloader.py:41-48) --, runs each clip, keeps the
+centre frame's mask, writes mask * 255 (test.py:86-111) and scores every frame with the per-image F1 / IoU of measure.py:57-62, 86-89.
+Its CPU workers copy and resize every frame T times.  Here each frame is uploaded once; from there to the metric vector nothing leaves
+the device, and per batch of clips the host uploads two small tables and replays one graph (`VideoPredictor`):
+
+    clip_window_u8 (gather + resize + normalise out of the resident video) -> fused_forward -> mask_score_u8 (bank + counts)
+
+The host half (`clip_frame_indices`, `batch_plan`) imports and runs without a GPU."""
+import os
+
+import numpy as np
+import torch
+
+from .graph import GraphedForward
+
+SIDE = 224                       # the model's input side (inputRes of the reference's loaders)
+
+
+def clip_frame_indices(nframes: int, T: int) -> np.ndarray:
+    """(nframes, T) int32: row i holds clamp(j, 0, nframes - 1) for j = i - k .. i + k, k = T // 2 -- the comprehension of
+    universaldataloader.py:41-46.  An even T is refused: the reference's rule yields T + 1 frames there.
+    Column k of row i is i, the frame the mask belongs to: test.py names the saved file after that frame and measure.py scores it
+    against that frame's annotation.  (universaldataset.py:130 returns targets[1] as the clip's annotation, which is the centre frame
+    only for T = 3; this module follows measure.py.)"""
+    nframes, T = int(nframes), int(T)
+    if nframes < 1 or T < 1:
+        raise ValueError(f"clip_frame_indices: nframes={nframes} and T={T} must be at least 1")
+    if T % 2 == 0:
+        raise ValueError(f"clip_frame_indices: T={T} is even; the reference's window i - T//2 .. i + T//2 holds T + 1 frames then")
+    k = T // 2
+    j = np.arange(nframes)[:, None] + np.arange(-k, k + 1)[None, :]
+    return np.clip(j, 0, nframes - 1).astype(np.int32)
+
+
+def batch_plan(nframes: int, T: int, batch: int):
+    """-> (idx (nb, batch, T) int32, dest (nb, batch) int32), nb = ceil(nframes / batch): batch b runs the clips of frames
+    b * batch .. ; dest is the frame each clip's mask belongs to.  The tail of the last batch is padded with copies of the last clip
+    (valid indices) whose dest is -1: they write nothing and count for nothing."""
+    batch = int(batch)
+    if batch < 1:
+        raise ValueError(f"batch_plan: batch={batch} must be at least 1")
+    rows = clip_frame_indices(nframes, T)
+    nb = -(-nframes // batch)
+    pad = nb * batch - nframes
+    idx = np.concatenate([rows, np.repeat(rows[-1:], pad, axis=0)]).reshape(nb, batch, T)
+    dest = np.concatenate([np.arange(nframes, dtype=np.int32), np.full(pad, -1, np.int32)]).reshape(nb, batch)
+    return np.ascontiguousarray(idx), np.ascontiguousarray(dest)
+
+
+class VideoPredictor(GraphedForward):
+    """One forgery mask per frame of a video, and the F1 / IoU sums over its frames, without leaving the device.
+
+        vp = VideoPredictor(encoder, decoder, T=3, src_hw=(240, 432))
+        masks = vp.predict(frames_u8, gt_u8)            # (N, 224, 224) uint8, values 0 / 255, on the device
+        f1, iou, n = evaluate.finalize_metrics(vp.metric_vector())
+
+    It owns the frame bank (max_frames, Hs, Ws, 3), the index table (batch, T) and dest table (batch,), the clip batch
+    (batch, T, 3, 224, 224), the mask and annotation banks (max_frames, 224 * 224), the counts bank (max_frames, 4), the accumulator
+    of 3 doubles, and pinned host staging for the two tables.  With graph=True ONE graph is captured per predictor, holding
+    ops.clip_window_u8 into the clip batch, pipeline.fused_forward(..., with_mask=True) and ops.mask_score_u8; warm-up, capture
+    stream and the re-capture after a weight change are GraphedForward's.  Per batch the host uploads the two tables and replays.
+    graph=False issues the same three steps eagerly.
+
+    The reference's own test.py saves only clip 0 of each batch, so it works at batch size 1 only; this class returns every frame's
+    mask at any `batch`.  As in the reference, the forward couples the clips of one batch (SwinDAttention pairs windows across the
+    batch, see mumpy_hip/distributed.py): what comes out at `batch` = B is the model run at batch size B on these clips in this
+    order, the padding clips of the tail (copies of the last clip) included, and the GEMM kernels are chosen by the batch's row
+    count -- so results at different `batch` values are not bit for bit the same."""
+
+    def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True):
+        T, batch, max_frames = int(T), int(batch), int(max_frames)
+        clip_frame_indices(1, T)                                     # refuses an even T
+        model_t = int(encoder.configs[-1]["num_frames"])
+        if T != model_t:
+            raise ValueError(f"VideoPredictor: T={T}, but the encoder was built for clips of {model_t} frames")
+        if batch < 1 or max_frames < 1:
+            raise ValueError(f"VideoPredictor: batch={batch} and max_frames={max_frames} must be at least 1")
+        hs, ws = (int(v) for v in src_hw)
+        dev = next(encoder.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("VideoPredictor: the model is not on a GPU (there is no CPU path)")
+        self.T, self.batch, self.max_frames, self.src_hw, self.thr, self.graphed = T, batch, max_frames, (hs, ws), float(thr), bool(graph)
+        npix = SIDE * SIDE
+        nb = -(-max_frames // batch)
+        self.frames = torch.zeros(max_frames, hs, ws, 3, device=dev, dtype=torch.uint8)
+        self.idx = torch.zeros(batch, T, device=dev, dtype=torch.int32)
+        self.dest = torch.full((batch,), -1, device=dev, dtype=torch.int32)          # the warm-up runs write nothing
+        self.bank = torch.zeros(max_frames, npix, device=dev, dtype=torch.uint8)
+        self.gt = torch.zeros(max_frames, npix, device=dev, dtype=torch.uint8)
+        self.counts = torch.zeros(max_frames, 4, device=dev, dtype=torch.int32)
+        self.acc = torch.zeros(3, device=dev, dtype=torch.float64)
+        self._idx_host = torch.zeros(nb, batch, T, dtype=torch.int32).pin_memory()   # a whole video's plan: no slot is reused while
+        self._dest_host = torch.zeros(nb, batch, dtype=torch.int32).pin_memory()     # an upload out of it may still be in flight
+        self._uploaded = None
+        clips = torch.zeros(batch, T, 3, SIDE, SIDE, device=dev, dtype=torch.float32)
+        if self.graphed:
+            super().__init__(encoder, decoder, clips, with_mask=True)                # static_x is the clip batch
+        else:
+            self.encoder, self.decoder, self.with_mask, self.static_x = encoder, decoder, True, clips
+
+    def _fwd(self):
+        from . import ops
+        from .pipeline import fused_forward
+        ops.clip_window_u8(self.frames, self.idx, (SIDE, SIDE), out=self.static_x)
+        logits, mask, feats = fused_forward(self.encoder, self.decoder, self.static_x, with_mask=True, thr=self.thr)
+        ops.mask_score_u8(mask, self.dest, self.bank, gt=self.gt, counts=self.counts)
+        return logits, mask, feats
+
+    def __call__(self, frames_u8, gt_u8=None):
+        return self.predict(frames_u8, gt_u8)
+
+    def _run_batch(self):
+        if not self.graphed:
+            with torch.no_grad():
+                return self._fwd()
+        if self._stale():
+            self._capture()
+        self.graph.replay()
+        return self.static_out
+
+    @staticmethod
+    def _u8(t, name, shape):
+        t = torch.as_tensor(t)
+        if t.dtype != torch.uint8 or tuple(t.shape) != tuple(shape):
+            raise ValueError(f"VideoPredictor.predict: {name} must be uint8 of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+        return t
+
+    def predict(self, frames_u8, gt_u8=None, on_batch=None):
+        """frames_u8 (N, Hs, Ws, 3) uint8, on the host or the device, 1 <= N <= max_frames (N need not be a multiple of `batch`)
+        -> masks (N, 224, 224) uint8 with values 0 / 255 on the device: a view of the bank, valid until the next call.
+        gt_u8 (N, 224, 224) uint8 (> 0 counts as forged; the caller resizes annotations -- measure.py's BILINEAR resize of the
+        annotation is not part of this): the frame metrics of the N frames are added into the accumulator (`metric_vector`).
+        on_batch(b, logits, mask): called after batch b was issued, with the forward's static output buffers (logits (batch, 1, 224,
+        224) float32 and the 0 / 1 mask) -- the next batch overwrites them.
+        Everything is checked before anything is launched."""
+        from . import ops
+        frames_u8 = torch.as_tensor(frames_u8)
+        if frames_u8.dim() != 4 or frames_u8.shape[0] == 0:
+            raise ValueError(f"VideoPredictor.predict: frames must be (N, Hs, Ws, 3) with N >= 1, got {tuple(frames_u8.shape)}")
+        n = frames_u8.shape[0]
+        if n > self.max_frames:
+            raise ValueError(f"VideoPredictor.predict: {n} frames, but the banks hold max_frames={self.max_frames}")
+        frames_u8 = self._u8(frames_u8, "frames", (n, *self.src_hw, 3))
+        if gt_u8 is not None:
+            gt_u8 = self._u8(gt_u8, "gt", (n, SIDE, SIDE))
+        idx, dest = batch_plan(n, self.T, self.batch)
+        nb = idx.shape[0]
+        if self._uploaded is not None:
+            self._uploaded.synchronize()                             # the last video's uploads have left the staging
+        self._idx_host[:nb].copy_(torch.from_numpy(idx))
+        self._dest_host[:nb].copy_(torch.from_numpy(dest))
+        self.frames[:n].copy_(frames_u8, non_blocking=True)
+        if gt_u8 is not None:
+            self.gt[:n].copy_(gt_u8.reshape(n, SIDE * SIDE), non_blocking=True)
+        for b in range(nb):
+            self.idx.copy_(self._idx_host[b], non_blocking=True)
+            self.dest.copy_(self._dest_host[b], non_blocking=True)
+            out = self._run_batch()
+            if on_batch is not None:
+                on_batch(b, out[0], out[1])
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record()
+        if gt_u8 is not None:
+            ops.frame_metrics(self.counts, n, SIDE * SIDE, acc=self.acc, accumulate=True)
+        return self.bank[:n].view(n, SIDE, SIDE)
+
+    def metric_vector(self) -> torch.Tensor:
+        """The device [sum F1, sum IoU, n] over every frame scored since the last reset: what evaluate.finalize_metrics takes."""
+        return self.acc
+
+    def reset_metrics(self) -> None:
+        self.acc.zero_()
+
+    def write_masks(self, dirname, frame_numbers) -> None:
+        """Saves the masks of the last predict as '%04d_instance_%02d.png' % (frame_number, 0) (test.py:109-111), one per entry of
+        frame_numbers.  The one place that copies masks to the host."""
+        from PIL import Image
+        frame_numbers = [int(f) for f in frame_numbers]
+        if not 1 <= len(frame_numbers) <= self.max_frames:
+            raise ValueError(f"VideoPredictor.write_masks: {len(frame_numbers)} frame numbers for banks of {self.max_frames} frames")
+        masks = self.bank[:len(frame_numbers)].view(-1, SIDE, SIDE).cpu().numpy()
+        os.makedirs(dirname, exist_ok=True)
+        for f, m in zip(frame_numbers, masks):
+            Image.fromarray(m).save(os.path.join(dirname, "%04d_instance_%02d.png" % (f, 0)))
