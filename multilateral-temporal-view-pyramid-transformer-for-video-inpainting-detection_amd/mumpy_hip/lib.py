@@ -159,6 +159,12 @@ EXT5_SIGNATURES = {
 }
 EXT5_VERSION = 1
 
+# ... and after that one; mirrors include/mumpy_hip_ext6.h one to one (tests/test_annot_resize_host.py checks it)
+EXT6_SIGNATURES = {
+    "mumpy_resize_bilinear_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+}
+EXT6_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -221,8 +227,12 @@ def load_library():
     lib.mumpy_ext5_version.argtypes = []
     if lib.mumpy_ext5_version() != EXT5_VERSION:
         raise RuntimeError(f"{path}: fifth extension version {lib.mumpy_ext5_version()} != binding {EXT5_VERSION}; rebuild")
+    lib.mumpy_ext6_version.restype = c_i
+    lib.mumpy_ext6_version.argtypes = []
+    if lib.mumpy_ext6_version() != EXT6_VERSION:
+        raise RuntimeError(f"{path}: sixth extension version {lib.mumpy_ext6_version()} != binding {EXT6_VERSION}; rebuild")
     for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES,
-                       **EXT5_SIGNATURES}.items():
+                       **EXT5_SIGNATURES, **EXT6_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

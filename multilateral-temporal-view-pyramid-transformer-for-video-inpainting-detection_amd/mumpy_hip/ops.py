@@ -1033,6 +1033,42 @@ def frame_metrics(counts, nscored, npix, acc=None, accumulate=False):
     return acc
 
 
+_BILINEAR_TABLES = {}
+
+
+def _bilinear_tables(hs: int, ws: int, ho: int, wo: int, device):
+    """Pillow's BILINEAR taps of an (hs, ws) -> (ho, wo) resize (mumpy_hip.video.bilinear_taps), cached on the device:
+    (ystart, ycount, ycoef, xstart, xcount, xcoef)."""
+    key = (hs, ws, ho, wo, str(device))
+    t = _BILINEAR_TABLES.get(key)
+    if t is None:
+        from .video import bilinear_taps
+        t = _BILINEAR_TABLES[key] = tuple(torch.from_numpy(a).to(device) for a in bilinear_taps(hs, ho) + bilinear_taps(ws, wo))
+    return t
+
+
+def resize_bilinear_u8(src, size, out=None):
+    """Image.resize((W, H), Image.BILINEAR) of single-channel 8-bit images on the GPU (mumpy_resize_bilinear_u8_fwd,
+    include/mumpy_hip_ext6.h): src (n, Hs, Ws) uint8 -> (n, H, W) uint8, size = (H, W), Pillow's result bit for bit at any ratio
+    (mumpy_hip.video.bilinear_resize is the numpy statement) -- the resize measure.py:21-40 applies to every annotation.  out= is
+    written in place and must be contiguous uint8 of exactly that shape.  src is read where it is: never copied.  The first call for
+    a pair of sizes uploads its six tap tables (cached per sizes and device): make that call outside a graph capture."""
+    who = "resize_bilinear_u8"
+    if not src.is_cuda or src.dtype != torch.uint8 or src.dim() != 3 or not src.is_contiguous():
+        raise RuntimeError(f"mumpy_hip: resize_bilinear_u8 needs a contiguous uint8 GPU tensor (n, H, W) (there is no CPU path), got "
+                           f"{src.dtype} {tuple(src.shape)} on {src.device}")
+    n, hs, ws = src.shape
+    ho, wo = (int(v) for v in size)
+    if hs < 1 or ws < 1 or ho < 1 or wo < 1:
+        raise RuntimeError(f"mumpy_hip: resize_bilinear_u8: empty image, {hs}x{ws} -> {ho}x{wo}")
+    out = torch.empty(n, ho, wo, device=src.device, dtype=torch.uint8) if out is None else \
+        _chk_exact(out, "out", torch.uint8, (n, ho, wo), who)
+    ys, yc, yk, xs, xc, xk = _bilinear_tables(hs, ws, ho, wo, src.device)
+    _call("mumpy_resize_bilinear_u8_fwd", _p(src), _p(out), _p(ys), _p(yc), _p(yk), _p(xs), _p(xc), _p(xk), n, hs, ws, ho, wo,
+          yk.shape[1], xk.shape[1], _stream(), work=float(src.numel() + out.numel()))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- training tail (8f-2)
 def mask_loss(logits, target, need_grad=True, eps=0.0, loss_scale=1.0):
     """softIoULoss + WeightedFocalLoss as train.py:107-113 calls them (utils/loss.py:6-55).  logits (B,...) and 0/1 target of the

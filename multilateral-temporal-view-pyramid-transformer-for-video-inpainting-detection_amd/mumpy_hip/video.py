@@ -8,7 +8,12 @@ the device, and per batch of clips the host uploads two small tables and replays
 
     clip_window_u8 (gather + resize + normalise out of the resident video) -> fused_forward -> mask_score_u8 (bank + counts)
 
-The host half (`clip_frame_indices`, `batch_plan`) imports and runs without a GPU."""
+Annotations may arrive at their own size (`VideoPredictor(gt_hw=...)`): measure.py:21-40 resizes each to 224 x 224 with Pillow's 8-bit
+BILINEAR before it thresholds, and ops.resize_bilinear_u8 does that on the device, bit for bit.  `bilinear_taps` builds Pillow's
+coefficient tables and `bilinear_resize` is the numpy statement of the whole resize.  Not covered: a palette image's conversion to
+'L' (the caller's `.convert('L')`), RGB images, the other filters, `box=` and `reducing_gap=`.
+
+The host half (`clip_frame_indices`, `batch_plan`, `bilinear_taps`, `bilinear_resize`) imports and runs without a GPU."""
 import os
 
 import numpy as np
@@ -50,12 +55,76 @@ def batch_plan(nframes: int, T: int, batch: int):
     return np.ascontiguousarray(idx), np.ascontiguousarray(dest)
 
 
+PRECISION_BITS = 22             # Pillow's 8-bit resampling: coefficients are fixed point with 22 fractional bits (Resample.c)
+GT_MAX_RATIO = 32               # 2 * 32 + 1 taps = MUMPY_RESIZE_KMAX_CAP of include/mumpy_hip_ext6.h
+
+
+def bilinear_taps(n_in: int, n_out: int):
+    """Pillow's BILINEAR coefficients of an n_in -> n_out resize of 8-bit images, any ratio: (start (n_out,), count (n_out,),
+    coef (n_out, ksize)) int32.  Output position i reads input start[i] .. start[i] + count[i] - 1; coef[i, count[i]:] is 0.
+    precompute_coeffs + normalize_coeffs_8bpc restated for the triangle filter, in double and in Pillow's order: the filter is
+    stretched by max(n_in / n_out, 1) (the antialiasing of a downscale), so ksize = 2 * ceil(that) + 1 grows with the ratio; the
+    weights of a row are divided by their sum, then trunc(0.5 + w * 2^22).  n_in == n_out gives the identity -- coef[:, 0] = 2^22 and
+    zeros --, which is what the pass Pillow skips for an unchanged side amounts to."""
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"bilinear_taps: n_in={n_in} and n_out={n_out} must be at least 1")
+    scale = n_in / n_out
+    fs = max(scale, 1.0)
+    support = fs
+    ksize = 2 * int(np.ceil(support)) + 1
+    start, count = np.zeros(n_out, np.int32), np.zeros(n_out, np.int32)
+    coef = np.zeros((n_out, ksize), np.int32)
+    for i in range(n_out):
+        center = (i + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), n_in) - xmin
+        w = [max(0.0, 1.0 - abs((x + xmin - center + 0.5) / fs)) for x in range(xmax)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        for x, v in enumerate(w):
+            if ww != 0.0:
+                v = v / ww
+            coef[i, x] = int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS))
+        start[i], count[i] = xmin, xmax
+    return start, count, coef
+
+
+def _resample_rows(img, start, count, coef):
+    """One pass of Pillow's 8-bit resample along axis 0 of img (n_in, ...) -> (len(start), ...) int64 in [0, 255]."""
+    n_in = img.shape[0]
+    acc = np.full((len(start),) + img.shape[1:], 1 << (PRECISION_BITS - 1), np.int64)
+    tail = (1,) * (img.ndim - 1)
+    for k in range(coef.shape[1]):
+        c = np.where(k < count, coef[:, k], 0).astype(np.int64)
+        acc += c.reshape(-1, *tail) * img[np.clip(start.astype(np.int64) + k, 0, n_in - 1)]
+    return np.clip(acc >> PRECISION_BITS, 0, 255)
+
+
+def bilinear_resize(img_u8, out_hw) -> np.ndarray:
+    """Image.resize((w, h), Image.BILINEAR) of an 8-bit single-channel image (H, W) -- or of a stack (..., H, W) --, restated in
+    integers: the horizontal pass, its result rounded to uint8, then the vertical pass; each is
+    clip((2^21 + sum coef * src) >> 22, 0, 255) with the taps of `bilinear_taps`.  The numpy statement of ops.resize_bilinear_u8."""
+    img = np.asarray(img_u8)
+    if img.dtype != np.uint8 or img.ndim < 2:
+        raise ValueError(f"bilinear_resize: needs a uint8 image (..., H, W), got {img.dtype} {img.shape}")
+    oh, ow = (int(v) for v in out_hw)
+    img = img.astype(np.int64)
+    horiz = np.moveaxis(_resample_rows(np.moveaxis(img, -1, 0), *bilinear_taps(img.shape[-1], ow)), 0, -1)
+    vert = _resample_rows(np.moveaxis(horiz, -2, 0), *bilinear_taps(img.shape[-2], oh))
+    return np.ascontiguousarray(np.moveaxis(vert, 0, -2)).astype(np.uint8)
+
+
 class VideoPredictor(GraphedForward):
     """One forgery mask per frame of a video, and the F1 / IoU sums over its frames, without leaving the device.
 
         vp = VideoPredictor(encoder, decoder, T=3, src_hw=(240, 432))
         masks = vp.predict(frames_u8, gt_u8)            # (N, 224, 224) uint8, values 0 / 255, on the device
         f1, iou, n = evaluate.finalize_metrics(vp.metric_vector())
+
+    gt_hw=(Hg, Wg): predict takes the annotations at their own size and resizes them on the device as measure.py does (see predict);
+    gt_hw=None (the default) takes them at 224 x 224 and launches nothing more.
 
     It owns the frame bank (max_frames, Hs, Ws, 3), the index table (batch, T) and dest table (batch,), the clip batch
     (batch, T, 3, 224, 224), the mask and annotation banks (max_frames, 224 * 224), the counts bank (max_frames, 4), the accumulator
@@ -70,7 +139,7 @@ class VideoPredictor(GraphedForward):
     order, the padding clips of the tail (copies of the last clip) included, and the GEMM kernels are chosen by the batch's row
     count -- so results at different `batch` values are not bit for bit the same."""
 
-    def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True):
+    def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True, gt_hw=None, gt_chunk=64):
         T, batch, max_frames = int(T), int(batch), int(max_frames)
         clip_frame_indices(1, T)                                     # refuses an even T
         model_t = int(encoder.configs[-1]["num_frames"])
@@ -79,6 +148,12 @@ class VideoPredictor(GraphedForward):
         if batch < 1 or max_frames < 1:
             raise ValueError(f"VideoPredictor: batch={batch} and max_frames={max_frames} must be at least 1")
         hs, ws = (int(v) for v in src_hw)
+        self.gt_hw = None if gt_hw is None else tuple(int(v) for v in gt_hw)
+        self.gt_chunk = int(gt_chunk)
+        if self.gt_hw is not None and (len(self.gt_hw) != 2 or min(self.gt_hw) < 1 or self.gt_chunk < 1):
+            raise ValueError(f"VideoPredictor: gt_hw={gt_hw} must be (Hg, Wg) with both at least 1, and gt_chunk={gt_chunk} at least 1")
+        if self.gt_hw is not None and max(self.gt_hw) > GT_MAX_RATIO * SIDE:
+            raise ValueError(f"VideoPredictor: gt_hw={gt_hw} is more than {GT_MAX_RATIO} times {SIDE} (the resize kernel's tap cap)")
         dev = next(encoder.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("VideoPredictor: the model is not on a GPU (there is no CPU path)")
@@ -95,6 +170,13 @@ class VideoPredictor(GraphedForward):
         self._idx_host = torch.zeros(nb, batch, T, dtype=torch.int32).pin_memory()   # a whole video's plan: no slot is reused while
         self._dest_host = torch.zeros(nb, batch, dtype=torch.int32).pin_memory()     # an upload out of it may still be in flight
         self._uploaded = None
+        # annotations that arrive from the host at their own size pass through this, gt_chunk frames at a time (1080p annotations
+        # of a whole video would cost max_frames * Hg * Wg bytes)
+        self._gt_stage = None if self.gt_hw is None else \
+            torch.zeros(min(self.gt_chunk, max_frames), *self.gt_hw, device=dev, dtype=torch.uint8)
+        if self.gt_hw is not None:
+            from . import ops
+            ops._bilinear_tables(*self.gt_hw, SIDE, SIDE, dev)      # uploaded here, not in the first predict
         clips = torch.zeros(batch, T, 3, SIDE, SIDE, device=dev, dtype=torch.float32)
         if self.graphed:
             super().__init__(encoder, decoder, clips, with_mask=True)                # static_x is the clip batch
@@ -131,8 +213,11 @@ class VideoPredictor(GraphedForward):
     def predict(self, frames_u8, gt_u8=None, on_batch=None):
         """frames_u8 (N, Hs, Ws, 3) uint8, on the host or the device, 1 <= N <= max_frames (N need not be a multiple of `batch`)
         -> masks (N, 224, 224) uint8 with values 0 / 255 on the device: a view of the bank, valid until the next call.
-        gt_u8 (N, 224, 224) uint8 (> 0 counts as forged; the caller resizes annotations -- measure.py's BILINEAR resize of the
-        annotation is not part of this): the frame metrics of the N frames are added into the accumulator (`metric_vector`).
+        gt_u8 (N, 224, 224) uint8 (> 0 counts as forged), already resized by the caller -- or, in a predictor built with
+        gt_hw=(Hg, Wg), (N, Hg, Wg) uint8 at the annotations' own size, on the host or the device, holding the bytes
+        Image.open(...).convert('L') gives: measure.py's Image.resize((224, 224), BILINEAR) then runs on the device, bit for bit
+        (ops.resize_bilinear_u8), before the first batch.  The frame metrics of the N frames are added into the accumulator
+        (`metric_vector`).
         on_batch(b, logits, mask): called after batch b was issued, with the forward's static output buffers (logits (batch, 1, 224,
         224) float32 and the 0 / 1 mask) -- the next batch overwrites them.
         Everything is checked before anything is launched."""
@@ -145,7 +230,9 @@ class VideoPredictor(GraphedForward):
             raise ValueError(f"VideoPredictor.predict: {n} frames, but the banks hold max_frames={self.max_frames}")
         frames_u8 = self._u8(frames_u8, "frames", (n, *self.src_hw, 3))
         if gt_u8 is not None:
-            gt_u8 = self._u8(gt_u8, "gt", (n, SIDE, SIDE))
+            gt_u8 = self._u8(gt_u8, "gt", (n, *(self.gt_hw or (SIDE, SIDE))))
+            if self.gt_hw is not None and gt_u8.is_cuda and not gt_u8.is_contiguous():
+                raise ValueError("VideoPredictor.predict: gt on the device must be contiguous (it is resized where it is, never copied)")
         idx, dest = batch_plan(n, self.T, self.batch)
         nb = idx.shape[0]
         if self._uploaded is not None:
@@ -153,8 +240,10 @@ class VideoPredictor(GraphedForward):
         self._idx_host[:nb].copy_(torch.from_numpy(idx))
         self._dest_host[:nb].copy_(torch.from_numpy(dest))
         self.frames[:n].copy_(frames_u8, non_blocking=True)
-        if gt_u8 is not None:
+        if gt_u8 is not None and self.gt_hw is None:
             self.gt[:n].copy_(gt_u8.reshape(n, SIDE * SIDE), non_blocking=True)
+        elif gt_u8 is not None:
+            self._resize_gt(gt_u8, n)
         for b in range(nb):
             self.idx.copy_(self._idx_host[b], non_blocking=True)
             self.dest.copy_(self._dest_host[b], non_blocking=True)
@@ -166,6 +255,21 @@ class VideoPredictor(GraphedForward):
         if gt_u8 is not None:
             ops.frame_metrics(self.counts, n, SIDE * SIDE, acc=self.acc, accumulate=True)
         return self.bank[:n].view(n, SIDE, SIDE)
+
+    def _resize_gt(self, gt_u8, n):
+        """gt[:n] = Image.resize((224, 224), BILINEAR) of the annotations (ops.resize_bilinear_u8), issued on the current stream ahead
+        of the first batch: a device tensor straight from the caller's memory, a host tensor through the staging buffer, one upload
+        and one launch per gt_chunk frames (stream order keeps a chunk's upload behind the launch that read the one before)."""
+        from . import ops
+        bank = self.gt[:n].view(n, SIDE, SIDE)
+        if gt_u8.is_cuda:
+            ops.resize_bilinear_u8(gt_u8, (SIDE, SIDE), out=bank)
+            return
+        step = self._gt_stage.shape[0]
+        for i in range(0, n, step):
+            m = min(step, n - i)
+            self._gt_stage[:m].copy_(gt_u8[i:i + m], non_blocking=True)
+            ops.resize_bilinear_u8(self._gt_stage[:m], (SIDE, SIDE), out=bank[i:i + m])
 
     def metric_vector(self) -> torch.Tensor:
         """The device [sum F1, sum IoU, n] over every frame scored since the last reset: what evaluate.finalize_metrics takes."""
