@@ -40,6 +40,13 @@ def _grad_slot(p):
 _SLOTS_ON = [True]
 
 
+def _slot_2d(slot, n, k):
+    """The (N, K) image of a weight's gradient slot, or None where that image would be a copy (_grad_slot also returns 4-D slots that
+    are dense only as channels_last): a kernel would accumulate into the copy and the gradient would be lost, so such a slot takes
+    the route that returns dW to autograd."""
+    return slot.view(n, k) if slot is not None and slot.is_contiguous() else None
+
+
 class grad_slots:
     """Context manager: `with grad_slots(False):` makes every backward return its parameter gradients to autograd (no in-kernel
     accumulation into FlatAdamW's buffer) -- for torch.autograd.grad(inputs=[param]) and gradient inspection."""
@@ -99,7 +106,7 @@ def _linear_backward(x2, weight, dy2, params, need_dx, need_dw, need_db):
     dx = dw = db = None
     if (need_dx and not big) or need_dw or need_db:          # (a frozen Linear with a big input needs only the GEMM below)
         dx, dw, db = ops.linear_bwd(x2.contiguous(), weight, dy2, need_dx=need_dx and not big, need_dw=need_dw, need_db=need_db,
-                                    dw_out=wslot.reshape(n, k) if (need_dw and wslot is not None) else None,
+                                    dw_out=_slot_2d(wslot, n, k) if need_dw else None,
                                     db_out=bslot if need_db else None)
     if big:
         dx = ops.linear(dy2, ops.transpose(weight))
@@ -205,7 +212,7 @@ class MlpFn(torch.autograd.Function):
         elif need_dz or need_dw2 or need_db2:                    # the one gated call at every M (profiles/mlp_fused_train.md)
             w2slot, b2slot = _grad_slot(ctx.params[2]), _grad_slot(ctx.params[3])
             dz, dw2, db2 = ops.linear_gelu_bwd(a2, z2, w2, dy2, need_dz=need_dz, need_dw=need_dw2, need_db=need_db2,
-                                               dw_out=w2slot.reshape(n2, hid) if (need_dw2 and w2slot is not None) else None,
+                                               dw_out=_slot_2d(w2slot, n2, hid) if need_dw2 else None,
                                                db_out=b2slot if need_db2 else None)
         dx = dw1 = db1 = None
         if need_dz:

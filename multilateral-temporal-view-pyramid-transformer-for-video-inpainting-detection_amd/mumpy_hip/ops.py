@@ -100,6 +100,34 @@ def _opt(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
     return None if t is None else _chk(t, name)
 
 
+def _rd(t: torch.Tensor, name: str, numel: int, who: str, dtype=torch.float32) -> torch.Tensor:
+    """A read operand, measured against the launch that will read it: on the GPU, of the dtype the kernel reads, exactly `numel`
+    elements.  A non-contiguous one is copied (the copy is read, nothing is lost).  A handful of integer comparisons."""
+    if not t.is_cuda or t.dtype != dtype or t.numel() != numel:
+        raise RuntimeError(f"mumpy_hip: {who} needs {name} as a {dtype} GPU tensor of {numel} elements, got {t.dtype} {tuple(t.shape)} "
+                           f"on {t.device}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _rd_opt(t: Optional[torch.Tensor], name: str, numel: int, who: str) -> Optional[torch.Tensor]:
+    return None if t is None else _rd(t, name, numel, who)
+
+
+def _wr(t: torch.Tensor, name: str, numel: int, who: str, dtype=torch.float32) -> torch.Tensor:
+    """A buffer a kernel writes or accumulates into (out=, *_out, optimizer state): taken where it is or refused -- a copy would
+    receive the result and be dropped.  Where the wrapper knows the exact shape it uses _chk_exact instead."""
+    if not t.is_cuda or t.dtype != dtype or t.numel() != numel or not t.is_contiguous():
+        raise RuntimeError(f"mumpy_hip: {who} writes {name} in place and needs a contiguous {dtype} GPU tensor of {numel} elements, got "
+                           f"{t.dtype} {tuple(t.shape)} on {t.device}{'' if t.is_contiguous() else ' (not contiguous)'}")
+    return t
+
+
+def _drop_ln_stats(t: torch.Tensor) -> None:
+    """t is about to be overwritten: the LayerNorm-fold statistics a producer attached to it describe the old contents."""
+    if hasattr(t, "_mumpy_ln_stats"):
+        del t._mumpy_ln_stats
+
+
 def _ws_bytes(key, fn_name, *args):
     """Workspace size of a launch (in the library a pure host function of the shape), asked once per shape."""
     wsb = _WS_BYTES.get(key)
@@ -119,7 +147,8 @@ def layernorm_bf16(x, gamma, beta, eps=1e-5):
     x = _chk(x, "x")
     c = x.shape[-1]
     out = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    _call("mumpy_layernorm_bf16_fwd", _p(x), _p(_chk(gamma, "gamma")), _p(_chk(beta, "beta")), _p(out), x.numel() // c, c, eps,
+    gamma, beta = _rd(gamma, "gamma", c, "layernorm_bf16"), _rd(beta, "beta", c, "layernorm_bf16")
+    _call("mumpy_layernorm_bf16_fwd", _p(x), _p(gamma), _p(beta), _p(out), x.numel() // c, c, eps,
           _stream(), work=6.0 * x.numel())
     return out
 
@@ -136,7 +165,7 @@ def linear_bf16s(x16, w16, bias=None, act=ACT_NONE, residual=None, out_bf16=True
         residual = _chk(residual, "residual")
         if residual.numel() != m * n or out_bf16:
             raise RuntimeError("linear_bf16s: the residual is fp32 and needs an fp32 output of the same shape")
-    _call("mumpy_linear_bf16s_fwd", _p(x16), _p(w16), _p(_opt(bias, "bias")), _p(residual), _p(out),
+    _call("mumpy_linear_bf16s_fwd", _p(x16), _p(w16), _p(_rd_opt(bias, "bias", n, "linear_bf16s")), _p(residual), _p(out),
           m, n, k, act, 1 if out_bf16 else 0, _stream(), work=2.0 * m * n * k)
     return out
 
@@ -247,11 +276,30 @@ def _window_attention(entry, chk, dtype, who, qkv, bias_pad, b, hs, w, c, shift,
     qkv = chk(qkv, "qkv")
     if qkv.numel() != b * hs * w * 3 * c:
         raise RuntimeError(f"{who}: qkv shape mismatch")
-    out = torch.empty(b, hs * w, c, device=qkv.device, dtype=dtype) if out is None else out
-    n_mask = 0 if mask_id is None else mask_id.numel()
-    _call(entry, _p(qkv), _p(out), _p(_chk(bias_pad, "bias")), _p(mask_tab), _p(mask_id), n_mask,
+    out = torch.empty(b, hs * w, c, device=qkv.device, dtype=dtype) if out is None else _chk_exact(out, "out", dtype, (b, hs * w, c), who)
+    bias_pad = _rd(bias_pad, "bias", (c // 32) * 64 * 64, who)
+    mask_tab, mask_id, n_mask = _chk_mask(mask_tab, mask_id, b * (hs // 7) * (w // 7), who)
+    _call(entry, _p(qkv), _p(out), _p(bias_pad), _p(mask_tab), _p(mask_id), n_mask,
           b, hs, w, c, shift, scale, _stream(), work=307328.0 * b * (hs // 7) * (w // 7) * (c // 32))
     return out
+
+
+def _chk_mask(mask_tab, mask_id, nwin, who):
+    """The shifted-window mask operands -> (mask_tab, mask_id, n_mask): mask_id int32 (the kernel reads mask_id[window % n_mask],
+    4 bytes each: an int64 tensor would be read as pairs) with n_mask dividing the nwin windows of the launch (the broadcast of
+    swin:155), mask_tab whole (64, 64) fp32 patterns.  How many patterns the ids refer to is device data: that the table holds them
+    all is the word of compact_attn_mask."""
+    if mask_id is None:
+        if mask_tab is not None:
+            raise RuntimeError(f"mumpy_hip: {who}: mask_tab needs mask_id")
+        return None, None, 0
+    n_mask = mask_id.numel()
+    if n_mask < 1 or nwin % n_mask:
+        raise RuntimeError(f"mumpy_hip: {who}: {n_mask} mask ids do not divide the {nwin} windows of the launch")
+    mask_id = _rd(mask_id, "mask_id", n_mask, who, torch.int32)
+    if mask_tab is None or mask_tab.numel() < 4096 or mask_tab.numel() % 4096:
+        raise RuntimeError(f"mumpy_hip: {who} needs mask_tab (nU, 64, 64) with mask_id")
+    return _rd(mask_tab, "mask_tab", mask_tab.numel(), who), mask_id, n_mask
 
 
 def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, math=None):
@@ -269,8 +317,12 @@ def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=N
 def layernorm(x, gamma, beta, eps=1e-5, out=None):
     x = _chk(x, "x")
     c = x.shape[-1]
-    out = torch.empty_like(x) if out is None else out
-    _call("mumpy_layernorm_fwd", _p(x), _p(_chk(gamma, "gamma")), _p(_chk(beta, "beta")), _p(out), x.numel() // c, c,
+    gamma, beta = _rd(gamma, "gamma", c, "layernorm"), _rd(beta, "beta", c, "layernorm")
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _drop_ln_stats(_wr(out, "out", x.numel(), "layernorm"))
+    _call("mumpy_layernorm_fwd", _p(x), _p(gamma), _p(beta), _p(out), x.numel() // c, c,
           eps, _stream(), work=8.0 * x.numel())
     return out
 
@@ -287,12 +339,11 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, out=None, emit_sta
     m = x.numel() // k
     if out is None:
         out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=torch.float32)
-    if residual is not None:
-        residual = _chk(residual, "residual")
-        if residual.numel() != m * n:
-            raise RuntimeError("linear: residual shape mismatch")
+    else:
+        _drop_ln_stats(_wr(out, "out", m * n, "linear"))
+    residual, bias = _rd_opt(residual, "residual", m * n, "linear"), _rd_opt(bias, "bias", n, "linear")
     if _in_background():
-        _call("mumpy_linear_rd_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(residual), _p(out), m, n, k,
+        _call("mumpy_linear_rd_fwd", _p(x), _p(weight), _p(bias), _p(residual), _p(out), m, n, k,
               act, _stream(), work=2.0 * m * n * k)
         return out
     wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
@@ -304,12 +355,12 @@ def linear(x, weight, bias=None, act=ACT_NONE, residual=None, out=None, emit_sta
         if gn:
             stats = torch.empty(m, gn, 2, device=x.device, dtype=torch.float32)
             ws = _kept_workspace(max(wsb, 4096), x.device)
-            _call("mumpy_linear_lnx_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(residual), _p(out), m, n, k,
+            _call("mumpy_linear_lnx_fwd", _p(x), _p(weight), _p(bias), _p(residual), _p(out), m, n, k,
                   act, _p(ws), ws.numel() * 4, _p(stats), None, 0, None, 0.0, _stream(), work=2.0 * m * n * k)
             out._mumpy_ln_stats = stats
             return out
     ws = _kept_workspace(wsb, x.device) if wsb else None      # split-K slabs / the persistent kernel's flags + slabs
-    _call("mumpy_linear_wsz_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(residual),
+    _call("mumpy_linear_wsz_fwd", _p(x), _p(weight), _p(bias), _p(residual),
           _p(out), m, n, k, act | _MATH, _p(ws), 0 if ws is None else ws.numel() * 4, _stream(), work=2.0 * m * n * k)
     return out
 
@@ -368,12 +419,17 @@ def linear_ln(x, stats, wg, colsum, bprime, eps, act=ACT_NONE):
     colsum = row sums of wg, bprime = W beta + b (see fold_ln_weights).  The caller checked linear_ln_tiles(m, n, k) > 0."""
     x, wg = _chk(x, "x"), _chk(wg, "wg")
     n, k = wg.shape
+    if x.shape[-1] != k:
+        raise RuntimeError(f"linear_ln: x has {x.shape[-1]} features, wg expects {k}")
     m = x.numel() // k
+    if stats.dim() != 3 or stats.shape[0] != m or stats.shape[2] != 2 or stats.shape[1] < 1:
+        raise RuntimeError(f"linear_ln: stats must be ({m}, tiles, 2), got {tuple(stats.shape)}")
+    stats, colsum, bprime = _rd(stats, "stats", stats.numel(), "linear_ln"), _rd(colsum, "colsum", n, "linear_ln"), _rd(bprime, "bprime", n, "linear_ln")
     out = torch.empty(*x.shape[:-1], n, device=x.device, dtype=torch.float32)
     wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
     ws = _kept_workspace(max(wsb, 4096), x.device)
-    _call("mumpy_linear_lnx_fwd", _p(x), _p(wg), _p(_chk(bprime, "bprime")), None, _p(out), m, n, k, act, _p(ws), ws.numel() * 4, None,
-          _p(_chk(stats, "stats")), stats.shape[-2], _p(_chk(colsum, "colsum")), eps, _stream(), work=2.0 * m * n * k)
+    _call("mumpy_linear_lnx_fwd", _p(x), _p(wg), _p(bprime), None, _p(out), m, n, k, act, _p(ws), ws.numel() * 4, None,
+          _p(stats), stats.shape[-2], _p(colsum), eps, _stream(), work=2.0 * m * n * k)
     return out
 
 
@@ -455,13 +511,18 @@ def linear_rows(x_view, weight, bias=None, residual=None, out=None):
         raise RuntimeError("linear_rows: rows of a block must be contiguous")
     weight = _chk(weight, "weight")
     n = weight.shape[0]
+    if weight.numel() != n * k:
+        raise RuntimeError(f"linear_rows: x has {k} features, weight {tuple(weight.shape)}")
     m = nblk * rows
+    bias, residual = _rd_opt(bias, "bias", n, "linear_rows"), _rd_opt(residual, "residual", m * n, "linear_rows")
     if out is None:
         out = torch.empty(m, n, device=x_view.device, dtype=torch.float32)
+    else:
+        _drop_ln_stats(_wr(out, "out", m * n, "linear_rows"))
     wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
     ws = torch.empty(wsb // 4, device=x_view.device, dtype=torch.float32) if wsb else None
-    _call("mumpy_linear_rows_fwd", x_view.data_ptr(), rows, x_view.stride(0), _p(weight),
-          _p(_opt(bias, "bias")), _p(residual), _p(out), m, n, k, ACT_NONE | _MATH, _p(ws), wsb, _stream(),
+    _call("mumpy_linear_rows_fwd", _p(x_view), rows, x_view.stride(0), _p(weight),
+          _p(bias), _p(residual), _p(out), m, n, k, ACT_NONE | _MATH, _p(ws), wsb, _stream(),
           work=2.0 * m * n * k)
     return out
 
@@ -476,11 +537,10 @@ def linear_time_slices(x4, weight, bias=None, residual=None):
         raise RuntimeError(f"linear_time_slices: weight expects K = T*C = {t * c} (got {k}); C % 32 == 0")
     m = b * n
     out = torch.empty(m, nout, device=x4.device, dtype=torch.float32)
-    if residual is not None:
-        residual = _chk(residual, "residual")
+    residual, bias = _rd_opt(residual, "residual", m * nout, "linear_time_slices"), _rd_opt(bias, "bias", nout, "linear_time_slices")
     wsb = _ws_bytes((m, nout, k), "mumpy_linear_workspace_bytes", m, nout, k)
     ws = torch.empty(wsb // 4, device=x4.device, dtype=torch.float32) if wsb else None
-    _call("mumpy_linear_rows_kseg_fwd", _p(x4), n, t * n * c, c, n * c, _p(weight), _p(_opt(bias, "bias")),
+    _call("mumpy_linear_rows_kseg_fwd", _p(x4), n, t * n * c, c, n * c, _p(weight), _p(bias),
           _p(residual), _p(out), m, nout, k, ACT_NONE | _MATH, _p(ws), wsb, _stream(), work=2.0 * m * nout * k)
     return out
 
@@ -497,9 +557,12 @@ def conv2d_nhwc(x, w_krsc, bias=None, act=ACT_NONE, residual=None):
     out = empty_nhwc(b, cout, h, w, x.device)
     if residual is not None:
         residual = _nhwc(residual, "residual")
+        if tuple(residual.shape) != (b, cout, h, w):
+            raise RuntimeError(f"conv2d: residual {tuple(residual.shape)} != output {(b, cout, h, w)}")
+    bias = _rd_opt(bias, "bias", cout, "conv2d")
     wsb = _ws_bytes(("conv", b, h, w, cin, cout, kh, kw), "mumpy_conv2d_workspace_bytes", b, h, w, cin, cout, kh, kw)
     ws = torch.empty(wsb // 4, device=x.device, dtype=torch.float32) if wsb else None
-    _call("mumpy_conv2d_nhwc_fwd", _p(x), _p(w_krsc), _p(_opt(bias, "bias")), _p(residual), _p(out),
+    _call("mumpy_conv2d_nhwc_fwd", _p(x), _p(w_krsc), _p(bias), _p(residual), _p(out),
           b, h, w, cin, cout, kh, kw, act | _MATH, _p(ws), wsb, _stream(), work=2.0 * b * h * w * cout * kh * kw * cin)
     return out
 
@@ -512,7 +575,8 @@ def final_conv(x, w_krsc, bias, with_mask=False, thr=0.5):
         raise RuntimeError(f"final_conv is built for Conv2d(32k, 1, 3, padding=1); got C={c}, weight {tuple(w_krsc.shape)}")
     logits = torch.empty(b, 1, h, w, device=x.device, dtype=torch.float32)
     mask = torch.empty(b, 1, h, w, device=x.device, dtype=torch.uint8) if with_mask else None
-    _call("mumpy_final_conv_fwd", _p(x), _p(_chk(w_krsc, "weight")), _p(_chk(bias, "bias")), _p(logits), _p(mask), b, h, w, c, thr,
+    w_krsc, bias = _chk(w_krsc, "weight"), _rd(bias, "bias", 1, "final_conv")
+    _call("mumpy_final_conv_fwd", _p(x), _p(w_krsc), _p(bias), _p(logits), _p(mask), b, h, w, c, thr,
           _stream(), work=4.0 * (x.numel() + logits.numel()))
     return (logits, mask) if with_mask else logits
 
@@ -561,14 +625,23 @@ def gn_apply_resample(x, gn=None, act=0, mean4=False, scale=1, align_corners=Fal
     if out is None:
         out = empty_nhwc(b, cout, ho, wo, x.device)
     else:
-        assert out.shape[0] == b and out.shape[2] == ho and out.shape[3] == wo and out.stride(1) == 1
+        ctot = out.shape[1] if out.dim() == 4 else -1
+        if not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (b, ctot, ho, wo) or \
+                out.stride() != (ho * wo * ctot, 1, wo * ctot, ctot) or out_coff < 0 or out_coff + cout > ctot:
+            raise RuntimeError(f"mumpy_hip: gn_apply_resample writes out in place and needs a dense NHWC float32 GPU map ({b}, >= "
+                               f"{out_coff + cout}, {ho}, {wo}), got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
     if ep_a is not None:
         ep_a = _nhwc(ep_a, "ep_a")
-        assert tuple(ep_a.shape) == (b, cout, ho, wo), "epilogue operand shape"
+        if tuple(ep_a.shape) != (b, cout, ho, wo):
+            raise RuntimeError(f"gn_apply_resample: epilogue operand {tuple(ep_a.shape)} != output {(b, cout, ho, wo)}")
     if ep_b is not None:
         ep_b = _nhwc(ep_b, "ep_b")
-        assert tuple(ep_b.shape) == (b, cout, ho, wo), "epilogue operand shape"
+        if tuple(ep_b.shape) != (b, cout, ho, wo):
+            raise RuntimeError(f"gn_apply_resample: epilogue operand {tuple(ep_b.shape)} != output {(b, cout, ho, wo)}")
     partial, nsplit, gamma, beta, groups, eps = gn if gn is not None else (None, 0, None, None, 1, 0.0)
+    if gn is not None:
+        partial = _rd(partial, "partial", b * nsplit * groups * 2, "gn_apply_resample")
+        gamma, beta = _rd(gamma, "gamma", c, "gn_apply_resample"), _rd(beta, "beta", c, "gn_apply_resample")
     _call("mumpy_gn_apply_resample_nhwc_fwd", _p(x), _p(partial), nsplit, _p(gamma), _p(beta), groups, eps, act,
           1 if mean4 else 0, scale, 1 if align_corners else 0, ep_mode, _p(ep_a), _p(ep_b), _p(out), out.shape[1], out_coff,
           b, h, w, c, _stream(), work=4.0 * (x.numel() + b * cout * ho * wo))
@@ -594,7 +667,13 @@ def copy_rows(src, src_stride, dst, dst_stride, rows, cols):
     """dst[r, :cols] = src[r, :cols] for r < rows, row pitches in floats; src / dst are tensors whose data_ptr() is row 0."""
     if not (src.is_cuda and dst.is_cuda and src.dtype == dst.dtype == torch.float32):
         raise RuntimeError("mumpy_hip: copy_rows needs float32 GPU tensors (there is no CPU path)")
-    _call("mumpy_copy_rows_fwd", src.data_ptr(), src_stride, dst.data_ptr(), dst_stride, rows, cols, _stream(), work=8.0 * rows * cols)
+    for name, t, pitch in (("src", src, src_stride), ("dst", dst, dst_stride)):
+        if t.numel() > 1 and not any(st == 1 for sz, st in zip(t.shape, t.stride()) if sz > 1):
+            raise RuntimeError(f"mumpy_hip: copy_rows: {name} has no dense dimension (strides {t.stride()}): its rows are not contiguous")
+        if rows < 1 or cols < 1 or pitch < cols or t.storage_offset() + (rows - 1) * pitch + cols > t.untyped_storage().nbytes() // 4:
+            raise RuntimeError(f"mumpy_hip: copy_rows: {rows} rows of {cols} floats at a pitch of {pitch} do not fit into {name}'s storage")
+    _drop_ln_stats(dst)
+    _call("mumpy_copy_rows_fwd", _p(src), src_stride, _p(dst), dst_stride, rows, cols, _stream(), work=8.0 * rows * cols)
     return dst
 
 
@@ -603,8 +682,9 @@ def set_channels(dst, coff, src):
     src may be any per-pixel-contiguous strided view whose pixels are uniformly pitched (e.g. the first 3 of 5 temporal slices)."""
     b, c, h, w = src.shape
     ctot = dst.shape[1]
-    if dst.stride() != (h * w * ctot, 1, w * ctot, ctot) or tuple(dst.shape[2:]) != (h, w) or dst.shape[0] != b:
-        raise RuntimeError("set_channels: dst must be a dense NHWC map of the same batch and size")
+    if dst.stride() != (h * w * ctot, 1, w * ctot, ctot) or tuple(dst.shape[2:]) != (h, w) or dst.shape[0] != b or coff < 0 or coff + c > ctot:
+        raise RuntimeError("set_channels: dst must be a dense NHWC map of the same batch and size that holds channels [coff, coff + C)")
+    _drop_ln_stats(dst)
     pitch = src.stride(3)
     if src.stride(1) != 1 or src.stride(2) != w * pitch or (b > 1 and src.stride(0) != h * w * pitch) or pitch < c:
         src = _nhwc(src, "src")
@@ -617,6 +697,8 @@ def merge_views(views, token_t, n=49):
     v = [_chk(t, "view") for t in views]
     b = v[0].shape[0]
     tmax = max(token_t)
+    if len(v) != 3 or any(t.dim() != 3 or t.shape[0] != b or t.shape[1] != tv * n for t, tv in zip(v, token_t)):
+        raise RuntimeError(f"merge_views: three views (B, t_v * {n}, C_v) of one batch, got {[tuple(t.shape) for t in v]} for t_v = {list(token_t)}")
     out = torch.empty(b * n * tmax, sum(t.shape[2] for t in v), device=v[0].device, dtype=torch.float32)
     _call("mumpy_merge_views_fwd", _p(v[0]), _p(v[1]), _p(v[2]), _p(out), b, tmax, n, v[0].shape[2], v[1].shape[2], v[2].shape[2],
           token_t[0], token_t[1], token_t[2], _stream(), work=8.0 * out.numel())
@@ -636,8 +718,12 @@ def trunk_head(g, f, gcn, freq):
 
 
 def add(a, b, out=None):
-    a, b = _chk(a, "a"), _chk(b, "b")
-    out = torch.empty_like(a) if out is None else out
+    a = _chk(a, "a")
+    b = _rd(b, "b", a.numel(), "add")
+    if out is None:
+        out = torch.empty_like(a)
+    else:
+        _drop_ln_stats(_wr(out, "out", a.numel(), "add"))
     _call("mumpy_add_fwd", _p(a), _p(b), _p(out), a.numel(), _stream())
     return out
 
@@ -662,6 +748,9 @@ def expand_relpos_bias(table: torch.Tensor, index: torch.Tensor) -> torch.Tensor
     if not index.is_cuda:
         index = index.to(table.device)
     idx = index if index.dtype == torch.int32 and index.dim() == 1 else rel_index32(index)
+    idx = _rd(idx, "index", 49 * 49, "expand_relpos_bias", torch.int32)
+    if table.dim() != 2 or table.shape[0] != 169:
+        raise RuntimeError(f"expand_relpos_bias: table must be (169, nH), got {tuple(table.shape)}")
     out = torch.empty(nh, 64, 64, device=table.device, dtype=torch.float32)
     _call("mumpy_relpos_bias_expand_fwd", _p(table), _p(idx), _p(out), nh, _stream())
     return out
@@ -711,19 +800,23 @@ def window_attention_mm16(qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab=Non
 
 
 def deform_offsets(q, dw_w, dw_b, ln_g, ln_b, pw_w, b, h, w, c):
-    q = _chk(q, "q")
+    who = "deform_offsets"
+    q = _rd(q, "q", b * h * w * c, who)
     nwin = b * (h // 7) * (w // 7)
+    cg = c // 3                                                           # the offset network works per group of C / 3 channels
+    dw_w, dw_b = _rd(dw_w, "dw_w", cg * 25, who), _rd(dw_b, "dw_b", cg, who)
+    ln_g, ln_b, pw_w = _rd(ln_g, "ln_g", cg, who), _rd(ln_b, "ln_b", cg, who), _rd(pw_w, "pw_w", 2 * cg, who)
     pos = torch.empty(nwin, 3, 49, 2, device=q.device, dtype=torch.float32)
-    _call("mumpy_deform_offsets_fwd", _p(q), _p(_chk(dw_w, "dw_w")), _p(_chk(dw_b, "dw_b")), _p(_chk(ln_g, "ln_g")),
-          _p(_chk(ln_b, "ln_b")), _p(_chk(pw_w, "pw_w")), _p(pos), b, h, w, c, _stream())
+    _call("mumpy_deform_offsets_fwd", _p(q), _p(dw_w), _p(dw_b), _p(ln_g),
+          _p(ln_b), _p(pw_w), _p(pos), b, h, w, c, _stream())
     return pos
 
 
 def deform_sample(x2, pos, b, hs2, w, c, nq):
-    x2 = _chk(x2, "x2")
+    x2, pos = _rd(x2, "x2", b * hs2 * w * c, "deform_sample"), _rd(pos, "pos", nq * 3 * 49 * 2, "deform_sample")
     nw2 = b * (hs2 // 7) * (w // 7)
     out = torch.empty(nw2, 49, c, device=x2.device, dtype=torch.float32)
-    _call("mumpy_deform_sample_fwd", _p(x2), _p(_chk(pos, "pos")), _p(out), b, hs2, w, c, nq, _stream(),
+    _call("mumpy_deform_sample_fwd", _p(x2), _p(pos), _p(out), b, hs2, w, c, nq, _stream(),
           work=4.0 * (2 * nw2 * 49 * c + nw2 * 3 * 49 * 2))       # bytes: read kv once, write sampled once, read offsets
     return out
 
@@ -732,10 +825,12 @@ def deform_sample_kv(x2, pos, wkv, bkv, b, hs2, w, c, nq, math="fp32"):
     """[proj_k | proj_v] of the bilinearly sampled kv windows in one launch (the sampled map is never materialised).
     math="bf16": the fp32 sample and wkv are rounded to bf16 while staged and multiplied on the bf16 MFMA (see set_cva_math)."""
     entry = _mm16("mumpy_deform_sample_kv_fwd", math)
-    x2 = _chk(x2, "x2")
+    who = "deform_sample_kv"
+    x2, pos = _rd(x2, "x2", b * hs2 * w * c, who), _rd(pos, "pos", nq * 3 * 49 * 2, who)
+    wkv, bkv = _rd(wkv, "wkv", 2 * c * c, who), _rd(bkv, "bkv", 2 * c, who)
     nw2 = b * (hs2 // 7) * (w // 7)
     kv = torch.empty(nw2, 49, 2 * c, device=x2.device, dtype=torch.float32)
-    _call(entry, _p(x2), _p(_chk(pos, "pos")), _p(_chk(wkv, "wkv")), _p(_chk(bkv, "bkv")), _p(kv), b, hs2, w, c, nq,
+    _call(entry, _p(x2), _p(pos), _p(wkv), _p(bkv), _p(kv), b, hs2, w, c, nq,
           _stream(), work=2.0 * nw2 * 49 * 2 * c * c)
     return kv
 
@@ -744,9 +839,11 @@ def deform_out_combine(o, wout, bout, x1, b, h, w, c, math="fp32"):
     """x1 + x1[window order] + scrambled proj_out(o) in one launch (replaces linear + deform_combine).
     math="bf16": wout and o are rounded to bf16 while staged and multiplied on the bf16 MFMA; the epilogue stays fp32."""
     entry = _mm16("mumpy_deform_out_combine_fwd", math)
-    o, x1 = _chk(o, "o"), _chk(x1, "x1")
+    who = "deform_out_combine"
+    o, x1 = _rd(o, "o", b * h * w * c, who), _rd(x1, "x1", b * h * w * c, who)
+    wout, bout = _rd(wout, "wout", c * c, who), _rd(bout, "bout", c, who)
     out = torch.empty_like(x1)
-    _call(entry, _p(o), _p(_chk(wout, "wout")), _p(_chk(bout, "bout")), _p(x1), _p(out), b, h, w, c, _stream(),
+    _call(entry, _p(o), _p(wout), _p(bout), _p(x1), _p(out), b, h, w, c, _stream(),
           work=2.0 * o.numel() * c)
     return out
 
@@ -757,18 +854,17 @@ def deform_attention(q, kv, padmask, b, h, w, c, r, scale, math="fp32"):
     backward) pass it.  math="bf16": q / k / v rounded to bf16 in registers, both products on the bf16 MFMA, fp32 softmax and
     accumulation; its backward is deform_attention_bwd(..., math="bf16")."""
     entry = _mm16("mumpy_deform_attention_fwd", math)
-    q, kv = _chk(q, "q"), _chk(kv, "kv")
     b1w = b * (h // 7) * (w // 7)
-    if kv.numel() != b1w * r * 49 * 2 * c:
-        raise RuntimeError("deform_attention: kv shape mismatch")
+    q, kv = _rd(q, "q", b * h * w * c, "deform_attention"), _rd(kv, "kv", b1w * r * 49 * 2 * c, "deform_attention")
+    padmask = _rd(padmask, "padmask", 64 * 64, "deform_attention")
     out = torch.empty(b1w, 49, c, device=q.device, dtype=torch.float32)
-    _call(entry, _p(q), _p(kv), _p(_chk(padmask, "padmask")), _p(out), b, h, w, c, r, scale,
+    _call(entry, _p(q), _p(kv), _p(padmask), _p(out), b, h, w, c, r, scale,
           _stream(), work=307328.0 * b1w * r * (c // 32))
     return out
 
 
 def deform_combine(x1, yt, b, h, w, c):
-    x1, yt = _chk(x1, "x1"), _chk(yt, "yt")
+    x1, yt = _rd(x1, "x1", b * h * w * c, "deform_combine"), _rd(yt, "yt", b * h * w * c, "deform_combine")
     out = torch.empty_like(x1)
     _call("mumpy_deform_combine_fwd", _p(x1), _p(yt), _p(out), b, h, w, c, _stream())
     return out
@@ -781,7 +877,8 @@ def faf(x, d, dt, frame, lo_hi, mid_lo, mid_hi):
         raise RuntimeError(f"faf: expects (B,T,3,224,224) clips (dct.py:57,72), got {tuple(x.shape)}")
     scratch = torch.empty(b, 3, 224, 224, device=x.device, dtype=torch.float32)
     out = torch.empty(b, 9, 224, 224, device=x.device, dtype=torch.float32)
-    _call("mumpy_faf_fwd", _p(x), _p(_chk(d, "D")), _p(_chk(dt, "Dt")), _p(scratch), _p(out), b, t, frame, lo_hi, mid_lo,
+    d, dt = _rd(d, "D", 224 * 224, "faf"), _rd(dt, "Dt", 224 * 224, "faf")
+    _call("mumpy_faf_fwd", _p(x), _p(d), _p(dt), _p(scratch), _p(out), b, t, frame, lo_hi, mid_lo,
           mid_hi, _stream())
     return out
 
@@ -790,25 +887,30 @@ def patch_embed(x, wt, bias, gamma, beta, t, eps=1e-5):
     """x (B,T,3,H,W), wt (48t, C) -> (B, t_out*H/4*W/4, C)."""
     x = _chk(x, "x")
     b, tt, _, h, w = x.shape
+    if wt.dim() != 2 or wt.shape[0] != 48 * t or x.shape[2] != 3:
+        raise RuntimeError(f"patch_embed: x (B,T,3,H,W) and wt (48 t, C) for t = {t}, got {tuple(x.shape)} and {tuple(wt.shape)}")
     c = wt.shape[1]
+    wt, bias = _rd(wt, "wt", 48 * t * c, "patch_embed"), _rd(bias, "bias", c, "patch_embed")
+    gamma, beta = _rd(gamma, "gamma", c, "patch_embed"), _rd(beta, "beta", c, "patch_embed")
     t_out = (tt - t) // t + 1
     out = torch.empty(b, t_out * (h // 4) * (w // 4), c, device=x.device, dtype=torch.float32)
-    _call("mumpy_patch_embed_fwd", _p(x), _p(_chk(wt, "wt")), _p(_chk(bias, "bias")), _p(_chk(gamma, "gamma")),
-          _p(_chk(beta, "beta")), _p(out), b, tt, h, w, t, c, eps, _stream())
+    _call("mumpy_patch_embed_fwd", _p(x), _p(wt), _p(bias), _p(gamma),
+          _p(beta), _p(out), b, tt, h, w, t, c, eps, _stream())
     return out
 
 
 def patch_merge_ln(x, gamma, beta, b, hs, w, c, eps=1e-5):
-    x = _chk(x, "x")
+    x = _rd(x, "x", b * hs * w * c, "patch_merge_ln")
+    gamma, beta = _rd(gamma, "gamma", 4 * c, "patch_merge_ln"), _rd(beta, "beta", 4 * c, "patch_merge_ln")
     out = torch.empty(b, (hs // 2) * (w // 2), 4 * c, device=x.device, dtype=torch.float32)
-    _call("mumpy_patch_merge_ln_fwd", _p(x), _p(_chk(gamma, "gamma")), _p(_chk(beta, "beta")), _p(out), b, hs, w, c, eps,
+    _call("mumpy_patch_merge_ln_fwd", _p(x), _p(gamma), _p(beta), _p(out), b, hs, w, c, eps,
           _stream())
     return out
 
 
 def temporal_attention(qkv, s, t, c, heads, scale, tq=None):
     """tq: number of leading temporal tokens that are queries (default all): out (s, tq, c)."""
-    qkv = _chk(qkv, "qkv")
+    qkv = _rd(qkv, "qkv", s * t * 3 * c, "temporal_attention")
     tq = t if tq is None else tq
     out = torch.empty(s, tq, c, device=qkv.device, dtype=torch.float32)
     _call("mumpy_temporal_attention_q_fwd", _p(qkv), _p(out), s, t, tq, c, heads, scale, _stream())
@@ -819,10 +921,15 @@ def attention_probs(q, k, outer, heads, nq, nk, d, q_strides, k_strides, scale, 
     """softmax(scale * q k^T) maps (outer, heads, nq, nk) for the `return_attention=True` variants; q_strides / k_strides =
     (outer stride, row stride) in floats, head h adds h * d; q_mod: q outer index = outer % q_mod."""
     for t in (q, k):                      # views into a larger tensor are fine: addressing is by the strides given (no copy)
-        if not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError("mumpy_hip: attention_probs needs float32 GPU tensors (there is no CPU path)")
+        if not t.is_cuda or t.dtype != torch.float32 or t.stride(-1) != 1:
+            raise RuntimeError("mumpy_hip: attention_probs needs float32 GPU tensors with a dense last dimension (there is no CPU path)")
+    q_outer = outer if q_mod is None else q_mod
+    for name, t, rows, n_outer, st in (("q", q, nq, q_outer, q_strides), ("k", k, nk, outer, k_strides)):
+        last = (n_outer - 1) * st[0] + (rows - 1) * st[1] + heads * d          # one past the last float the launch reads, from data_ptr()
+        if min(st) < 0 or t.storage_offset() + last > t.untyped_storage().nbytes() // 4:
+            raise RuntimeError(f"mumpy_hip: attention_probs: the strides given reach past the end of {name}'s storage")
     out = torch.empty(outer, heads, nq, nk, device=q.device, dtype=torch.float32)
-    _call("mumpy_attention_probs_fwd", q.data_ptr(), k.data_ptr(), _p(out), outer, heads, nq, nk, d, q_strides[0], q_strides[1], k_strides[0],
+    _call("mumpy_attention_probs_fwd", _p(q), _p(k), _p(out), outer, heads, nq, nk, d, q_strides[0], q_strides[1], k_strides[0],
           k_strides[1], outer if q_mod is None else q_mod, scale, _stream())
     return out
 
@@ -1076,6 +1183,8 @@ def mask_loss(logits, target, need_grad=True, eps=0.0, loss_scale=1.0):
     logits = _chk(logits, "logits")
     b = logits.shape[0]
     p = logits.numel() // b
+    if target.numel() != b * p:
+        raise RuntimeError(f"mask_loss: target has {target.numel()} elements, logits {b} x {p}")
     target = _chk(target.to(torch.float32).reshape(b, p), "target")
     loss3 = torch.empty(3, device=logits.device, dtype=torch.float32)
     dz = torch.empty_like(logits) if need_grad else None
@@ -1107,9 +1216,10 @@ def layernorm_bwd(x, gamma, dy, eps=1e-5, dx_add=None, dg_out=None, db_out=None)
     """-> (dx like x, dgamma (C), dbeta (C)) of nn.LayerNorm over the last dim.  dx_add: a gradient to add to dx (the residual
     branch that bypasses the norm).  dg_out / db_out (both or neither): gradient buffers to ACCUMULATE into; the matching
     return values are then None."""
-    x, dy, gamma = _chk(x, "x"), _chk(dy, "dy"), _chk(gamma, "gamma")
+    x = _chk(x, "x")
     c = x.shape[-1]
     rows = x.numel() // c
+    dy, gamma = _rd(dy, "dy", x.numel(), "layernorm_bwd"), _rd(gamma, "gamma", c, "layernorm_bwd")
     dx = torch.empty_like(x)
     if dx_add is not None:
         dx_add = _chk(dx_add, "dx_add")
@@ -1118,8 +1228,8 @@ def layernorm_bwd(x, gamma, dy, eps=1e-5, dx_add=None, dg_out=None, db_out=None)
     if (dg_out is None) != (db_out is None):
         raise RuntimeError("layernorm_bwd: dg_out and db_out go together")
     acc = dg_out is not None
-    dg = _chk(dg_out, "dg_out") if acc else torch.empty(c, device=x.device, dtype=torch.float32)
-    db = _chk(db_out, "db_out") if acc else torch.empty(c, device=x.device, dtype=torch.float32)
+    dg = _wr(dg_out, "dg_out", c, "layernorm_bwd") if acc else torch.empty(c, device=x.device, dtype=torch.float32)
+    db = _wr(db_out, "db_out", c, "layernorm_bwd") if acc else torch.empty(c, device=x.device, dtype=torch.float32)
     wsb = _ws_bytes(("lnbwd", rows, c), "mumpy_layernorm_bwd_workspace_bytes", rows, c)
     ws = _ws(wsb, x.device)
     _call("mumpy_layernorm_bwd", _p(x), _p(gamma), _p(dy), _p(dx_add), _p(dx), _p(dg), _p(db), _p(ws), wsb, rows, c, eps, int(acc),
@@ -1135,7 +1245,8 @@ def gelu(x):
 
 
 def gelu_bwd(x, dy):
-    x, dy = _chk(x, "x"), _chk(dy, "dy")
+    x = _chk(x, "x")
+    dy = _rd(dy, "dy", x.numel(), "gelu_bwd")
     dx = torch.empty_like(x)
     _call("mumpy_gelu_bwd", _p(x), _p(dy), _p(dx), x.numel(), _stream(), work=12.0 * x.numel())
     return dx
@@ -1164,6 +1275,8 @@ def linear_bwd(x2d, weight, dy2d, need_dx=True, dw_out=None, db_out=None, need_d
     if x2d is None and weight is None:                           # bias gradient only (column sums of dY, e.g. a convolution's bias)
         if need_dx or need_dw or not need_db:
             raise RuntimeError("linear_bwd: without x and weight only the bias gradient can be asked for")
+        if dy2d.dim() != 2:
+            raise RuntimeError(f"linear_bwd: dy must be (M, N), got {tuple(dy2d.shape)}")
         m, n = dy2d.shape
         k = 32
     else:
@@ -1178,12 +1291,12 @@ def linear_bwd(x2d, weight, dy2d, need_dx=True, dw_out=None, db_out=None, need_d
     dw = db = None
     if need_dw:
         if dw_out is not None:
-            dw, acc = _chk(dw_out, "dw_out"), acc | 1
+            dw, acc = _chk_exact(dw_out, "dw_out", torch.float32, (n, k), "linear_bwd"), acc | 1
         else:
             dw = torch.empty(n, k, device=dev, dtype=torch.float32)
     if need_db:
         if db_out is not None:
-            db, acc = _chk(db_out, "db_out"), acc | 2
+            db, acc = _wr(db_out, "db_out", n, "linear_bwd"), acc | 2
         else:
             db = torch.empty(n, device=dev, dtype=torch.float32)
     wsb = _ws_bytes(("lbwd", m, n, k), "mumpy_linear_bwd_workspace_bytes", m, n, k)
@@ -1212,7 +1325,7 @@ def linear_gelu_dual(x, weight, bias=None):
     a = torch.empty_like(z)
     wsb = _ws_bytes((m, n, k), "mumpy_linear_workspace_bytes", m, n, k)
     ws = _kept_workspace(wsb, x.device) if wsb else None
-    _call("mumpy_linear_gelu_dual_fwd", _p(x), _p(weight), _p(_opt(bias, "bias")), _p(z), _p(a), m, n, k, _MATH, _p(ws),
+    _call("mumpy_linear_gelu_dual_fwd", _p(x), _p(weight), _p(_rd_opt(bias, "bias", n, "linear_gelu_dual")), _p(z), _p(a), m, n, k, _MATH, _p(ws),
           0 if ws is None else ws.numel() * 4, _stream(), work=2.0 * m * n * k)
     return z, a
 
@@ -1232,12 +1345,12 @@ def linear_gelu_bwd(a2d, z2d, weight, dy2d, need_dz=True, need_dw=True, need_db=
     dw = db = None
     if need_dw:
         if dw_out is not None:
-            dw, acc = _chk(dw_out, "dw_out"), acc | 1
+            dw, acc = _chk_exact(dw_out, "dw_out", torch.float32, (n, k), "linear_gelu_bwd"), acc | 1
         else:
             dw = torch.empty(n, k, device=dev, dtype=torch.float32)
     if need_db:
         if db_out is not None:
-            db, acc = _chk(db_out, "db_out"), acc | 2
+            db, acc = _wr(db_out, "db_out", n, "linear_gelu_bwd"), acc | 2
         else:
             db = torch.empty(n, device=dev, dtype=torch.float32)
     wsb = _ws_bytes(("lgbwd", m, n, k), "mumpy_linear_gelu_bwd_workspace_bytes", m, n, k)
@@ -1256,7 +1369,7 @@ def final_conv_bwd(x, w_krsc, dy):
     (dx like x, dw (1,3,3,32), db (1,)).  One streaming pass + a small fixed-tree reduce."""
     x = _nhwc(x, "x")
     b, c, h, w = x.shape
-    dy = _chk(dy.reshape(b, h, w), "dy")
+    dy = _rd(dy, "dy", b * h * w, "final_conv_bwd")
     if c != 32 or tuple(w_krsc.shape) != (1, 3, 3, 32):
         raise RuntimeError(f"final_conv_bwd is built for Conv2d(32, 1, 3, padding=1); got C={c}, weight {tuple(w_krsc.shape)}")
     dx = empty_nhwc(b, c, h, w, x.device)
@@ -1298,9 +1411,8 @@ def conv2d_wgrad(x, dy, kh, kw, dw_out=None):
     if dy.shape != (b, cout, h, w):
         raise RuntimeError(f"conv2d_wgrad: x {tuple(x.shape)} and dy {tuple(dy.shape)} do not match")
     acc = dw_out is not None
-    dw = _chk(dw_out, "dw_out") if acc else torch.empty(cout, kh, kw, cin, device=x.device, dtype=torch.float32)
-    if dw.shape != (cout, kh, kw, cin):
-        raise RuntimeError(f"conv2d_wgrad: gradient buffer {tuple(dw.shape)} != {(cout, kh, kw, cin)}")
+    dw = _chk_exact(dw_out, "dw_out", torch.float32, (cout, kh, kw, cin), "conv2d_wgrad") if acc else \
+        torch.empty(cout, kh, kw, cin, device=x.device, dtype=torch.float32)
     wsb = _ws_bytes(("cwgrad", b, h, w, cin, cout, kh, kw), "mumpy_conv2d_wgrad_workspace_bytes", b, h, w, cin, cout, kh, kw)
     ws = _ws(wsb, x.device) if wsb else None
     if _MATH not in (MATH_FP32, MATH_BF16):
@@ -1353,23 +1465,26 @@ def window_attention_bwd(qkv, dout, bias_pad, rel_index32, b, hs, w, c, shift, s
         raise RuntimeError("window_attention_bwd: rel_index32 must be the (49*49) int32 relative_position_index on the GPU")
     dqkv = torch.empty_like(qkv)
     acc = dtable_out is not None
-    dtable = _chk(dtable_out, "dtable_out") if acc else torch.empty(169, c // 32, device=qkv.device, dtype=torch.float32)
-    if dtable.shape != (169, c // 32):
-        raise RuntimeError(f"window_attention_bwd: table gradient buffer {tuple(dtable.shape)} != {(169, c // 32)}")
+    dtable = _chk_exact(dtable_out, "dtable_out", torch.float32, (169, c // 32), "window_attention_bwd") if acc else \
+        torch.empty(169, c // 32, device=qkv.device, dtype=torch.float32)
+    bias_pad = _rd(bias_pad, "bias", (c // 32) * 64 * 64, "window_attention_bwd")
+    mask_tab, mask_id, n_mask = _chk_mask(mask_tab, mask_id, b * (hs // 7) * (w // 7), "window_attention_bwd")
+    rel_index32 = rel_index32.contiguous()
+    if rel_csr is not None:
+        if rel_csr.dtype != torch.int32 or rel_csr.numel() != 170 + 49 * 49 or rel_csr.device != qkv.device:
+            raise RuntimeError("window_attention_bwd: rel_csr must come from ops.rel_index_csr on this device")
+        rel_csr = rel_csr.contiguous()
     if math == "bf16":
         wsb = _ws_bytes(("wabwd16", b, hs, w, c), "mumpy_window_attention_mm16_bwd_workspace_bytes", b, hs, w, c)
     else:
         wsb = _ws_bytes(("wabwd", b, hs, w, c), "mumpy_window_attention_bwd_workspace_bytes", b, hs, w, c)
     ws = _ws(wsb, qkv.device)
-    n_mask = 0 if mask_id is None else mask_id.numel()
-    if rel_csr is not None and (rel_csr.dtype != torch.int32 or rel_csr.numel() != 170 + 49 * 49 or rel_csr.device != qkv.device):
-        raise RuntimeError("window_attention_bwd: rel_csr must come from ops.rel_index_csr on this device")
     if math == "bf16":
         name, csr_args = "mumpy_window_attention_mm16_bwd", (_p(rel_csr),)        # one entry: a null rel_csr selects the scanning kernel
     else:
         name, csr_args = "mumpy_window_attention_bwd" + ("" if rel_csr is None else "_csr"), (() if rel_csr is None else (_p(rel_csr),))
-    _call(name, _p(qkv), _p(dout), _p(_chk(bias_pad, "bias")), _p(mask_tab),
-          _p(mask_id), n_mask, _p(rel_index32.contiguous()), *csr_args, _p(dqkv), _p(dtable), _p(ws), wsb, b, hs, w, c, shift, scale, int(acc), _stream(),
+    _call(name, _p(qkv), _p(dout), _p(bias_pad), _p(mask_tab),
+          _p(mask_id), n_mask, _p(rel_index32), *csr_args, _p(dqkv), _p(dtable), _p(ws), wsb, b, hs, w, c, shift, scale, int(acc), _stream(),
           work=5 * 153664.0 * b * (hs // 7) * (w // 7) * (c // 32))
     return dqkv, (None if acc else dtable)
 
@@ -1383,16 +1498,18 @@ def gn_bwd(z, stats, gamma, beta, dy, groups, eps=1e-5, act=ACT_RELU, dg_out=Non
     with dg_out AND db_out the parameter gradients are ACCUMULATED into those buffers (grad slots) and returned as None."""
     z, dy = _nhwc(z, "z"), _nhwc(dy, "dy")
     b, c, h, w = z.shape
+    if dy.shape != z.shape:
+        raise RuntimeError(f"gn_bwd: z {tuple(z.shape)} and dy {tuple(dy.shape)} do not match")
     partial, nsplit = stats
+    partial = _rd(partial, "partial", b * nsplit * groups * 2, "gn_bwd")
+    gamma, beta = _rd(gamma, "gamma", c, "gn_bwd"), _rd(beta, "beta", c, "gn_bwd")
     dz = empty_nhwc(b, c, h, w, z.device)
     acc = dg_out is not None and db_out is not None
-    dg = _chk(dg_out, "dgamma") if acc else torch.empty(c, device=z.device, dtype=torch.float32)
-    db = _chk(db_out, "dbeta") if acc else torch.empty(c, device=z.device, dtype=torch.float32)
-    if dg.numel() != c or db.numel() != c:
-        raise RuntimeError("gn_bwd: parameter gradient buffers must hold C values")
+    dg = _wr(dg_out, "dg_out", c, "gn_bwd") if acc else torch.empty(c, device=z.device, dtype=torch.float32)
+    db = _wr(db_out, "db_out", c, "gn_bwd") if acc else torch.empty(c, device=z.device, dtype=torch.float32)
     wsb = int(_lib().mumpy_gn_bwd_workspace_bytes(b, h * w, c))
     ws = _ws(wsb, z.device)
-    _call("mumpy_gn_bwd_nhwc", _p(z), _p(partial), nsplit, _p(_chk(gamma, "gamma")), _p(_chk(beta, "beta")), _p(dy), _p(dz), _p(dg),
+    _call("mumpy_gn_bwd_nhwc", _p(z), _p(partial), nsplit, _p(gamma), _p(beta), _p(dy), _p(dz), _p(dg),
           _p(db), _p(ws), wsb, b, h * w, c, groups, eps, int(act) | (GN_ACCUMULATE if acc else 0), _stream(), work=20.0 * z.numel())
     return (dz, None, None) if acc else (dz, dg, db)
 
@@ -1423,7 +1540,7 @@ def scale_samples(x, scale):
 
 
 def temporal_attention_bwd(qkv, dout, s_, t, c, heads, scale):
-    qkv, dout = _chk(qkv, "qkv"), _chk(dout, "dout")
+    qkv, dout = _rd(qkv, "qkv", s_ * t * 3 * c, "temporal_attention_bwd"), _rd(dout, "dout", s_ * t * c, "temporal_attention_bwd")
     dqkv = torch.empty_like(qkv)
     _call("mumpy_temporal_attention_bwd", _p(qkv), _p(dout), _p(dqkv), s_, t, c, heads, scale, _stream(), work=4.0 * (2 * qkv.numel() + dout.numel()))
     return dqkv
@@ -1433,31 +1550,40 @@ def temporal_attention_bwd(qkv, dout, s_, t, c, heads, scale):
 def dwconv5_window(x, w25, b):
     """x (N,49,C) token-major windows, w25 (C,25), b (C) -> (N,49,C): depthwise 5x5 conv (padding 2) inside each 7x7 window."""
     x = _chk(x, "x")
-    n, _, c = x.shape
+    n, p49, c = x.shape
+    if p49 != 49:
+        raise RuntimeError(f"dwconv5_window: x must be (N, 49, C), got {tuple(x.shape)}")
+    w25, b = _rd(w25, "w", c * 25, "dwconv5_window"), _rd(b, "b", c, "dwconv5_window")
     u = torch.empty_like(x)
-    _call("mumpy_dwconv5_window_fwd", _p(x), _p(_chk(w25, "w")), _p(_chk(b, "b")), _p(u), n, c, _stream(), work=8.0 * x.numel())
+    _call("mumpy_dwconv5_window_fwd", _p(x), _p(w25), _p(b), _p(u), n, c, _stream(), work=8.0 * x.numel())
     return u
 
 
 def dwconv5_window_bwd(x, w25, du):
     """-> (dx (N,49,C), dw (C,25), db (C))."""
-    x, du = _chk(x, "x"), _chk(du, "du")
-    n, _, c = x.shape
+    x = _chk(x, "x")
+    n, p49, c = x.shape
+    if p49 != 49:
+        raise RuntimeError(f"dwconv5_window_bwd: x must be (N, 49, C), got {tuple(x.shape)}")
+    du, w25 = _rd(du, "du", x.numel(), "dwconv5_window_bwd"), _rd(w25, "w", c * 25, "dwconv5_window_bwd")
     dx = torch.empty_like(x)
     dw_t = torch.empty(26, c, device=x.device, dtype=torch.float32)       # rows 0..24 = taps; row 25 unused scratch
     db = torch.empty(c, device=x.device, dtype=torch.float32)
     wsb = int(_lib().mumpy_dwconv5_window_bwd_workspace_bytes(n, c))
     ws = _ws(wsb, x.device)
-    _call("mumpy_dwconv5_window_bwd", _p(x), _p(_chk(w25, "w")), _p(du), _p(dx), _p(dw_t), _p(db), _p(ws), wsb, n, c, _stream(),
+    _call("mumpy_dwconv5_window_bwd", _p(x), _p(w25), _p(du), _p(dx), _p(dw_t), _p(db), _p(ws), wsb, n, c, _stream(),
           work=16.0 * x.numel())
     return dx, transpose(dw_t[:25].contiguous()), db
 
 
 def deform_sample_bwd(x2w, pos, dsampled):
     """window form: x2w, dsampled (B2,49,C), pos (nq,3,49,2) -> (dx2 (B2,49,C), dpos (nq,3,49,2))."""
-    x2w, pos, dsampled = _chk(x2w, "x2"), _chk(pos, "pos"), _chk(dsampled, "dsampled")
-    b2, _, c = x2w.shape
+    x2w, pos = _chk(x2w, "x2"), _chk(pos, "pos")
+    b2, p49, c = x2w.shape
     nq = pos.shape[0]
+    if p49 != 49 or nq < 1 or b2 % nq or pos.numel() != nq * 3 * 49 * 2:
+        raise RuntimeError(f"deform_sample_bwd: x2 (B2, 49, C) and pos (nq, 3, 49, 2) with nq dividing B2, got {tuple(x2w.shape)} and {tuple(pos.shape)}")
+    dsampled = _rd(dsampled, "dsampled", x2w.numel(), "deform_sample_bwd")
     dx2 = torch.empty_like(x2w)
     part = torch.empty(b2, 3, 49, 2, device=x2w.device, dtype=torch.float32)
     _call("mumpy_deform_sample_bwd", _p(x2w), _p(pos), _p(dsampled), _p(dx2), _p(part), b2, c, nq, _stream(), work=12.0 * x2w.numel())
@@ -1472,12 +1598,13 @@ def deform_attention_bwd(q, kv, dout, r, scale, math="fp32"):
     over its r kv windows on the device in a fixed order (no partial slices, no add launches)."""
     if math not in ("fp32", "bf16"):
         raise ValueError(f"unknown cross-view attention math mode {math!r}")
-    q, kv, dout = _chk(q, "q"), _chk(kv, "kv"), _chk(dout, "dout")
-    b1, _, c = q.shape
+    q = _chk(q, "q")
+    b1, p49, c = q.shape
     b2 = b1 * r
+    if p49 != 49:
+        raise RuntimeError(f"deform_attention_bwd: q must be (B1, 49, C), got {tuple(q.shape)}")
+    kv, dout = _rd(kv, "kv", b2 * 49 * 2 * c, "deform_attention_bwd"), _rd(dout, "dout", q.numel(), "deform_attention_bwd")
     if math == "bf16":
-        if kv.numel() != b2 * 49 * 2 * c or dout.numel() != q.numel():
-            raise RuntimeError("deform_attention_bwd: shape mismatch")
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         wsb = _ws_bytes(("cvabwd16", b1, r, c), "mumpy_deform_attention_mm16_bwd_workspace_bytes", b1, r, c)
         ws = _ws(wsb, q.device)
@@ -1514,9 +1641,16 @@ def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, hyper_dev):
         _chk(t, name)
         if t.numel() != n or not t.is_contiguous():
             raise RuntimeError(f"adamw_step_dev: {name} must be a contiguous buffer of {n} elements (in-place update)")
-    _call("mumpy_adamw_step_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(_chk(hyper_dev, "hyper")), _stream(),
+    _call("mumpy_adamw_step_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(_chk_hyper("adamw_step_dev", hyper_dev, 8)), _stream(),
           work=28.0 * n)
     return param
+
+
+def _chk_hyper(fn, hyper, count):
+    """The staged device constants of a step: read where they are (grad_norm_finish scales them in place)."""
+    if not hyper.is_cuda or hyper.dtype != torch.float32 or hyper.numel() < count or not hyper.is_contiguous():
+        raise RuntimeError(f"{fn}: hyper must be a contiguous float32 GPU tensor of at least {count} constants")
+    return hyper
 
 
 def _flat_bufs(fn, n, **bufs):
@@ -1557,7 +1691,7 @@ def sgd_step_dev(param, grad, momentum_buf, hyper_dev, nesterov=False):
     """SGD over flat buffers with the step constants in the device tensor `hyper_dev` (4 floats): capturable."""
     n = param.numel()
     _flat_bufs("sgd_step_dev", n, param=param, grad=grad, momentum_buf=momentum_buf)
-    _call("mumpy_sgd_step_dev", _p(param), _p(grad), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")), int(bool(nesterov)),
+    _call("mumpy_sgd_step_dev", _p(param), _p(grad), _p(momentum_buf), n, _p(_chk_hyper("sgd_step_dev", hyper_dev, 4)), int(bool(nesterov)),
           _stream(), work=(20.0 if momentum_buf is not None else 12.0) * n)
     return param
 
@@ -1582,7 +1716,7 @@ def rmsprop_step_dev(param, grad, square_avg, momentum_buf, hyper_dev):
     """RMSprop over flat buffers with the step constants in the device tensor `hyper_dev` (8 floats): capturable."""
     n = param.numel()
     _flat_bufs("rmsprop_step_dev", n, param=param, grad=grad, square_avg=square_avg, momentum_buf=momentum_buf)
-    _call("mumpy_rmsprop_step_dev", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")),
+    _call("mumpy_rmsprop_step_dev", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, _p(_chk_hyper("rmsprop_step_dev", hyper_dev, 8)),
           _stream(), work=(28.0 if momentum_buf is not None else 20.0) * n)
     return param
 
@@ -1626,11 +1760,9 @@ def grad_norm_finish(partials, sizes, hypers, kinds, stats, max_norm=None):
         if k not in _OPT_KINDS:
             raise ValueError(f"grad_norm_finish: unknown optimizer kind {k!r} (group {g})")
         _chk(p, "partials")
-        _chk(h, "hyper")
         if not p.is_contiguous() or p.numel() != 2 * grad_norm_partials(n):
             raise RuntimeError(f"grad_norm_finish: partials of group {g} must hold {2 * grad_norm_partials(n)} floats")
-        if not h.is_contiguous() or h.numel() < (4 if k == "SGD" else 8):
-            raise RuntimeError(f"grad_norm_finish: hyper buffer of group {g} is too small for {k}")
+        _chk_hyper(f"grad_norm_finish (group {g})", h, 4 if k == "SGD" else 8)
     _chk(stats, "stats")
     if not stats.is_contiguous() or stats.numel() != 4 + groups:
         raise RuntimeError(f"grad_norm_finish: stats must be a contiguous buffer of {4 + groups} floats")
@@ -1689,9 +1821,7 @@ def update_gate(stats, gate, hypers, kinds, applied, adam_raw):
     for g, (h, k) in enumerate(zip(hypers, kinds)):
         if k not in _OPT_KINDS:
             raise ValueError(f"update_gate: unknown optimizer kind {k!r} (group {g})")
-        _chk(h, "hyper")
-        if not h.is_contiguous() or h.numel() < (4 if k == "SGD" else 8):
-            raise RuntimeError(f"update_gate: hyper buffer of group {g} is too small for {k}")
+        _chk_hyper(f"update_gate (group {g})", h, 4 if k == "SGD" else 8)
     _chk_gate("update_gate", gate)
     if not applied.is_cuda or applied.dtype != torch.int64 or applied.numel() != groups or not applied.is_contiguous():
         raise RuntimeError(f"update_gate: applied must be a contiguous int64 GPU tensor of {groups} counts")
@@ -1708,7 +1838,7 @@ def adamw_step_gated_dev(param, grad, exp_avg, exp_avg_sq, hyper_dev, gate):
     """adamw_step_dev behind `gate` (update_gate): nothing is read or written when gate[0] != 0, the same bits otherwise."""
     n = param.numel()
     _flat_bufs("adamw_step_gated_dev", n, param=param, grad=grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
-    _call("mumpy_adamw_step_gated_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(_chk(hyper_dev, "hyper")),
+    _call("mumpy_adamw_step_gated_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(_chk_hyper("adamw_step_gated_dev", hyper_dev, 8)),
           _p(_chk_gate("adamw_step_gated_dev", gate)), _stream(), work=28.0 * n)
     return param
 
@@ -1717,7 +1847,7 @@ def sgd_step_gated_dev(param, grad, momentum_buf, hyper_dev, gate, nesterov=Fals
     """sgd_step_dev behind `gate` (as adamw_step_gated_dev)."""
     n = param.numel()
     _flat_bufs("sgd_step_gated_dev", n, param=param, grad=grad, momentum_buf=momentum_buf)
-    _call("mumpy_sgd_step_gated_dev", _p(param), _p(grad), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")), int(bool(nesterov)),
+    _call("mumpy_sgd_step_gated_dev", _p(param), _p(grad), _p(momentum_buf), n, _p(_chk_hyper("sgd_step_gated_dev", hyper_dev, 4)), int(bool(nesterov)),
           _p(_chk_gate("sgd_step_gated_dev", gate)), _stream(), work=(20.0 if momentum_buf is not None else 12.0) * n)
     return param
 
@@ -1726,6 +1856,6 @@ def rmsprop_step_gated_dev(param, grad, square_avg, momentum_buf, hyper_dev, gat
     """rmsprop_step_dev behind `gate` (as adamw_step_gated_dev)."""
     n = param.numel()
     _flat_bufs("rmsprop_step_gated_dev", n, param=param, grad=grad, square_avg=square_avg, momentum_buf=momentum_buf)
-    _call("mumpy_rmsprop_step_gated_dev", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, _p(_chk(hyper_dev, "hyper")),
+    _call("mumpy_rmsprop_step_gated_dev", _p(param), _p(grad), _p(square_avg), _p(momentum_buf), n, _p(_chk_hyper("rmsprop_step_gated_dev", hyper_dev, 8)),
           _p(_chk_gate("rmsprop_step_gated_dev", gate)), _stream(), work=(28.0 if momentum_buf is not None else 20.0) * n)
     return param

@@ -711,7 +711,8 @@ def _():
 def _():
     def call(ops, t):                                                    # the pitched 3-of-T token slice of test_decoder_wiring_kernels
         view = t.g.reshape(3, 49, 5 * 768)[:, :, :2304].reshape(3, 7, 7, 2304).permute(0, 3, 1, 2)
-        assert view.data_ptr() == t.g.data_ptr()
+        if not t.g.is_contiguous() or view.data_ptr() != t.g.data_ptr():         # (an error of the caller, not an assert:
+            raise RuntimeError("the view must be a pitched alias of a dense g")   # tests/test_ops_handoff.py counts it as a refusal)
         cat = ops.empty_nhwc(3, 256 + 2304, 7, 7, t.g.device)
         ops.set_channels(cat, 256, view)
         return {"cat": cat}
