@@ -12,6 +12,7 @@
 // (B,32,448,448) intermediates are never formed — the kernel averages 4 channels per tap and writes (B,32,224,224).
 // NHWC: lanes run over channels (16-B accesses), a tap is one contiguous channel vector.  HBM-bound streaming.
 #include "common.h"
+#include "sigmoid_thr.h"
 using namespace mumpy;
 
 namespace {
@@ -208,7 +209,7 @@ __global__ __launch_bounds__(256) void final_conv_kernel(const float* __restrict
         if (sub == 0) {
             const float z = acc + b0;
             logits[pix] = z;
-            if (mask) mask[pix] = (1.0f / (1.0f + __expf(-z)) > thr) ? 1 : 0;
+            if (mask) mask[pix] = sigmoid_exceeds(z, thr) ? 1 : 0;
         }
     }
 }
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(256) void final_conv_wide_kernel(const float* __res
         if (sub == 0) {
             const float z = acc + b0;
             logits[pix] = z;
-            if (mask) mask[pix] = (1.0f / (1.0f + __expf(-z)) > thr) ? 1 : 0;
+            if (mask) mask[pix] = sigmoid_exceeds(z, thr) ? 1 : 0;
         }
     }
 }

@@ -10,6 +10,7 @@
 // The last two move ~50 KB per clip and a few KB per video: one workgroup per clip / one workgroup, bounded by launch latency.
 #include "common.h"
 #include "u8_pixel.h"
+#include "frame_metric.h"
 #include "../../include/mumpy_hip_ext5.h"
 using namespace mumpy;
 
@@ -107,10 +108,10 @@ __global__ __launch_bounds__(256) void frame_metrics_kernel(const int32_t* __res
     for (int f = tid; f < nscored; f += 256) {
         const int32_t* c = counts + (int64_t)f * 4;
         const double inter = (double)c[0], sp = (double)c[1], sg = (double)c[2], uni = (double)c[3];
-        const double recall = inter / (sg + eps_g);          // eps_g = 1e-6 * npix: measure.py sums (gt + 1e-6) over all pixels
-        const double precision = inter / (sp + 1e-6);
-        f1 += 2.0 * precision * recall / (precision + recall + 1e-6);
-        iou += (inter + 1e-5) / (uni + 1e-5);
+        double ff, fi;
+        frame_f1_iou(inter, sp, sg, uni, eps_g, ff, fi);     // eps_g = 1e-6 * npix (frame_metric.h)
+        f1 += ff;
+        iou += fi;
     }
     red[tid][0] = f1; red[tid][1] = iou;
     __syncthreads();

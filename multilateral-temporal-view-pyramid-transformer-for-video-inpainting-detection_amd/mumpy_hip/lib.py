@@ -165,6 +165,13 @@ EXT6_SIGNATURES = {
 }
 EXT6_VERSION = 1
 
+# ... and after that one; mirrors include/mumpy_hip_ext7.h one to one (tests/test_threshold_sweep_host.py checks it)
+EXT7_SIGNATURES = {
+    "mumpy_score_exceed_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_l, c_i, c_f],
+    "mumpy_sweep_metrics_fwd": [c_f, c_l, c_l, c_i, c_f, c_f, c_i, c_f],
+}
+EXT7_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -231,8 +238,12 @@ def load_library():
     lib.mumpy_ext6_version.argtypes = []
     if lib.mumpy_ext6_version() != EXT6_VERSION:
         raise RuntimeError(f"{path}: sixth extension version {lib.mumpy_ext6_version()} != binding {EXT6_VERSION}; rebuild")
+    lib.mumpy_ext7_version.restype = c_i
+    lib.mumpy_ext7_version.argtypes = []
+    if lib.mumpy_ext7_version() != EXT7_VERSION:
+        raise RuntimeError(f"{path}: seventh extension version {lib.mumpy_ext7_version()} != binding {EXT7_VERSION}; rebuild")
     for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES,
-                       **EXT5_SIGNATURES, **EXT6_SIGNATURES}.items():
+                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

@@ -1140,6 +1140,71 @@ def frame_metrics(counts, nscored, npix, acc=None, accumulate=False):
     return acc
 
 
+SWEEP_MAX_THRESHOLDS = 1023      # MUMPY_SWEEP_MAX_THRESHOLDS of include/mumpy_hip_ext7.h
+
+
+def _chk_exceed(exceed, who):
+    """-> (rows, K) of an exceed buffer (rows, 2, K + 1) int32, read or written where it is."""
+    if exceed.dim() != 3 or exceed.shape[1] != 2 or not 2 <= exceed.shape[2] <= SWEEP_MAX_THRESHOLDS + 1:
+        raise RuntimeError(f"mumpy_hip: {who} needs exceed of shape (rows, 2, K + 1) with 1 <= K <= {SWEEP_MAX_THRESHOLDS}, got "
+                           f"{tuple(exceed.shape)}")
+    _chk_exact(exceed, "exceed", torch.int32, tuple(exceed.shape), who)
+    return exceed.shape[0], exceed.shape[2] - 1
+
+
+def score_exceed(logits, gt, dest, table, exceed):
+    """Per frame and class, the pixels whose probability exceeds each threshold of a table (mumpy_score_exceed_fwd,
+    include/mumpy_hip_ext7.h): logits (nclips, ...) float32 with npix elements per clip (what final_conv writes), gt (nbank, npix)
+    uint8 (> 0 is forged), dest (nclips) int32, table (K) float32 ascending, exceed (nbank, 2, K + 1) int32, written in place: for
+    every clip with 0 <= dest[c] < nbank, exceed[dest[c]][g][k] = #{pixels of class g with sigmoid(logit) > table[k]} and
+    exceed[dest[c]][g][K] = #{pixels of class g}; the other clips write nothing, the other rows stay.  Row k holds the counts
+    mask_score_u8 takes from final_conv's mask at thr = table[k], bit for bit (video.exceed_counts reads them out).  K is taken from
+    the table.  dest and table are read when the kernel runs.  Returns exceed."""
+    who = "score_exceed"
+    if table.dim() != 1 or not 1 <= table.shape[0] <= SWEEP_MAX_THRESHOLDS:
+        raise RuntimeError(f"mumpy_hip: score_exceed needs a table of 1 .. {SWEEP_MAX_THRESHOLDS} thresholds, got {tuple(table.shape)}")
+    k = table.shape[0]
+    _chk_exact(table, "table", torch.float32, (k,), who)
+    if gt.dim() != 2:
+        raise RuntimeError("mumpy_hip: score_exceed needs gt of shape (nbank, npix)")
+    nbank, npix = gt.shape
+    _chk_exact(gt, "gt", torch.uint8, (nbank, npix), who)
+    nclips = dest.shape[0] if dest.dim() == 1 else -1
+    _chk_exact(dest, "dest", torch.int32, (nclips,), who)
+    if not logits.is_cuda or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() < 1 or \
+            logits.shape[0] != nclips or logits.numel() != nclips * npix:
+        raise RuntimeError(f"mumpy_hip: score_exceed needs logits as a contiguous float32 GPU tensor ({nclips}, ...) of {npix} elements "
+                           f"per clip, got {logits.dtype} {tuple(logits.shape)} on {logits.device}")
+    _chk_exact(exceed, "exceed", torch.int32, (nbank, 2, k + 1), who)
+    _call("mumpy_score_exceed_fwd", _p(logits), _p(gt), _p(dest), _p(table), _p(exceed), nclips, npix, nbank, k, _stream(),
+          work=float(5 * logits.numel()))
+    return exceed
+
+
+def sweep_metrics(exceed, nscored, npix, acc=None, pooled=None, accumulate=False):
+    """Per-threshold [sum F1, sum IoU, n] float64 (K, 3) over frames 0 .. nscored - 1 of exceed (>= nscored, 2, K + 1) int32 as
+    score_exceed writes it (mumpy_sweep_metrics_fwd): row k is what frame_metrics gives for video.exceed_counts(exceed, k).
+    acc= (K, 3) float64 is written in place (allocated when not given).  pooled= (2, K + 1) int64, written in place, or True to have
+    one allocated: the counts summed over the frames (the ROC points of the table); None: not computed.  accumulate=True adds into
+    acc and pooled (both must then be the caller's).  Returns acc, or (acc, pooled) with pooled.  evaluate.finalize_sweep takes the
+    two."""
+    who = "sweep_metrics"
+    rows, k = _chk_exceed(exceed, who)
+    nscored, npix = int(nscored), int(npix)
+    if not 0 <= nscored <= rows:
+        raise RuntimeError(f"mumpy_hip: sweep_metrics needs exceed of shape (>= {nscored}, 2, K + 1), got {tuple(exceed.shape)}")
+    if accumulate and (acc is None or pooled is True):
+        raise RuntimeError("mumpy_hip: sweep_metrics: accumulate=True needs acc= (and pooled=, when given) as the caller's buffers")
+    acc = torch.empty(k, 3, device=exceed.device, dtype=torch.float64) if acc is None else \
+        _chk_exact(acc, "acc", torch.float64, (k, 3), who)
+    if pooled is True:
+        pooled = torch.empty(2, k + 1, device=exceed.device, dtype=torch.int64)
+    elif pooled is not None:
+        _chk_exact(pooled, "pooled", torch.int64, (2, k + 1), who)
+    _call("mumpy_sweep_metrics_fwd", _p(exceed), nscored, npix, k, _p(acc), _p(pooled), int(bool(accumulate)), _stream())
+    return acc if pooled is None else (acc, pooled)
+
+
 _BILINEAR_TABLES = {}
 
 

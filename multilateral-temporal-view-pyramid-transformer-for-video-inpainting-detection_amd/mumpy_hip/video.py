@@ -13,7 +13,13 @@ BILINEAR before it thresholds, and ops.resize_bilinear_u8 does that on the devic
 coefficient tables and `bilinear_resize` is the numpy statement of the whole resize.  Not covered: a palette image's conversion to
 'L' (the caller's `.convert('L')`), RGB images, the other filters, `box=` and `reducing_gap=`.
 
-The host half (`clip_frame_indices`, `batch_plan`, `bilinear_taps`, `bilinear_resize`) imports and runs without a GPU."""
+The threshold need not be chosen before the pass: `VideoPredictor(sweep=...)` also counts, per frame, how many pixels exceed each
+threshold of a table (ops.score_exceed, inside the same graph) and sums F1 / IoU per threshold (ops.sweep_metrics);
+evaluate.finalize_sweep turns that into the best threshold and a pixel-level AUC.  `sweep_table` builds the table and
+`exceed_counts` reads the four counts of one threshold out of the exceed rows.
+
+The host half (`clip_frame_indices`, `batch_plan`, `bilinear_taps`, `bilinear_resize`, `sweep_table`, `exceed_counts`) imports and
+runs without a GPU."""
 import os
 
 import numpy as np
@@ -116,6 +122,44 @@ def bilinear_resize(img_u8, out_hw) -> np.ndarray:
     return np.ascontiguousarray(np.moveaxis(vert, 0, -2)).astype(np.uint8)
 
 
+SWEEP_MAX_THRESHOLDS = 1023     # MUMPY_SWEEP_MAX_THRESHOLDS of include/mumpy_hip_ext7.h
+
+
+def sweep_table(thresholds=None) -> np.ndarray:
+    """The threshold table of a sweep, float32 (K,).  The default is the 255 values i / 256, i = 1 .. 255: exact in float32, and
+    0.5 -- the reference's threshold (test.py:108) -- is one of them.  A caller's list is converted to float32 and refused unless it
+    then holds 1 to 1023 finite, strictly ascending values (two values that collapse in float32 are refused: they would be one
+    operating point listed twice)."""
+    if thresholds is None:
+        return (np.arange(1, 256, dtype=np.float32) / np.float32(256.0)).astype(np.float32)
+    with np.errstate(over="ignore"):
+        t = np.asarray(thresholds, dtype=np.float64).astype(np.float32)
+    if t.ndim != 1 or not 1 <= t.size <= SWEEP_MAX_THRESHOLDS:
+        raise ValueError(f"sweep_table: needs a list of 1 to {SWEEP_MAX_THRESHOLDS} thresholds, got shape {t.shape}")
+    if not np.isfinite(t).all():
+        raise ValueError("sweep_table: every threshold must be finite in float32")
+    if not (np.diff(t) > 0).all():
+        raise ValueError("sweep_table: the thresholds must be strictly ascending after the conversion to float32")
+    return np.ascontiguousarray(t)
+
+
+def exceed_counts(exceed, k: int):
+    """The (n, 4) counts {inter, sum p, sum g, union} of threshold k out of exceed (n, 2, K + 1) as ops.score_exceed writes it --
+    what ops.mask_score_u8 counts from the mask at thr = table[k], and what ops.frame_metrics / the metric formulas take.  Works
+    on a numpy array (-> int64) and on a tensor (-> int32, on its device)."""
+    if exceed.ndim != 3 or exceed.shape[1] != 2 or exceed.shape[2] < 2:
+        raise ValueError(f"exceed_counts: needs exceed of shape (n, 2, K + 1), got {tuple(exceed.shape)}")
+    last = exceed.shape[2] - 1
+    k = int(k)
+    if not 0 <= k < last:
+        raise ValueError(f"exceed_counts: k={k} is outside the table's 0 .. {last - 1}")
+    on_device = isinstance(exceed, torch.Tensor)
+    e = exceed.to(torch.int64) if on_device else np.asarray(exceed).astype(np.int64)
+    inter, sp, sg = e[:, 1, k], e[:, 0, k] + e[:, 1, k], e[:, 1, last]
+    cols = [inter, sp, sg, sp + sg - inter]
+    return torch.stack(cols, 1).to(torch.int32).contiguous() if on_device else np.stack(cols, 1)
+
+
 class VideoPredictor(GraphedForward):
     """One forgery mask per frame of a video, and the F1 / IoU sums over its frames, without leaving the device.
 
@@ -125,6 +169,12 @@ class VideoPredictor(GraphedForward):
 
     gt_hw=(Hg, Wg): predict takes the annotations at their own size and resizes them on the device as measure.py does (see predict);
     gt_hw=None (the default) takes them at 224 x 224 and launches nothing more.
+
+    sweep=True (the 255 thresholds of `sweep_table()`) or a list of thresholds: the predictor also owns the table on the device,
+    exceed (max_frames, 2, K + 1) int32, sweep_acc (K, 3) float64 and sweep_pooled (2, K + 1) int64; the captured forward ends with
+    ops.score_exceed(logits, gt, dest, table, exceed), and a predict with gt_u8 ends with ops.sweep_metrics(..., accumulate=True)
+    beside frame_metrics.  `sweep_vector()` is what evaluate.finalize_sweep takes.  thr, the masks, the bank, counts and the metric
+    vector are not affected; sweep=None (the default) allocates nothing and captures exactly the three steps below.
 
     It owns the frame bank (max_frames, Hs, Ws, 3), the index table (batch, T) and dest table (batch,), the clip batch
     (batch, T, 3, 224, 224), the mask and annotation banks (max_frames, 224 * 224), the counts bank (max_frames, 4), the accumulator
@@ -139,7 +189,8 @@ class VideoPredictor(GraphedForward):
     order, the padding clips of the tail (copies of the last clip) included, and the GEMM kernels are chosen by the batch's row
     count -- so results at different `batch` values are not bit for bit the same."""
 
-    def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True, gt_hw=None, gt_chunk=64):
+    def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True, gt_hw=None, gt_chunk=64,
+                 sweep=None):
         T, batch, max_frames = int(T), int(batch), int(max_frames)
         clip_frame_indices(1, T)                                     # refuses an even T
         model_t = int(encoder.configs[-1]["num_frames"])
@@ -154,6 +205,9 @@ class VideoPredictor(GraphedForward):
             raise ValueError(f"VideoPredictor: gt_hw={gt_hw} must be (Hg, Wg) with both at least 1, and gt_chunk={gt_chunk} at least 1")
         if self.gt_hw is not None and max(self.gt_hw) > GT_MAX_RATIO * SIDE:
             raise ValueError(f"VideoPredictor: gt_hw={gt_hw} is more than {GT_MAX_RATIO} times {SIDE} (the resize kernel's tap cap)")
+        if sweep is not None and not isinstance(sweep, bool) and isinstance(sweep, (str, bytes, int, float)):
+            raise ValueError(f"VideoPredictor: sweep={sweep!r} must be None, True or a list of thresholds")
+        table = None if sweep is None or sweep is False else sweep_table(None if sweep is True else sweep)    # refuses a bad list
         dev = next(encoder.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("VideoPredictor: the model is not on a GPU (there is no CPU path)")
@@ -170,6 +224,14 @@ class VideoPredictor(GraphedForward):
         self._idx_host = torch.zeros(nb, batch, T, dtype=torch.int32).pin_memory()   # a whole video's plan: no slot is reused while
         self._dest_host = torch.zeros(nb, batch, dtype=torch.int32).pin_memory()     # an upload out of it may still be in flight
         self._uploaded = None
+        # sweep: the table (uploaded once), the per-frame exceed counts and the two accumulators; nothing of it exists without
+        self.table = self.exceed = self.sweep_acc = self.sweep_pooled = None
+        if table is not None:
+            k = len(table)
+            self.table = torch.from_numpy(table).to(dev)
+            self.exceed = torch.zeros(max_frames, 2, k + 1, device=dev, dtype=torch.int32)
+            self.sweep_acc = torch.zeros(k, 3, device=dev, dtype=torch.float64)
+            self.sweep_pooled = torch.zeros(2, k + 1, device=dev, dtype=torch.int64)
         # annotations that arrive from the host at their own size pass through this, gt_chunk frames at a time (1080p annotations
         # of a whole video would cost max_frames * Hg * Wg bytes)
         self._gt_stage = None if self.gt_hw is None else \
@@ -189,6 +251,8 @@ class VideoPredictor(GraphedForward):
         ops.clip_window_u8(self.frames, self.idx, (SIDE, SIDE), out=self.static_x)
         logits, mask, feats = fused_forward(self.encoder, self.decoder, self.static_x, with_mask=True, thr=self.thr)
         ops.mask_score_u8(mask, self.dest, self.bank, gt=self.gt, counts=self.counts)
+        if self.table is not None:
+            ops.score_exceed(logits, self.gt, self.dest, self.table, self.exceed)
         return logits, mask, feats
 
     def __call__(self, frames_u8, gt_u8=None):
@@ -254,6 +318,8 @@ class VideoPredictor(GraphedForward):
         self._uploaded.record()
         if gt_u8 is not None:
             ops.frame_metrics(self.counts, n, SIDE * SIDE, acc=self.acc, accumulate=True)
+            if self.table is not None:
+                ops.sweep_metrics(self.exceed, n, SIDE * SIDE, acc=self.sweep_acc, pooled=self.sweep_pooled, accumulate=True)
         return self.bank[:n].view(n, SIDE, SIDE)
 
     def _resize_gt(self, gt_u8, n):
@@ -275,8 +341,19 @@ class VideoPredictor(GraphedForward):
         """The device [sum F1, sum IoU, n] over every frame scored since the last reset: what evaluate.finalize_metrics takes."""
         return self.acc
 
+    def sweep_vector(self):
+        """(table (K,) float32, sweep_acc (K, 3) float64, sweep_pooled (2, K + 1) int64) on the device: the thresholds, per threshold
+        [sum F1, sum IoU, n] and the pooled exceed counts over every frame scored since the last reset -- what
+        evaluate.finalize_sweep takes.  Only in a predictor built with sweep=."""
+        if self.table is None:
+            raise RuntimeError("VideoPredictor.sweep_vector: this predictor was built without sweep=")
+        return self.table, self.sweep_acc, self.sweep_pooled
+
     def reset_metrics(self) -> None:
         self.acc.zero_()
+        if self.table is not None:
+            self.sweep_acc.zero_()
+            self.sweep_pooled.zero_()
 
     def write_masks(self, dirname, frame_numbers) -> None:
         """Saves the masks of the last predict as '%04d_instance_%02d.png' % (frame_number, 0) (test.py:109-111), one per entry of
