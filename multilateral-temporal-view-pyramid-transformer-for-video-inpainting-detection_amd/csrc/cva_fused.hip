@@ -31,7 +31,8 @@
 //     (the fp32 form: 154 | 184 | 172 | 172 / 0 / 44 | 44 | 47 | 47 / 73,728 B / 2)
 //   deform_out_combine_kernel<96 | 192 | 384 | 768, true>  54 | 58 | 60 | 58 / 0 / 20 / 20,480 B / 8
 //     (the fp32 form: 54 / 0 / 20 / 36,864 B / 4)
-#include "common.h"
+#include "cva_pairing.h"
+#include "../../include/mumpy_hip_ext8.h"
 using namespace mumpy;
 
 namespace {
@@ -56,11 +57,12 @@ __device__ __forceinline__ void divmod49(unsigned m, unsigned& q, unsigned& r) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-template <int C, bool MM16>
+// GROUPED: the pairing rule of cva_pairing.h; <false> carries nq alone and is the kernel it was
+template <int C, bool MM16, bool GROUPED>
 __global__ __launch_bounds__(256, 2) void deform_sample_kv_kernel(const float* __restrict__ x2, const float* __restrict__ pos,
                                                                   const float* __restrict__ Wkv, const float* __restrict__ bkv,
-                                                                  float* __restrict__ kv, int Hs2, int W, int nWx, int nW2, int nq,
-                                                                  int M, unsigned gn) {
+                                                                  float* __restrict__ kv, int Hs2, int W, int nWx, int nW2,
+                                                                  CvaPairing<GROUPED> pair, int M, unsigned gn) {
     constexpr int BM = 64, BN = 192, TN = 3, N = 2 * C, K = C, CG = C / 3, NK = K / BK, CPG = CG / BK;   // CPG: chunks per group
     constexpr int A_LD = BM / 32, B_LD = BN / 32;
     __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * (MM16 ? LDH : LDR)];
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256, 2) void deform_sample_kv_kernel(const float* _
         const unsigned b = b2 / (unsigned)nW2, n = b2 - b * (unsigned)nW2;
         const unsigned wy = n / (unsigned)nWx, wx = n - wy * (unsigned)nWx;
         abase[i] = x2 + (((int64_t)b * Hs2 + wy * WS) * W + wx * WS) * C + 4 * ld_c4;
-        apos[i] = pos + ((int64_t)(b2 % (unsigned)nq) * 3 * WT + p) * 2;
+        apos[i] = pos + ((int64_t)cva_q_window(b2, pair) * 3 * WT + p) * 2;
     }
     auto set_group = [&](int g) {
 #pragma unroll
@@ -306,10 +308,11 @@ __global__ __launch_bounds__(256, 2) void deform_out_combine_kernel(const float*
 
 }  // namespace
 
-// one validation + launch body per kernel; `who` names the entry in mumpy_last_error
+// one validation + launch body per kernel; `who` names the entry in mumpy_last_error.  groups: 1 from the frozen entries (the
+// <GROUPED = false> kernels, no refusal added), any value from the grouped ones (include/mumpy_hip_ext8.h)
 template <bool MM16>
 static int sample_kv_launch(const char* who, const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv, int B,
-                            int Hs2, int W, int C, int nq, void* stream) {
+                            int Hs2, int W, int C, int nq, int groups, void* stream) {
     MUMPY_REQUIRE(x2 && pos && Wkv && bkv && kv, MUMPY_ENULL, "%s: null pointer", who);
     MUMPY_REQUIRE(aligned16(x2) && aligned16(Wkv) && aligned16(kv), MUMPY_EALIGN, "%s: pointers must be 16-byte aligned", who);
     MUMPY_REQUIRE(B > 0 && Hs2 > 0 && W > 0 && Hs2 % WS == 0 && W % WS == 0 && nq > 0, MUMPY_EINVAL,
@@ -322,9 +325,15 @@ static int sample_kv_launch(const char* who, const float* x2, const float* pos, 
     const unsigned gn = (unsigned)((2 * C + 191) / 192);
     const int64_t grid = ((M + 63) / 64) * gn;
     MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "%s: too many tiles", who);
+    CvaPairing<true> pg;
+    const int bad = cva_grouping(who, nwin, nq, B, groups, &pg);
+    if (bad) return bad;
+    const CvaPairing<false> p1 = {nq};
+#define MUMPY_SKV_AS(C_, G_, P_)                                                                                             \
+    hipLaunchKernelGGL((deform_sample_kv_kernel<C_, MM16, G_>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), x2, pos, Wkv, \
+                       bkv, kv, Hs2, W, nWx, nW2, P_, (int)M, gn)
 #define MUMPY_SKV(C_)                                                                                                        \
-    hipLaunchKernelGGL((deform_sample_kv_kernel<C_, MM16>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), x2, pos, Wkv, \
-                       bkv, kv, Hs2, W, nWx, nW2, nq, (int)M, gn)
+    if (groups > 1) MUMPY_SKV_AS(C_, true, pg); else MUMPY_SKV_AS(C_, false, p1)
     switch (C) {
         case 96: MUMPY_SKV(96); break;
         case 192: MUMPY_SKV(192); break;
@@ -332,6 +341,7 @@ static int sample_kv_launch(const char* who, const float* x2, const float* pos, 
         default: MUMPY_SKV(768); break;
     }
 #undef MUMPY_SKV
+#undef MUMPY_SKV_AS
     MUMPY_CHECK_LAUNCH(who);
     return 0;
 }
@@ -366,12 +376,22 @@ static int out_combine_launch(const char* who, const float* o, const float* Wout
 
 extern "C" int mumpy_deform_sample_kv_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv, int B,
                                           int Hs2, int W, int C, int nq, void* stream) {
-    return sample_kv_launch<false>("deform_sample_kv", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, stream);
+    return sample_kv_launch<false>("deform_sample_kv", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, 1, stream);
+}
+
+extern "C" int mumpy_deform_sample_kv_grouped_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv,
+                                                  int B, int Hs2, int W, int C, int nq, int groups, void* stream) {
+    return sample_kv_launch<false>("deform_sample_kv_grouped", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, groups, stream);
+}
+
+extern "C" int mumpy_deform_sample_kv_mm16_grouped_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv,
+                                                       float* kv, int B, int Hs2, int W, int C, int nq, int groups, void* stream) {
+    return sample_kv_launch<true>("deform_sample_kv_mm16_grouped", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, groups, stream);
 }
 
 extern "C" int mumpy_deform_sample_kv_mm16_fwd(const float* x2, const float* pos, const float* Wkv, const float* bkv, float* kv,
                                                int B, int Hs2, int W, int C, int nq, void* stream) {
-    return sample_kv_launch<true>("deform_sample_kv_mm16", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, stream);
+    return sample_kv_launch<true>("deform_sample_kv_mm16", x2, pos, Wkv, bkv, kv, B, Hs2, W, C, nq, 1, stream);
 }
 
 extern "C" int mumpy_deform_out_combine_fwd(const float* o, const float* Wout, const float* bout, const float* x1, float* out, int B,

@@ -3,7 +3,8 @@
 // The attention + r-tuple aggregation lives in deform_attention.hip (win_attn_cross_kernel); q/k/v/out projections
 // and `pre` are mumpy_linear_fwd.
 #include <stdlib.h>
-#include "common.h"
+#include "cva_pairing.h"
+#include "../../include/mumpy_hip_ext8.h"
 using namespace mumpy;
 
 namespace {
@@ -141,16 +142,17 @@ __global__ __launch_bounds__(256) void deform_offsets_kernel(const float* __rest
 // HBM sees x2 once and the sampled map once.  Window decode is scalar (per block) and the channel count is a template
 // constant, so the per-thread index math is two constant divisions (the first version spent its time in 64-bit
 // runtime divisions: 3.6 TB/s).
-template <int C>
+// GROUPED (both sampling kernels): the pairing rule of cva_pairing.h; <false> carries nq alone and is the kernel it was.
+template <int C, bool GROUPED>
 __global__ __launch_bounds__(256) void deform_sample_kernel(const float* __restrict__ x2, const float* __restrict__ pos,
                                                             float* __restrict__ out, int Hs2, int W, int nWx, int nW2,
-                                                            int nq) {
+                                                            CvaPairing<GROUPED> pair) {
     constexpr int C4N = C / 4, CG = C / 3;
     const int b2 = blockIdx.x;
     const int b = b2 / nW2, n = b2 - b * nW2;
     const int wy = n / nWx, wx = n - wy * nWx;
     const float* base = x2 + ((int64_t)b * Hs2 * W + (int64_t)wy * WS * W + wx * WS) * C;   // window's top-left token
-    const float* pw = pos + (int64_t)(b2 % nq) * 3 * WT * 2;
+    const float* pw = pos + (int64_t)cva_q_window(b2, pair) * 3 * WT * 2;
     float* ob = out + (int64_t)b2 * WT * C;
     for (int idx = threadIdx.x; idx < WT * C4N; idx += 256) {
         const int p = idx / C4N, c4 = idx - p * C4N;
@@ -183,10 +185,10 @@ __global__ __launch_bounds__(256) void deform_sample_kernel(const float* __restr
 // all four corner reads of every point come from there, so HBM sees exactly the algorithmic bytes: the direct form above
 // fetched ~1.5x the tile (PMC FETCH_SIZE: corner rows touched a second time after leaving L2) -- profiles/r01_pmc_traffic.md.
 // Eight blocks per CU fit (147 KB of LDS), lanes run over channels so a point's corner read is one contiguous 384-B LDS row.
-template <int C>
+template <int C, bool GROUPED>
 __global__ __launch_bounds__(256) void deform_sample_lds_kernel(const float* __restrict__ x2, const float* __restrict__ pos,
                                                                 float* __restrict__ out, int Hs2, int W, int nWx, int nW2,
-                                                                int nq) {
+                                                                CvaPairing<GROUPED> pair) {
     constexpr int SL = 96, S4 = SL / 4, CG = C / 3;
     __shared__ __attribute__((aligned(16))) float tile[WT * SL];
     const int b2 = blockIdx.x, slab = blockIdx.y;
@@ -199,7 +201,7 @@ __global__ __launch_bounds__(256) void deform_sample_lds_kernel(const float* __r
         *reinterpret_cast<f32x4*>(&tile[tok * SL + 4 * j]) = *reinterpret_cast<const f32x4*>(base + (ty * W + tx) * C + 4 * j);
     }
     __syncthreads();
-    const float* pw = pos + (int64_t)(b2 % nq) * 3 * WT * 2;
+    const float* pw = pos + (int64_t)cva_q_window(b2, pair) * 3 * WT * 2;
     float* ob = out + (int64_t)b2 * WT * C + slab * SL;
     for (int idx = threadIdx.x; idx < WT * S4; idx += 256) {
         const int p = idx / S4, c4 = idx - p * S4;
@@ -288,25 +290,34 @@ extern "C" int mumpy_deform_offsets_fwd(const float* q, const float* dw_w, const
     return 0;
 }
 
-extern "C" int mumpy_deform_sample_fwd(const float* x2, const float* pos, float* out, int B, int Hs2, int W, int C,
-                                       int nq, void* stream) {
-    MUMPY_REQUIRE(x2 && pos && out, MUMPY_ENULL, "deform_sample: null pointer");
-    MUMPY_REQUIRE(aligned16(x2) && aligned16(out), MUMPY_EALIGN, "deform_sample: pointers must be 16-byte aligned");
+// one validation + launch body for the frozen entry (groups = 1) and the grouped one; groups == 1 launches the <GROUPED = false>
+// kernels and adds no refusal to the frozen entry's
+static int sample_launch(const char* who, const float* x2, const float* pos, float* out, int B, int Hs2, int W, int C, int nq,
+                         int groups, void* stream) {
+    MUMPY_REQUIRE(x2 && pos && out, MUMPY_ENULL, "%s: null pointer", who);
+    MUMPY_REQUIRE(aligned16(x2) && aligned16(out), MUMPY_EALIGN, "%s: pointers must be 16-byte aligned", who);
     MUMPY_REQUIRE(B > 0 && Hs2 > 0 && W > 0 && Hs2 % WS == 0 && W % WS == 0 && nq > 0, MUMPY_EINVAL,
-                  "deform_sample: bad grid (%d,%d) / nq=%d", Hs2, W, nq);
+                  "%s: bad grid (%d,%d) / nq=%d", who, Hs2, W, nq);
     MUMPY_REQUIRE(C == 96 || C == 192 || C == 384 || C == 768, MUMPY_EINVAL,
-                  "deform_sample: C=%d is not one of the encoder widths 96/192/384/768", C);
+                  "%s: C=%d is not one of the encoder widths 96/192/384/768", who, C);
     const int nWx = W / WS, nW2 = (Hs2 / WS) * nWx;
     const int64_t nwin = (int64_t)B * nW2;
-    MUMPY_REQUIRE(nwin < (1ll << 31), MUMPY_ERANGE, "deform_sample: too many windows");
+    MUMPY_REQUIRE(nwin < (1ll << 31), MUMPY_ERANGE, "%s: too many windows", who);
+    CvaPairing<true> pg;
+    const int bad = cva_grouping(who, nwin, nq, B, groups, &pg);
+    if (bad) return bad;
+    const bool G = groups > 1;
+    const CvaPairing<false> p1 = {nq};
     static const bool direct = tune_int("MUMPY_SAMPLE_DIRECT", 0) != 0;   // A/B hook
-#define MUMPY_SAMPLE(C_)                                                                                             \
+#define MUMPY_SAMPLE_AS(C_, G_, P_)                                                                                  \
     if (direct)                                                                                                      \
-        hipLaunchKernelGGL(deform_sample_kernel<C_>, dim3((unsigned)nwin), dim3(256), 0, as_stream(stream), x2, pos, out,  \
-                           Hs2, W, nWx, nW2, nq);                                                                    \
+        hipLaunchKernelGGL((deform_sample_kernel<C_, G_>), dim3((unsigned)nwin), dim3(256), 0, as_stream(stream), x2, pos, out, \
+                           Hs2, W, nWx, nW2, P_);                                                                    \
     else                                                                                                             \
-        hipLaunchKernelGGL(deform_sample_lds_kernel<C_>, dim3((unsigned)nwin, C_ / 96), dim3(256), 0, as_stream(stream), x2, \
-                           pos, out, Hs2, W, nWx, nW2, nq)
+        hipLaunchKernelGGL((deform_sample_lds_kernel<C_, G_>), dim3((unsigned)nwin, C_ / 96), dim3(256), 0, as_stream(stream), x2, \
+                           pos, out, Hs2, W, nWx, nW2, P_)
+#define MUMPY_SAMPLE(C_)                                                                                             \
+    if (G) { MUMPY_SAMPLE_AS(C_, true, pg); } else { MUMPY_SAMPLE_AS(C_, false, p1); }
     switch (C) {
         case 96: MUMPY_SAMPLE(96); break;
         case 192: MUMPY_SAMPLE(192); break;
@@ -314,9 +325,22 @@ extern "C" int mumpy_deform_sample_fwd(const float* x2, const float* pos, float*
         default: MUMPY_SAMPLE(768); break;
     }
 #undef MUMPY_SAMPLE
-    MUMPY_CHECK_LAUNCH("deform_sample");
+#undef MUMPY_SAMPLE_AS
+    MUMPY_CHECK_LAUNCH(who);
     return 0;
 }
+
+extern "C" int mumpy_deform_sample_fwd(const float* x2, const float* pos, float* out, int B, int Hs2, int W, int C,
+                                       int nq, void* stream) {
+    return sample_launch("deform_sample", x2, pos, out, B, Hs2, W, C, nq, 1, stream);
+}
+
+extern "C" int mumpy_deform_sample_grouped_fwd(const float* x2, const float* pos, float* out, int B, int Hs2, int W, int C, int nq,
+                                               int groups, void* stream) {
+    return sample_launch("deform_sample_grouped", x2, pos, out, B, Hs2, W, C, nq, groups, stream);
+}
+
+extern "C" int mumpy_ext8_version(void) { return MUMPY_EXT8_VERSION; }
 
 extern "C" int mumpy_deform_combine_fwd(const float* x1, const float* Yt, float* out, int B, int H, int W, int C,
                                         void* stream) {

@@ -34,16 +34,22 @@
 // training tape) are the backward of win_attn_cross_mm16_kernel on the bf16 MFMA; their form, arithmetic and measurements are above them.
 #include <stdlib.h>
 #include "win_attn_unit.h"
+#include "cva_pairing.h"
 #include "../../include/mumpy_hip_ext2.h"
+#include "../../include/mumpy_hip_ext8.h"
 
 namespace {
 
+// GROUPED (the three forward kernels): the pairing rule of cva_pairing.h.  <false> carries the q window count B1w alone, where it
+// always was in this struct, and is the kernel it was.
+template <bool GROUPED>
 struct CrossArgs {
     const float* q;        // (B, H*W, C) raster
     const float* kv;       // (B2w, 49, 2C) window-major
     const float* padmask;  // (1,64,64)
     float* out;            // (B1w, 49, C) window-major
-    int B, H, W, C, nH, r, nWx, nWf, B1w;
+    int B, H, W, C, nH, r, nWx, nWf;
+    CvaPairing<GROUPED> pair;   // .nq = B1w
     float scale;
     int64_t units;
 };
@@ -57,8 +63,8 @@ __device__ __forceinline__ f32x4 pad_bias(int jt, int g, int h) { return pad_key
 // hits L2) and its own 32 queries and runs one qk_product / bias_softmax / pv_product.  The loop over the r kv windows stays inside
 // the wave, in the order t = 0 .. r-1, and every product and softmax is the same instruction sequence on the same values, so the
 // outputs are bitwise those of the one-wave form; a unit's dependent chain is roughly half as long.
-template <bool SPLIT>
-__global__ __launch_bounds__(256, 2) void win_attn_cross_kernel(CrossArgs a) {
+template <bool SPLIT, bool GROUPED>
+__global__ __launch_bounds__(256, 2) void win_attn_cross_kernel(CrossArgs<GROUPED> a) {
     __shared__ int tok_tab[4][64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c = lane & 31, h = lane >> 5;
@@ -74,7 +80,7 @@ __global__ __launch_bounds__(256, 2) void win_attn_cross_kernel(CrossArgs a) {
 
     for (int t = 0; t < a.r; ++t) {
         const int64_t b2 = b1 * a.r + t;                  // kv window; adjacent r-tuples are summed (deform:394-395)
-        const int qw = (int)(b2 % a.B1w);                 // q window = kv window mod B1 (x1.repeat, deform:330)
+        const int qw = (int)cva_q_window(b2, a.pair);     // q window = kv window mod B1 (x1.repeat, deform:330), per group
         const int qb = qw / a.nWf, qn = qw - qb * a.nWf;
         const int wy = qn / a.nWx, wx = qn - wy * a.nWx;
         __builtin_amdgcn_wave_barrier();
@@ -122,7 +128,8 @@ __global__ __launch_bounds__(256, 2) void win_attn_cross_kernel(CrossArgs a) {
 // raster (rewritten per kv window, its q window changes with t), tk the kv rows of a window (slot * 8C, the same for every t); padded
 // slots 49..63 are clamped to slot 48 -- finite duplicates whose scores get -1e30 (keys) or are never stored (queries).  1 / row sum
 // lives on the query's lane and the product has the query in its registers: it crosses through 64 floats of LDS per wave.
-__global__ __launch_bounds__(256, 2) void win_attn_cross_mm16_kernel(CrossArgs a) {
+template <bool GROUPED>
+__global__ __launch_bounds__(256, 2) void win_attn_cross_mm16_kernel(CrossArgs<GROUPED> a) {
     __shared__ __attribute__((aligned(16))) uint32_t tok_q[4][64];
     __shared__ __attribute__((aligned(16))) uint32_t tok_k[4][64];
     __shared__ __attribute__((aligned(16))) float inv_s[4][64];
@@ -142,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void win_attn_cross_mm16_kernel(CrossArgs a
 
     for (int t = 0; t < a.r; ++t) {
         const int64_t b2 = b1 * a.r + t;                  // kv window; adjacent r-tuples are summed (deform:394-395)
-        const int qw = (int)(b2 % a.B1w);                 // q window = kv window mod B1 (x1.repeat, deform:330)
+        const int qw = (int)cva_q_window(b2, a.pair);     // q window = kv window mod B1 (x1.repeat, deform:330), per group
         const int qb = qw / a.nWf, qn = qw - qb * a.nWf;
         const int wy = qn / a.nWx, wx = qn - wy * a.nWx;
         __builtin_amdgcn_wave_barrier();
@@ -591,31 +598,40 @@ extern "C" int mumpy_deform_attention_plan(int B, int H, int W, int C, int r) {
     return cross_plan((int64_t)B * (H / WS) * (W / WS) * (C / HD));
 }
 
-// one validation + launch body for both forward kernels; `who` names the entry in mumpy_last_error
-template <bool MM16>
+// one validation + launch body for the forward kernels; `who` names the entry in mumpy_last_error.  GROUPED is chosen by the
+// caller below from groups > 1; the plan (cross_plan) is a function of the unit count alone, so it holds for every grouping.
+template <bool MM16, bool GROUPED>
 static int cross_launch(const char* who, const float* q, const float* kv, const float* padmask, float* out, int B, int H, int W, int C,
-                        int r, float scale, void* stream) {
+                        int r, float scale, int groups, void* stream) {
     MUMPY_REQUIRE(q && kv && padmask && out, MUMPY_ENULL, "%s: null pointer", who);
     MUMPY_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(padmask) && aligned16(out), MUMPY_EALIGN,
                   "%s: pointers must be 16-byte aligned", who);
     MUMPY_REQUIRE(B > 0 && H > 0 && W > 0 && H % WS == 0 && W % WS == 0 && r >= 1, MUMPY_EINVAL,
                   "%s: bad grid (%d,%d) or ratio %d", who, H, W, r);
     MUMPY_REQUIRE(C > 0 && C % HD == 0, MUMPY_EINVAL, "%s: C=%d not a multiple of 32", who, C);
-    CrossArgs a;
+    CrossArgs<GROUPED> a;
     a.q = q; a.kv = kv; a.padmask = padmask; a.out = out;
     a.B = B; a.H = H; a.W = W; a.C = C; a.nH = C / HD; a.r = r;
-    a.nWx = W / WS; a.nWf = (H / WS) * (W / WS); a.B1w = B * a.nWf; a.scale = scale;
-    a.units = (int64_t)a.B1w * a.nH;
+    a.nWx = W / WS; a.nWf = (H / WS) * (W / WS); a.scale = scale;
+    const int64_t B1w = (int64_t)B * a.nWf;
+    if constexpr (GROUPED) {
+        const int bad = cva_grouping(who, B1w * r, B1w, B, groups, &a.pair);
+        if (bad) return bad;
+    } else {
+        a.pair.nq = (int)B1w;
+    }
+    a.units = (int64_t)a.pair.nq * a.nH;
     const int64_t grid = (a.units + 3) / 4;
     MUMPY_REQUIRE(grid < (1ll << 31), MUMPY_ERANGE, "%s: too many windows", who);
     if (MM16) {
         MUMPY_REQUIRE((int64_t)H * W * C * 4 < (1ll << 32), MUMPY_ERANGE, "%s: image too large for 32-bit row offsets", who);
-        hipLaunchKernelGGL(win_attn_cross_mm16_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+        hipLaunchKernelGGL(win_attn_cross_mm16_kernel<GROUPED>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     } else {
         if (cross_plan(a.units) & 1)
-            hipLaunchKernelGGL(win_attn_cross_kernel<true>, dim3((unsigned)((a.units + 1) / 2)), dim3(256), 0, as_stream(stream), a);
+            hipLaunchKernelGGL((win_attn_cross_kernel<true, GROUPED>), dim3((unsigned)((a.units + 1) / 2)), dim3(256), 0,
+                               as_stream(stream), a);
         else
-            hipLaunchKernelGGL(win_attn_cross_kernel<false>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+            hipLaunchKernelGGL((win_attn_cross_kernel<false, GROUPED>), dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
     }
     MUMPY_CHECK_LAUNCH(who);
     return 0;
@@ -623,12 +639,29 @@ static int cross_launch(const char* who, const float* q, const float* kv, const 
 
 extern "C" int mumpy_deform_attention_fwd(const float* q, const float* kv, const float* padmask, float* out, int B,
                                           int H, int W, int C, int r, float scale, void* stream) {
-    return cross_launch<false>("deform_attention", q, kv, padmask, out, B, H, W, C, r, scale, stream);
+    return cross_launch<false, false>("deform_attention", q, kv, padmask, out, B, H, W, C, r, scale, 1, stream);
 }
 
 extern "C" int mumpy_deform_attention_mm16_fwd(const float* q, const float* kv, const float* padmask, float* out, int B,
                                                int H, int W, int C, int r, float scale, void* stream) {
-    return cross_launch<true>("deform_attention_mm16", q, kv, padmask, out, B, H, W, C, r, scale, stream);
+    return cross_launch<true, false>("deform_attention_mm16", q, kv, padmask, out, B, H, W, C, r, scale, 1, stream);
+}
+
+// include/mumpy_hip_ext8.h: groups == 1 is the frozen entry's launch, after the grouped entry's own refusals
+extern "C" int mumpy_deform_attention_grouped_fwd(const float* q, const float* kv, const float* padmask, float* out, int B, int H,
+                                                  int W, int C, int r, float scale, int groups, void* stream) {
+    const char* who = "deform_attention_grouped";
+    MUMPY_REQUIRE(groups >= 1, MUMPY_EINVAL, "%s: groups=%d must be at least 1", who, groups);
+    if (groups == 1) return cross_launch<false, false>(who, q, kv, padmask, out, B, H, W, C, r, scale, 1, stream);
+    return cross_launch<false, true>(who, q, kv, padmask, out, B, H, W, C, r, scale, groups, stream);
+}
+
+extern "C" int mumpy_deform_attention_mm16_grouped_fwd(const float* q, const float* kv, const float* padmask, float* out, int B,
+                                                       int H, int W, int C, int r, float scale, int groups, void* stream) {
+    const char* who = "deform_attention_mm16_grouped";
+    MUMPY_REQUIRE(groups >= 1, MUMPY_EINVAL, "%s: groups=%d must be at least 1", who, groups);
+    if (groups == 1) return cross_launch<true, false>(who, q, kv, padmask, out, B, H, W, C, r, scale, 1, stream);
+    return cross_launch<true, true>(who, q, kv, padmask, out, B, H, W, C, r, scale, groups, stream);
 }
 
 extern "C" int64_t mumpy_deform_attention_bwd_workspace_bytes(int64_t B2w, int C) {

@@ -17,6 +17,9 @@ The reference's index behaviour is specification and is reproduced exactly:
 kv window i pairs with q window (i mod B1) (`x1.repeat`, deform:330), the "(b t)" sum adds ADJACENT kv windows
 (deform:394-395), and the output is the flat (C,49) image re-read as (49,C) (deform:403).  The (B, r*nH, 49, 49)
 attention tensor the reference also returns is discarded by its only caller (mTVE:284) and is not materialised.
+Because B1 counts the q windows of every clip of the batch, that rule couples the clips of a batch.  Under
+ops.set_clip_coupling("clip") the block entries (attend_combine, attend_raster) apply it inside each clip instead (groups = b
+on the grouped kernels, include/mumpy_hip_ext8.h; ops.cva_pairing is the host statement): every clip pairs as a batch of one.
 """
 import torch
 import torch.nn as nn
@@ -90,16 +93,18 @@ class SwinDAttention(nn.Module):
                                  b, h, w, self.nc)
         return q, pos
 
-    def _run(self, x1, x2, q_grid, kv_grid, prep=None):
+    def _run(self, x1, x2, q_grid, kv_grid, prep=None, groups=None):
         """q_grid = (b, h, w): x1 is (b, h*w, C) raster;  kv_grid = (b2, hs2, w2): x2 is (b2, hs2*w2, C) raster.
         Returns proj_out output Yt (nq, 49, C): window-major, token-major, i.e. BEFORE the deform:403 reshape."""
-        o = self._attend(x1, x2, q_grid, kv_grid, prep)
+        o = self._attend(x1, x2, q_grid, kv_grid, prep, groups=groups)
         return ops.linear(o, self.proj_out.weight, self.proj_out.bias)
 
-    def _attend(self, x1, x2, q_grid, kv_grid, prep=None, want_maps=False):
+    def _attend(self, x1, x2, q_grid, kv_grid, prep=None, want_maps=False, groups=None):
         """Everything up to (not including) proj_out: -> o (nq,49,C), the attention output summed over the r-tuples.
         want_maps: also return the attention maps (nq, r*nH, 49, 49) the reference hands back (deform:396) -- a visualisation path
-        (the fast kernel keeps the probabilities in registers; a small separate kernel recomputes them from q and k)."""
+        (the fast kernel keeps the probabilities in registers; a small separate kernel recomputes them from q and k).
+        groups: the pairing rule (ops.cva_pairing).  None follows ops.clip_coupling(), read here, at launch time: b (every clip of
+        the grid pairs as a batch of one) under "clip", 1 (the reference's batch-wide `i mod B1`) under "batch"."""
         c = self.nc
         b, h, w = q_grid
         b2, hs2, w2 = kv_grid
@@ -107,22 +112,31 @@ class SwinDAttention(nn.Module):
         nkv = b2 * (hs2 // 7) * (w2 // 7)
         if nkv % nq:
             raise RuntimeError(f"SwinDAttention: {nkv} kv windows is not a multiple of {nq} q windows")
+        if groups is None:
+            groups = b if ops.clip_coupling() == "clip" else 1
+        if groups > 1 and b2 % groups:
+            raise RuntimeError(f"SwinDAttention: groups={groups} does not divide the kv side's batch {b2}")
         q, pos = prep if prep is not None else self._prep(x1, q_grid)
         wkv = self._wkv.get((self.proj_k.weight, self.proj_v.weight),
                             lambda: torch.cat([self.proj_k.weight.reshape(c, c), self.proj_v.weight.reshape(c, c)], 0))
         bkv = self._bkv.get((self.proj_k.bias, self.proj_v.bias), lambda: torch.cat([self.proj_k.bias, self.proj_v.bias]))
         math = ops.cva_math()                                                     # "bf16": the _mm16 kernels, before any other mode
         if math == "bf16" or (FUSED["sample_kv"] and ops.matrix_math() == "fp32" and ops.storage() == "fp32"):
-            kv = ops.deform_sample_kv(x2, pos, wkv, bkv, b2, hs2, w2, c, nq, math=math)   # sampling = the projection's A loader
+            kv = ops.deform_sample_kv(x2, pos, wkv, bkv, b2, hs2, w2, c, nq, math=math, groups=groups)   # sampling = the projection's A loader
         else:
-            sampled = ops.deform_sample(x2, pos, b2, hs2, w2, c, nq)
+            sampled = ops.deform_sample(x2, pos, b2, hs2, w2, c, nq, groups=groups)
             kv = ops.linear(sampled, wkv, bkv)                                    # (nkv,49,2C)
         pad = self._pad.get((self.proj_q.weight,), lambda: ops.pad_mask().to(x1.device))
-        o = ops.deform_attention(q, kv, pad, b, h, w, c, nkv // nq, self.scale, math=math)      # (nq,49,C)
+        o = ops.deform_attention(q, kv, pad, b, h, w, c, nkv // nq, self.scale, math=math, groups=groups)      # (nq,49,C)
         if not want_maps:
             return o
         # kv window i pairs with q window i mod nq; q is raster (b, h*w, C): gather its windows first (49 x C each)
         qw = q.view(b, h // 7, 7, w // 7, 7, c).permute(0, 1, 3, 2, 4, 5).reshape(nq, 49, c).contiguous()
+        if groups > 1:      # the same rule inside each group: one launch per group on host slices (not a hot path)
+            nqg, nkg = nq // groups, nkv // groups
+            maps = torch.cat([ops.attention_probs(qw[g * nqg:(g + 1) * nqg], kv[g * nkg:(g + 1) * nkg], nkg, self.n_heads, 49, 49, 32,
+                                                  (49 * c, c), (49 * 2 * c, 2 * c), self.scale, q_mod=nqg) for g in range(groups)])
+            return o, maps.reshape(nq, (nkv // nq) * self.n_heads, 49, 49)
         maps = ops.attention_probs(qw, kv, nkv, self.n_heads, 49, 49, 32, (49 * c, c), (49 * 2 * c, 2 * c), self.scale, q_mod=nq)
         return o, maps.reshape(nq, (nkv // nq) * self.n_heads, 49, 49)                # '(B nH) n m -> B (r nH) n m' (deform:396)
 
@@ -144,13 +158,16 @@ class SwinDAttention(nn.Module):
         `pre`), both raster with frames stacked on rows.  prep: the result of `_prep(x1, (b, h, w))` if already computed."""
         return self._run(x1, x2, (b, h, w), (b, hs2, w), prep)
 
-    def forward(self, x1, x2, return_attention=False):
+    def forward(self, x1, x2, return_attention=False, groups=None):
         """Reference signature (deform:324): x1 (B1,49,C) q windows, x2 (B2,49,C) kv windows, B2 = r*B1.
-        Every window is its own 7x7 image for the kernels.  Returns (y (B1,49,C), None)."""
+        Every window is its own 7x7 image for the kernels.  Returns (y (B1,49,C), None).
+        groups: window lists carry no clip boundaries, so this entry does NOT follow ops.clip_coupling(): None means 1, the
+        reference's pairing over all B1 windows; a caller that knows its clips passes their number (it must divide B1 and B2)."""
         b1, b2, c = x1.shape[0], x2.shape[0], x1.shape[2]
+        groups = 1 if groups is None else groups
         if return_attention:      # the reference returns (x, attn) always (deform:405); here the maps cost a launch, so on request
-            o, maps = self._attend(x1, x2, (b1, 7, 7), (b2, 7, 7), want_maps=True)
+            o, maps = self._attend(x1, x2, (b1, 7, 7), (b2, 7, 7), want_maps=True, groups=groups)
             yt = ops.linear(o, self.proj_out.weight, self.proj_out.bias)
             return yt.transpose(1, 2).reshape(b1, 49, c), maps
-        yt = self._run(x1, x2, (b1, 7, 7), (b2, 7, 7))
+        yt = self._run(x1, x2, (b1, 7, 7), (b2, 7, 7), groups=groups)
         return yt.transpose(1, 2).reshape(b1, 49, c), None       # flat (C,49) re-read as (49,C) (deform:403)

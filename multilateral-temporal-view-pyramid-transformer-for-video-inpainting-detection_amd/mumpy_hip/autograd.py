@@ -616,12 +616,21 @@ class DWConv5Fn(torch.autograd.Function):
         return dx, dw.reshape(ctx.wshape), db
 
 
+def _refuse_clip_coupling(who):
+    """The backward kernels pair kv window b2 with q window b2 % nq only: under ops.set_clip_coupling("clip") the tape would
+    differentiate another function than the one the inference forward computes.  Refused before anything is launched."""
+    if ops.clip_coupling() != "batch":
+        raise RuntimeError(f"{who}: the training tape has no per-clip pairing (ops.set_clip_coupling(\"clip\") is an inference "
+                           "setting; its backward kernels keep the batch-coupled rule) -- set_clip_coupling(\"batch\") to train")
+
+
 class DeformSampleFn(torch.autograd.Function):
     """Bilinear sampling of kv windows at the learned positions (grid_sample semantics of deform:353-356), window form:
     x2w (B2,49,C), pos (nq,3,49,2) -> (B2,49,C); kv window b2 uses pos[b2 % nq]."""
 
     @staticmethod
     def forward(ctx, x2w, pos):
+        _refuse_clip_coupling("DeformSampleFn")
         ctx.save_for_backward(x2w, pos)
         b2, _, c = x2w.shape
         return ops.deform_sample(x2w.reshape(b2, 49, c), pos, b2, 7, 7, c, pos.shape[0])
@@ -640,6 +649,7 @@ class DeformAttentionFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, kv, scale):
+        _refuse_clip_coupling("DeformAttentionFn")
         b1, _, c = q.shape
         r = kv.shape[0] // b1
         ctx.save_for_backward(q, kv)
@@ -742,6 +752,7 @@ def encoder_train(enc, x):
     """Encoder.forward (encoder.py:11-18; ThreeViewSwinTransformer.forward mTVE:732-746) with a backward:
     x (B,T,3,224,224) -> (final_x (B,2304,7,7), view_x[4][3] of (B,1,L,C), dct_x (B,9,224,224)).  The DCT features carry no
     parameters and are computed without a tape."""
+    _refuse_clip_coupling("encoder_train")
     m = enc.base
     b = x.shape[0]
     with torch.no_grad():

@@ -4,7 +4,9 @@ mechanism, torch.nn.DataParallel (test.py:56-58, train.py:290-292).
 
 The forward couples the samples of a micro-batch (SwinDAttention pairs windows across the batch, deform:330,394), so
 the partition unit is the MICRO-BATCH: rank r owns a contiguous slice of the global batch and its result equals the
-reference forward run on that slice alone — not a slice of a whole-batch forward."""
+reference forward run on that slice alone — not a slice of a whole-batch forward.  Under
+ops.set_clip_coupling("clip") the inference forward pairs windows inside each clip, no clip's result depends on
+its batch, and the partition no longer matters: any split of the clips over ranks gives the same per-clip results."""
 import os
 from typing import Tuple
 

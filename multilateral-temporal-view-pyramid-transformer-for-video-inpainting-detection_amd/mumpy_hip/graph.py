@@ -5,9 +5,16 @@ import torch
 
 
 class GraphedForward:
-    def __init__(self, encoder, decoder, example: torch.Tensor, warmup: int = 2, with_mask: bool = False):
+    def __init__(self, encoder, decoder, example: torch.Tensor, warmup: int = 2, with_mask: bool = False, coupling=None):
         """with_mask=True captures Decoder.predict_mask: outputs are (logits, uint8 mask, feats), the thresholded mask
-        of test.py:100-108 coming out of the same last kernel."""
+        of test.py:100-108 coming out of the same last kernel.
+        coupling: "batch" or "clip" -- warm-up and capture run under ops.clip_coupling_as(coupling), whatever the global switch
+        says, and leave the switch as they found it.  None: whatever ops.clip_coupling() says now.  Either way the value is kept
+        in self.coupling and a re-capture (weights moved) uses it again: a graph never changes its pairing."""
+        from . import ops
+        if coupling not in (None, "batch", "clip"):
+            raise ValueError(f"GraphedForward: coupling must be \"batch\", \"clip\" or None, got {coupling!r}")
+        self.coupling = ops.clip_coupling() if coupling is None else coupling
         self.encoder, self.decoder, self.with_mask = encoder, decoder, with_mask
         self.static_x = example.clone()
         self._warmup = warmup
@@ -66,8 +73,10 @@ class GraphedForward:
         return False
 
     def _fwd(self):
+        from . import ops
         from .pipeline import fused_forward
-        return fused_forward(self.encoder, self.decoder, self.static_x, with_mask=self.with_mask)
+        with ops.clip_coupling_as(self.coupling):                  # warm-up and capture only: a replay launches what was captured
+            return fused_forward(self.encoder, self.decoder, self.static_x, with_mask=self.with_mask)
 
     def __call__(self, x: torch.Tensor):
         """Returns the static (logits, feats) buffers; contents are overwritten by the next call.
@@ -77,7 +86,8 @@ class GraphedForward:
         steps.  The check is host-only (keys of the derived caches, addresses of the parameters; no kernel, no sync) and runs
         while the previous replay is still on the GPU.  An in-place edit through `.data` (p.data.mul_()) or a swapped
         nn.Parameter object is invisible to torch and to this check: call mumpy_hip.state.bump_weights_epoch() after it.
-        Mode switches (ops.set_storage, set_matrix_math, set_attention_math, set_cva_math) after capture are not followed."""
+        Mode switches (ops.set_storage, set_matrix_math, set_attention_math, set_cva_math, set_clip_coupling) after capture are
+        not followed."""
         if self._stale():
             self._capture()
         self.static_x.copy_(x, non_blocking=True)

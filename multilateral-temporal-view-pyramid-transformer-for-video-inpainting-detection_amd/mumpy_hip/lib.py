@@ -172,6 +172,17 @@ EXT7_SIGNATURES = {
 }
 EXT7_VERSION = 1
 
+# ... and after that one; mirrors include/mumpy_hip_ext8.h one to one (tests/test_clip_coupling_host.py checks it): the frozen
+# siblings' arguments plus `int groups` before the stream
+EXT8_SIGNATURES = {
+    "mumpy_deform_sample_grouped_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+    "mumpy_deform_sample_kv_grouped_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+    "mumpy_deform_sample_kv_mm16_grouped_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+    "mumpy_deform_attention_grouped_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
+    "mumpy_deform_attention_mm16_grouped_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
+}
+EXT8_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -242,8 +253,12 @@ def load_library():
     lib.mumpy_ext7_version.argtypes = []
     if lib.mumpy_ext7_version() != EXT7_VERSION:
         raise RuntimeError(f"{path}: seventh extension version {lib.mumpy_ext7_version()} != binding {EXT7_VERSION}; rebuild")
+    lib.mumpy_ext8_version.restype = c_i
+    lib.mumpy_ext8_version.argtypes = []
+    if lib.mumpy_ext8_version() != EXT8_VERSION:
+        raise RuntimeError(f"{path}: eighth extension version {lib.mumpy_ext8_version()} != binding {EXT8_VERSION}; rebuild")
     for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES,
-                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES}.items():
+                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES, **EXT8_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

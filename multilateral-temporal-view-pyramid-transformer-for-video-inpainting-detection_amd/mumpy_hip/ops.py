@@ -236,6 +236,73 @@ def cva_math() -> str:
     return _CVA_MATH
 
 
+def _clip_coupling_from_env() -> str:
+    mode = os.environ.get("MUMPY_CLIP_COUPLING", "") or "batch"
+    if mode not in ("batch", "clip"):
+        raise ValueError(f"MUMPY_CLIP_COUPLING: unknown clip coupling {mode!r}")
+    return mode
+
+
+_CLIP_COUPLING = _clip_coupling_from_env()       # read once, at import
+
+
+def set_clip_coupling(mode: str) -> None:
+    """How the cross-view attention (SwinDAttention) pairs windows across the clips of a batch in the INFERENCE forward.
+    "batch" (default): the reference's rule -- kv window i attends with q window i mod B1 (`x1.repeat`, deform:330), B1 counting the
+    q windows of EVERY clip, so a clip's result depends on the batch it travels in.  "clip": the same rule applied inside each clip
+    (groups = batch size on the grouped kernels, include/mumpy_hip_ext8.h): every clip is computed as the reference computes a batch
+    of one, whatever the batch size, the order of the clips or the padding of a tail; the launches are the full-batch ones.
+    For a batch of one, and wherever r = 1, the two coincide.  The ops never follow the switch by themselves (their groups= defaults
+    to 1); the module does.  The training tape has no grouped backward: encoder_train and the deform autograd functions refuse
+    "clip".  The initial value is the environment variable MUMPY_CLIP_COUPLING, read when this module is imported.  Read at launch
+    time: a GraphedForward keeps the pairing it was captured with (its coupling= argument pins it)."""
+    global _CLIP_COUPLING
+    if mode not in ("batch", "clip"):
+        raise ValueError(f"unknown clip coupling {mode!r}")
+    _CLIP_COUPLING = mode
+
+
+def clip_coupling() -> str:
+    return _CLIP_COUPLING
+
+
+class clip_coupling_as:
+    """`with ops.clip_coupling_as("clip"): ...` -- set_clip_coupling for the body; the previous value is restored on exit, also when
+    the body raises.  None leaves the switch alone (the body follows whatever it says)."""
+
+    def __init__(self, mode: Optional[str]):
+        if mode not in (None, "batch", "clip"):
+            raise ValueError(f"unknown clip coupling {mode!r}")
+        self.mode = mode
+
+    def __enter__(self):
+        self.prev = _CLIP_COUPLING
+        if self.mode is not None:
+            set_clip_coupling(self.mode)
+        return self
+
+    def __exit__(self, *exc):
+        set_clip_coupling(self.prev)
+        return False
+
+
+def cva_pairing(nkv: int, nq: int, groups: int = 1):
+    """Host statement of the pairing rule of the cross-view attention kernels: -> (q_of_kv, out_of_kv), numpy int64 arrays of length
+    nkv.  kv window i attends with q window q_of_kv[i] and is summed into output window out_of_kv[i] = i // r, r = nkv // nq.  The
+    launch is cut into `groups` equal contiguous groups of nqg = nq // groups q windows and r nqg kv windows, and inside group
+    g = i // (r nqg) the reference's rule holds: q = g nqg + (i - g r nqg) mod nqg.  groups = 1: i mod nq (deform:330)."""
+    import numpy as np
+    nkv, nq, groups = int(nkv), int(nq), int(groups)
+    if nq < 1 or nkv < 1 or nkv % nq:
+        raise ValueError(f"cva_pairing: {nkv} kv windows are not a positive multiple of {nq} q windows")
+    if groups < 1 or nq % groups:
+        raise ValueError(f"cva_pairing: groups={groups} must be at least 1 and divide the {nq} q windows")
+    r, nqg = nkv // nq, nq // groups
+    i = np.arange(nkv, dtype=np.int64)
+    g = i // (r * nqg)
+    return g * nqg + (i - g * r * nqg) % nqg, i // r
+
+
 def _mlp_fusion_from_env() -> bool:
     v = os.environ.get("MUMPY_MLP_FUSED", "") or "0"
     if v not in ("0", "1"):
@@ -812,25 +879,37 @@ def deform_offsets(q, dw_w, dw_b, ln_g, ln_b, pw_w, b, h, w, c):
     return pos
 
 
-def deform_sample(x2, pos, b, hs2, w, c, nq):
+def _grouped(entry, groups, b, nq, who):
+    """-> (C-ABI entry, trailing arguments before the stream) of a cross-view attention op for groups = 1 (the frozen entry, called
+    exactly as before there was a grouped one) or more (its _grouped form, include/mumpy_hip_ext8.h).  The refusals are the
+    library's, restated here so that a bad grouping never reaches a launch."""
+    if not isinstance(groups, int) or isinstance(groups, bool) or groups < 1 or nq % groups or b % groups:
+        raise ValueError(f"{who}: groups={groups!r} must be a positive int that divides the {nq} q windows and the batch {b}")
+    return (entry, ()) if groups == 1 else (entry.replace("_fwd", "_grouped_fwd"), (groups,))
+
+
+def deform_sample(x2, pos, b, hs2, w, c, nq, groups=1):
+    """groups: the pairing rule (cva_pairing): 1 is the reference's `i mod nq`, b is per-clip pairing."""
+    entry, extra = _grouped("mumpy_deform_sample_fwd", groups, b, nq, "deform_sample")
     x2, pos = _rd(x2, "x2", b * hs2 * w * c, "deform_sample"), _rd(pos, "pos", nq * 3 * 49 * 2, "deform_sample")
     nw2 = b * (hs2 // 7) * (w // 7)
     out = torch.empty(nw2, 49, c, device=x2.device, dtype=torch.float32)
-    _call("mumpy_deform_sample_fwd", _p(x2), _p(pos), _p(out), b, hs2, w, c, nq, _stream(),
+    _call(entry, _p(x2), _p(pos), _p(out), b, hs2, w, c, nq, *extra, _stream(),
           work=4.0 * (2 * nw2 * 49 * c + nw2 * 3 * 49 * 2))       # bytes: read kv once, write sampled once, read offsets
     return out
 
 
-def deform_sample_kv(x2, pos, wkv, bkv, b, hs2, w, c, nq, math="fp32"):
+def deform_sample_kv(x2, pos, wkv, bkv, b, hs2, w, c, nq, math="fp32", groups=1):
     """[proj_k | proj_v] of the bilinearly sampled kv windows in one launch (the sampled map is never materialised).
-    math="bf16": the fp32 sample and wkv are rounded to bf16 while staged and multiplied on the bf16 MFMA (see set_cva_math)."""
-    entry = _mm16("mumpy_deform_sample_kv_fwd", math)
+    math="bf16": the fp32 sample and wkv are rounded to bf16 while staged and multiplied on the bf16 MFMA (see set_cva_math).
+    groups: the pairing rule (cva_pairing): 1 is the reference's `i mod nq`, b is per-clip pairing."""
     who = "deform_sample_kv"
+    entry, extra = _grouped(_mm16("mumpy_deform_sample_kv_fwd", math), groups, b, nq, who)
     x2, pos = _rd(x2, "x2", b * hs2 * w * c, who), _rd(pos, "pos", nq * 3 * 49 * 2, who)
     wkv, bkv = _rd(wkv, "wkv", 2 * c * c, who), _rd(bkv, "bkv", 2 * c, who)
     nw2 = b * (hs2 // 7) * (w // 7)
     kv = torch.empty(nw2, 49, 2 * c, device=x2.device, dtype=torch.float32)
-    _call(entry, _p(x2), _p(pos), _p(wkv), _p(bkv), _p(kv), b, hs2, w, c, nq,
+    _call(entry, _p(x2), _p(pos), _p(wkv), _p(bkv), _p(kv), b, hs2, w, c, nq, *extra,
           _stream(), work=2.0 * nw2 * 49 * 2 * c * c)
     return kv
 
@@ -848,17 +927,18 @@ def deform_out_combine(o, wout, bout, x1, b, h, w, c, math="fp32"):
     return out
 
 
-def deform_attention(q, kv, padmask, b, h, w, c, r, scale, math="fp32"):
+def deform_attention(q, kv, padmask, b, h, w, c, r, scale, math="fp32", groups=1):
     """Cross-view attention core + r-tuple sum.  math is explicit and defaults to "fp32" whatever set_cva_math says: the callers that
     follow the switch (the module's inference forward, and the training tape's DeformAttentionFn, which carries the mode to its
     backward) pass it.  math="bf16": q / k / v rounded to bf16 in registers, both products on the bf16 MFMA, fp32 softmax and
-    accumulation; its backward is deform_attention_bwd(..., math="bf16")."""
-    entry = _mm16("mumpy_deform_attention_fwd", math)
+    accumulation; its backward is deform_attention_bwd(..., math="bf16").  groups: the pairing rule (cva_pairing): 1 is the
+    reference's `i mod B1`, b is per-clip pairing; the backward has no grouped form."""
     b1w = b * (h // 7) * (w // 7)
+    entry, extra = _grouped(_mm16("mumpy_deform_attention_fwd", math), groups, b, b1w, "deform_attention")
     q, kv = _rd(q, "q", b * h * w * c, "deform_attention"), _rd(kv, "kv", b1w * r * 49 * 2 * c, "deform_attention")
     padmask = _rd(padmask, "padmask", 64 * 64, "deform_attention")
     out = torch.empty(b1w, 49, c, device=q.device, dtype=torch.float32)
-    _call(entry, _p(q), _p(kv), _p(padmask), _p(out), b, h, w, c, r, scale,
+    _call(entry, _p(q), _p(kv), _p(padmask), _p(out), b, h, w, c, r, scale, *extra,
           _stream(), work=307328.0 * b1w * r * (c // 32))
     return out
 

@@ -187,10 +187,20 @@ class VideoPredictor(GraphedForward):
     mask at any `batch`.  As in the reference, the forward couples the clips of one batch (SwinDAttention pairs windows across the
     batch, see mumpy_hip/distributed.py): what comes out at `batch` = B is the model run at batch size B on these clips in this
     order, the padding clips of the tail (copies of the last clip) included, and the GEMM kernels are chosen by the batch's row
-    count -- so results at different `batch` values are not bit for bit the same."""
+    count -- so results at different `batch` values are not bit for bit the same.
+
+    coupling="batch" (the default) is that behaviour: the same launches and the same bits as before the option existed.
+    coupling="clip" runs every forward, eager or captured, under ops.clip_coupling_as("clip"): the cross-view attention pairs
+    windows inside each clip (the grouped kernels of include/mumpy_hip_ext8.h on the full batch), so every clip is computed as the
+    reference's batch-size-1 test.py computes it.  A frame's mask then depends neither on `batch`, nor on which clips share its
+    batch or in what order, nor on the tail's padding clips -- up to the fp32 rounding of the GEMM routes, which are still chosen
+    by the batch's row count (logits agree to ~1e-6 relative, not bit for bit).  The predictor sets the switch around its own
+    forwards only and leaves the global ops.clip_coupling() as it found it."""
 
     def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True, gt_hw=None, gt_chunk=64,
-                 sweep=None):
+                 sweep=None, coupling="batch"):
+        if coupling not in ("batch", "clip"):
+            raise ValueError(f"VideoPredictor: coupling must be \"batch\" or \"clip\", got {coupling!r}")
         T, batch, max_frames = int(T), int(batch), int(max_frames)
         clip_frame_indices(1, T)                                     # refuses an even T
         model_t = int(encoder.configs[-1]["num_frames"])
@@ -241,15 +251,16 @@ class VideoPredictor(GraphedForward):
             ops._bilinear_tables(*self.gt_hw, SIDE, SIDE, dev)      # uploaded here, not in the first predict
         clips = torch.zeros(batch, T, 3, SIDE, SIDE, device=dev, dtype=torch.float32)
         if self.graphed:
-            super().__init__(encoder, decoder, clips, with_mask=True)                # static_x is the clip batch
+            super().__init__(encoder, decoder, clips, with_mask=True, coupling=coupling)     # static_x is the clip batch
         else:
-            self.encoder, self.decoder, self.with_mask, self.static_x = encoder, decoder, True, clips
+            self.encoder, self.decoder, self.with_mask, self.static_x, self.coupling = encoder, decoder, True, clips, coupling
 
     def _fwd(self):
         from . import ops
         from .pipeline import fused_forward
         ops.clip_window_u8(self.frames, self.idx, (SIDE, SIDE), out=self.static_x)
-        logits, mask, feats = fused_forward(self.encoder, self.decoder, self.static_x, with_mask=True, thr=self.thr)
+        with ops.clip_coupling_as(self.coupling):                    # eager, warm-up and capture alike; restored on the way out
+            logits, mask, feats = fused_forward(self.encoder, self.decoder, self.static_x, with_mask=True, thr=self.thr)
         ops.mask_score_u8(mask, self.dest, self.bank, gt=self.gt, counts=self.counts)
         if self.table is not None:
             ops.score_exceed(logits, self.gt, self.dest, self.table, self.exceed)
