@@ -37,6 +37,7 @@
 #include "cva_pairing.h"
 #include "../../include/mumpy_hip_ext2.h"
 #include "../../include/mumpy_hip_ext8.h"
+#include "../../include/mumpy_hip_ext9.h"
 
 namespace {
 
@@ -204,15 +205,22 @@ __global__ __launch_bounds__(256, 2) void win_attn_cross_mm16_kernel(CrossArgs<G
 // deform:394-395, hands the same dO to its r members).  Same two-orientation scheme as the self-attention backward;
 // no bias (only the 49 -> 64 key padding), scale on the product.  dq_part holds each kv window's contribution to its q
 // window; the caller sums the r contributions per q window.
+// GROUPED (all four backward kernels, include/mumpy_hip_ext9.h): the pairing rule of cva_pairing.h, as in the forward kernels.  <false>
+// carries the q window count alone, where it always was (.nq = B1w), and computes what it computed.
+// Resources of the fp32 pair (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), <false> -> <true>: q kernel 180 VGPRs + 80 AGPRs /
+// 40 -> 44 SGPRs, kv kernel 256 + 62 / 44 -> 48 SGPRs; no LDS, 1 wave per SIMD, no scratch, no spill in all four.
+template <bool GROUPED>
 struct CrossBwdArgs {
     const float* q; const float* kv; const float* dout;
     float* dq_part; float* dkv; float* stats;
-    int C, nH, r, B1w;
+    int C, nH, r;
+    CvaPairing<GROUPED> pair;   // .nq = B1w
     float scale;
     int64_t units;
 };
 
-__global__ __launch_bounds__(256, 1) void deform_attn_bwd_q_kernel(CrossBwdArgs a) {
+template <bool GROUPED>
+__global__ __launch_bounds__(256, 1) void deform_attn_bwd_q_kernel(CrossBwdArgs<GROUPED> a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, h = lane >> 5;
@@ -220,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_q_kernel(CrossBwdArgs 
     if (u >= a.units) return;
     const int head = (int)(u % a.nH);
     const int64_t b2 = u / a.nH;
-    const int64_t qw = b2 % a.B1w, b1 = b2 / a.r;
+    const int64_t qw = cva_q_window(b2, a.pair), b1 = b2 / a.r;
     const uint32_t rq = 4u * a.C, rk = 8u * a.C;                          // row pitches in bytes
     const char* qb = reinterpret_cast<const char*>(a.q + qw * WT * a.C + head * HD);
     const char* kb = reinterpret_cast<const char*>(a.kv + b2 * WT * 2 * a.C + head * HD);
@@ -279,7 +287,8 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_q_kernel(CrossBwdArgs 
     }
 }
 
-__global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs a) {
+template <bool GROUPED>
+__global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs<GROUPED> a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int c = lane & 31, h = lane >> 5;
@@ -287,7 +296,7 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs
     if (u >= a.units) return;
     const int head = (int)(u % a.nH);
     const int64_t b2 = u / a.nH;
-    const int64_t qw = b2 % a.B1w, b1 = b2 / a.r;
+    const int64_t qw = cva_q_window(b2, a.pair), b1 = b2 / a.r;
     const uint32_t rq = 4u * a.C, rk = 8u * a.C;
     const char* qb = reinterpret_cast<const char*>(a.q + qw * WT * a.C + head * HD);
     const char* kb = reinterpret_cast<const char*>(a.kv + b2 * WT * 2 * a.C + head * HD);
@@ -372,7 +381,8 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs
 // dV / dK.
 // Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): q kernel 147 VGPRs / 71 SGPRs / 1,024 B of LDS per block, 3 waves per
 // SIMD; kv kernel 199 / 48 / 5,120 B, 2 waves per SIMD; 0 AGPRs and no scratch in both (the fp32 pair: 180 + 80 and 256 + 62 registers,
-// 1 wave per SIMD).
+// 1 wave per SIMD).  The <GROUPED = true> instantiations: q kernel 147 / 70 / 1,024 B, kv kernel 199 / 52 / 5,120 B, the same occupancy,
+// 0 AGPRs, no scratch, no spill.
 // Measured against the fp32 entry on the same input (tools/kernel_micro.py cva_attn_bwd16; profiles/bf16_cva_train.md): the eight
 // (B1w, r, C) launches of the B=2, T=5 training step, us on one MI355X, medians of 12 alternating replays of 20 captured calls; the
 // backward is the whole entry -- fp32: q kernel, kv kernel and the r - 1 add launches of ops.deform_attention_bwd; bf16: two launches:
@@ -387,15 +397,18 @@ __global__ __launch_bounds__(256, 1) void deform_attn_bwd_kv_kernel(CrossBwdArgs
 //   (  2, 5, 768)   32.1 -> 22.0 (1.46x)            21.6 -> 16.2
 // No shape is slower.  The graphed B=2 step, switch off -> on, alternating: 33.64 -> 33.53 ms under bf16 matrix math, 40.38 -> 40.28 ms
 // under fp32 (eight such launches per step).  Not measured: the two kernels separately (no kernel trace was taken), and the fallback form.
+template <bool GROUPED>
 struct CrossBwd16Args {
     const float* q; const float* kv; const float* dout;
     float* dq; float* dkv; float* stats;
-    int C, nH, r, B1w;
+    int C, nH, r;
+    CvaPairing<GROUPED> pair;       // .nq = B1w
     float scale;
     int64_t units_q, units_kv;      // B1w nH 2 and B1w r nH
 };
 
-__global__ __launch_bounds__(256, 2) void deform_attn_bwd_q_bf16mm_kernel(CrossBwd16Args a) {
+template <bool GROUPED>
+__global__ __launch_bounds__(256, 2) void deform_attn_bwd_q_bf16mm_kernel(CrossBwd16Args<GROUPED> a) {
     __shared__ __attribute__((aligned(16))) uint32_t row_k[4][64];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -417,7 +430,7 @@ __global__ __launch_bounds__(256, 2) void deform_attn_bwd_q_bf16mm_kernel(CrossB
     f32x16 dq = {};
 
     for (int m = 0; m < a.r; ++m) {
-        const int64_t b2 = qw + (int64_t)m * a.B1w;                       // kv windows qw + m B1w pair with q window qw (deform:330)
+        const int64_t b2 = cva_kv_window(qw, m, a.pair);                  // kv windows qw + m B1w pair with q window qw (deform:330), per group
         const int64_t b1 = b2 / a.r;                                      // ... and take dO of output window b2 / r (deform:394-395)
         const char* kb = reinterpret_cast<const char*>(a.kv + b2 * WT * 2 * a.C + head * HD);
         const char* vb = kb + 4 * a.C;
@@ -478,7 +491,8 @@ __global__ __launch_bounds__(256, 2) void deform_attn_bwd_q_bf16mm_kernel(CrossB
     }
 }
 
-__global__ __launch_bounds__(256, 2) void deform_attn_bwd_kv_bf16mm_kernel(CrossBwd16Args a) {
+template <bool GROUPED>
+__global__ __launch_bounds__(256, 2) void deform_attn_bwd_kv_bf16mm_kernel(CrossBwd16Args<GROUPED> a) {
     __shared__ __attribute__((aligned(16))) uint32_t row_q[4][64];
     __shared__ __attribute__((aligned(16))) uint32_t row_k[4][64];
     __shared__ __attribute__((aligned(16))) float stat_s[4][192];         // the unit's {m, 1/l, D}: one coalesced read, then 16-byte LDS reads
@@ -489,7 +503,7 @@ __global__ __launch_bounds__(256, 2) void deform_attn_bwd_kv_bf16mm_kernel(Cross
     if (u >= a.units_kv) return;
     const int head = (int)(u % a.nH);
     const int64_t b2 = u / a.nH;
-    const int64_t qw = b2 % a.B1w, b1 = b2 / a.r;
+    const int64_t qw = cva_q_window(b2, a.pair), b1 = b2 / a.r;
     const uint32_t rq = 4u * a.C, rk = 8u * a.C;
     uint32_t* tq = row_q[wave];
     uint32_t* tk = row_k[wave];
@@ -668,26 +682,51 @@ extern "C" int64_t mumpy_deform_attention_bwd_workspace_bytes(int64_t B2w, int C
     return (B2w <= 0 || C <= 0) ? 0 : B2w * (C / HD) * 192 * (int64_t)sizeof(float);
 }
 
+// one validation + launch body for the frozen entry (groups = 1: the <GROUPED = false> kernels, no refusal added) and the grouped one
+template <bool GROUPED>
+static int cross_bwd_launch(const char* who, const float* q, const float* kv, const float* dout, float* dq_part, float* dkv,
+                            void* workspace, int64_t workspace_bytes, int64_t B1w, int r, int C, float scale, int groups,
+                            void* stream) {
+    MUMPY_REQUIRE(q && kv && dout && dq_part && dkv && workspace, MUMPY_ENULL, "%s: null pointer", who);
+    MUMPY_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(dout) && aligned16(dq_part) && aligned16(dkv) && aligned16(workspace),
+                  MUMPY_EALIGN, "%s: pointers must be 16-byte aligned", who);
+    MUMPY_REQUIRE(B1w > 0 && r >= 1 && C > 0 && C % HD == 0, MUMPY_EINVAL, "%s: bad shape", who);
+    const int64_t B2w = B1w * r;
+    MUMPY_REQUIRE(workspace_bytes >= mumpy_deform_attention_bwd_workspace_bytes(B2w, C), MUMPY_EINVAL, "%s: workspace too small", who);
+    CrossBwdArgs<GROUPED> a;
+    a.q = q; a.kv = kv; a.dout = dout; a.dq_part = dq_part; a.dkv = dkv; a.stats = static_cast<float*>(workspace);
+    a.C = C; a.nH = C / HD; a.r = r; a.scale = scale; a.units = B2w * a.nH;
+    const int64_t grid = (a.units + 3) / 4;
+    MUMPY_REQUIRE(grid < (1ll << 31) && B1w < (1ll << 31), MUMPY_ERANGE, "%s: too many windows", who);
+    if constexpr (GROUPED) {
+        const int bad = cva_grouping_windows(who, B2w, B1w, groups, &a.pair);
+        if (bad) return bad;
+    } else {
+        a.pair.nq = (int)B1w;
+    }
+    hipLaunchKernelGGL(deform_attn_bwd_q_kernel<GROUPED>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(deform_attn_bwd_kv_kernel<GROUPED>, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH(who);
+    return 0;
+}
+
 extern "C" int mumpy_deform_attention_bwd(const float* q, const float* kv, const float* dout, float* dq_part, float* dkv,
                                           void* workspace, int64_t workspace_bytes, int64_t B1w, int r, int C, float scale,
                                           void* stream) {
-    MUMPY_REQUIRE(q && kv && dout && dq_part && dkv && workspace, MUMPY_ENULL, "deform_attention_bwd: null pointer");
-    MUMPY_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(dout) && aligned16(dq_part) && aligned16(dkv) && aligned16(workspace),
-                  MUMPY_EALIGN, "deform_attention_bwd: pointers must be 16-byte aligned");
-    MUMPY_REQUIRE(B1w > 0 && r >= 1 && C > 0 && C % HD == 0, MUMPY_EINVAL, "deform_attention_bwd: bad shape");
-    const int64_t B2w = B1w * r;
-    MUMPY_REQUIRE(workspace_bytes >= mumpy_deform_attention_bwd_workspace_bytes(B2w, C), MUMPY_EINVAL,
-                  "deform_attention_bwd: workspace too small");
-    CrossBwdArgs a;
-    a.q = q; a.kv = kv; a.dout = dout; a.dq_part = dq_part; a.dkv = dkv; a.stats = static_cast<float*>(workspace);
-    a.C = C; a.nH = C / HD; a.r = r; a.B1w = (int)B1w; a.scale = scale; a.units = B2w * a.nH;
-    const int64_t grid = (a.units + 3) / 4;
-    MUMPY_REQUIRE(grid < (1ll << 31) && B1w < (1ll << 31), MUMPY_ERANGE, "deform_attention_bwd: too many windows");
-    hipLaunchKernelGGL(deform_attn_bwd_q_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
-    MUMPY_CHECK_LAUNCH("deform_attention_bwd(q)");
-    hipLaunchKernelGGL(deform_attn_bwd_kv_kernel, dim3((unsigned)grid), dim3(256), 0, as_stream(stream), a);
-    MUMPY_CHECK_LAUNCH("deform_attention_bwd(kv)");
-    return 0;
+    return cross_bwd_launch<false>("deform_attention_bwd", q, kv, dout, dq_part, dkv, workspace, workspace_bytes, B1w, r, C, scale, 1,
+                                   stream);
+}
+
+// include/mumpy_hip_ext9.h: groups == 1 is the frozen entry's launch, after the grouped entry's own refusals
+extern "C" int mumpy_deform_attention_grouped_bwd(const float* q, const float* kv, const float* dout, float* dq_part, float* dkv,
+                                                  void* workspace, int64_t workspace_bytes, int64_t B1w, int r, int C, float scale,
+                                                  int groups, void* stream) {
+    const char* who = "deform_attention_grouped_bwd";
+    MUMPY_REQUIRE(groups >= 1, MUMPY_EINVAL, "%s: groups=%d must be at least 1", who, groups);
+    if (groups == 1)
+        return cross_bwd_launch<false>(who, q, kv, dout, dq_part, dkv, workspace, workspace_bytes, B1w, r, C, scale, 1, stream);
+    return cross_bwd_launch<true>(who, q, kv, dout, dq_part, dkv, workspace, workspace_bytes, B1w, r, C, scale, groups, stream);
 }
 
 // ---- include/mumpy_hip_ext2.h ----
@@ -708,24 +747,49 @@ extern "C" int64_t mumpy_deform_attention_mm16_bwd_workspace_bytes(int64_t B1w, 
     return mm16_bwd_shape(B1w, r, C) ? 0 : B1w * r * (C / HD) * 192 * (int64_t)sizeof(float);
 }
 
+template <bool GROUPED>
+static int cross_bwd16_launch(const char* who, const float* q, const float* kv, const float* dout, float* dq, float* dkv,
+                              void* workspace, int64_t workspace_bytes, int64_t B1w, int r, int C, float scale, int groups,
+                              void* stream) {
+    MUMPY_REQUIRE(q && kv && dout && dq && dkv && workspace, MUMPY_ENULL, "%s: null pointer", who);
+    MUMPY_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(dout) && aligned16(dq) && aligned16(dkv) && aligned16(workspace),
+                  MUMPY_EALIGN, "%s: pointers must be 16-byte aligned", who);
+    const int bad = mm16_bwd_shape(B1w, r, C);
+    MUMPY_REQUIRE(bad != MUMPY_EINVAL, MUMPY_EINVAL, "%s: bad shape (B1w=%lld, r=%d, C=%d)", who, (long long)B1w, r, C);
+    MUMPY_REQUIRE(bad == 0, MUMPY_ERANGE, "%s: too many windows or C=%d too wide for 32-bit row offsets", who, C);
+    MUMPY_REQUIRE(workspace_bytes >= mumpy_deform_attention_mm16_bwd_workspace_bytes(B1w, r, C), MUMPY_EINVAL,
+                  "%s: workspace too small", who);
+    CrossBwd16Args<GROUPED> a;
+    a.q = q; a.kv = kv; a.dout = dout; a.dq = dq; a.dkv = dkv; a.stats = static_cast<float*>(workspace);
+    a.C = C; a.nH = C / HD; a.r = r; a.scale = scale;
+    a.units_q = B1w * a.nH * 2; a.units_kv = B1w * r * a.nH;
+    if constexpr (GROUPED) {
+        const int badg = cva_grouping_windows(who, B1w * r, B1w, groups, &a.pair);
+        if (badg) return badg;
+    } else {
+        a.pair.nq = (int)B1w;
+    }
+    hipLaunchKernelGGL(deform_attn_bwd_q_bf16mm_kernel<GROUPED>, dim3((unsigned)((a.units_q + 3) / 4)), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH(who);
+    hipLaunchKernelGGL(deform_attn_bwd_kv_bf16mm_kernel<GROUPED>, dim3((unsigned)((a.units_kv + 3) / 4)), dim3(256), 0, as_stream(stream), a);
+    MUMPY_CHECK_LAUNCH(who);
+    return 0;
+}
+
 extern "C" int mumpy_deform_attention_mm16_bwd(const float* q, const float* kv, const float* dout, float* dq, float* dkv,
                                                void* workspace, int64_t workspace_bytes, int64_t B1w, int r, int C, float scale,
                                                void* stream) {
-    MUMPY_REQUIRE(q && kv && dout && dq && dkv && workspace, MUMPY_ENULL, "deform_attention_mm16_bwd: null pointer");
-    MUMPY_REQUIRE(aligned16(q) && aligned16(kv) && aligned16(dout) && aligned16(dq) && aligned16(dkv) && aligned16(workspace),
-                  MUMPY_EALIGN, "deform_attention_mm16_bwd: pointers must be 16-byte aligned");
-    const int bad = mm16_bwd_shape(B1w, r, C);
-    MUMPY_REQUIRE(bad != MUMPY_EINVAL, MUMPY_EINVAL, "deform_attention_mm16_bwd: bad shape (B1w=%lld, r=%d, C=%d)", (long long)B1w, r, C);
-    MUMPY_REQUIRE(bad == 0, MUMPY_ERANGE, "deform_attention_mm16_bwd: too many windows or C=%d too wide for 32-bit row offsets", C);
-    MUMPY_REQUIRE(workspace_bytes >= mumpy_deform_attention_mm16_bwd_workspace_bytes(B1w, r, C), MUMPY_EINVAL,
-                  "deform_attention_mm16_bwd: workspace too small");
-    CrossBwd16Args a;
-    a.q = q; a.kv = kv; a.dout = dout; a.dq = dq; a.dkv = dkv; a.stats = static_cast<float*>(workspace);
-    a.C = C; a.nH = C / HD; a.r = r; a.B1w = (int)B1w; a.scale = scale;
-    a.units_q = B1w * a.nH * 2; a.units_kv = B1w * r * a.nH;
-    hipLaunchKernelGGL(deform_attn_bwd_q_bf16mm_kernel, dim3((unsigned)((a.units_q + 3) / 4)), dim3(256), 0, as_stream(stream), a);
-    MUMPY_CHECK_LAUNCH("deform_attention_mm16_bwd(q)");
-    hipLaunchKernelGGL(deform_attn_bwd_kv_bf16mm_kernel, dim3((unsigned)((a.units_kv + 3) / 4)), dim3(256), 0, as_stream(stream), a);
-    MUMPY_CHECK_LAUNCH("deform_attention_mm16_bwd(kv)");
-    return 0;
+    return cross_bwd16_launch<false>("deform_attention_mm16_bwd", q, kv, dout, dq, dkv, workspace, workspace_bytes, B1w, r, C, scale, 1,
+                                     stream);
+}
+
+// ---- include/mumpy_hip_ext9.h ----
+extern "C" int mumpy_deform_attention_mm16_grouped_bwd(const float* q, const float* kv, const float* dout, float* dq, float* dkv,
+                                                       void* workspace, int64_t workspace_bytes, int64_t B1w, int r, int C,
+                                                       float scale, int groups, void* stream) {
+    const char* who = "deform_attention_mm16_grouped_bwd";
+    MUMPY_REQUIRE(groups >= 1, MUMPY_EINVAL, "%s: groups=%d must be at least 1", who, groups);
+    if (groups == 1)
+        return cross_bwd16_launch<false>(who, q, kv, dout, dq, dkv, workspace, workspace_bytes, B1w, r, C, scale, 1, stream);
+    return cross_bwd16_launch<true>(who, q, kv, dout, dq, dkv, workspace, workspace_bytes, B1w, r, C, scale, groups, stream);
 }

@@ -5,7 +5,8 @@
 // 1x1 conv to 2 offsets (mumpy_linear_fwd) -> tanh * 2/7 + reference points.  This file holds what has no counterpart
 // elsewhere: the windowed depthwise convolution (forward + backward) and the backward of the bilinear window sampling.
 // Layout everywhere: token-major windows (N, 49, C'), pixel p = 7*y + x, channels contiguous.  Deterministic reductions.
-#include "common.h"
+#include "cva_pairing.h"
+#include "../../include/mumpy_hip_ext9.h"
 using namespace mumpy;
 
 namespace {
@@ -110,7 +111,8 @@ __global__ __launch_bounds__(1024) void window_partial_reduce_kernel(const float
 // ---------------------------------------------------------------------------------------------------------------
 // bilinear window sampling (grid_sample, align_corners=True, zeros padding; deform:353-356) backward.
 // forward (deform.hip): sampled[b2][p][g*Cg + c] = sum_{4 corners} wgt * x2[b2][corner][g*Cg + c], sample point
-// (fy, fx) = ((pos_y + 1) * 3, (pos_x + 1) * 3), pos = pos[b2 % nq][g][p].
+// (fy, fx) = ((pos_y + 1) * 3, (pos_x + 1) * 3), pos = pos[q(b2)][g][p], q(b2) = b2 % nq or, GROUPED, the same rule inside each
+// group (cva_pairing.h; <false> carries nq alone and is the kernel it was).
 //   dx2[b2][pix][ch]      = sum_p wgt(p, pix) dsampled[b2][p][ch]            (gather over the 49 points of the channel's group)
 //   dpos_part[b2][g][p]   = 3 * sum_{c in g} dsampled[b2][p][c] * d(sample)/d(fy, fx)     (summed over the r windows that share
 //                           a q window by the caller, in order)
@@ -127,10 +129,13 @@ __device__ __forceinline__ Corner corner_of(float py, float px) {
 // Round 3: the corner of every point is computed ONCE and each pixel gets the list of (point, weight) pairs that touch it, in point
 // order (the first version recomputed all 49 corners in every (pixel, channel) thread); the position gradient is a wave per point
 // with the channels across lanes and a fixed-tree wave sum (it was one THREAD per point walking Cg channels).  178 -> see DESIGN 7c.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950), <false> and <true> alike: 40 VGPRs / 46 SGPRs / 0 AGPRs, no static
+// LDS (the dynamic carve below: 33,124 B at C = 96 ... 120,932 B at C = 768), 8 waves per SIMD by registers, no scratch, no spill.
 constexpr int SB_LIST = WT;                       // worst case: every point lands on one pixel
+template <bool GROUPED>
 __global__ __launch_bounds__(256) void deform_sample_bwd_kernel(const float* __restrict__ x2, const float* __restrict__ pos,
                                                                 const float* __restrict__ ds, float* __restrict__ dx2,
-                                                                float* __restrict__ dpos_part, int C, int nq) {
+                                                                float* __restrict__ dpos_part, int C, CvaPairing<GROUPED> pair) {
     extern __shared__ float sm[];     // x2 slice (49*Cg) | dsampled slice (49*Cg) | pos (49*2) | corners (49*4) | counts (49) | lists
     const int b2 = blockIdx.x, g = blockIdx.y, Cg = C / 3;
     float* sx = sm;
@@ -161,7 +166,7 @@ __global__ __launch_bounds__(256) void deform_sample_bwd_kernel(const float* __r
             if (i < n4) { reinterpret_cast<f32x4*>(sx)[i] = va[u]; reinterpret_cast<f32x4*>(sd)[i] = vb[u]; }
         }
     }
-    const float* pq = pos + ((int64_t)(b2 % nq) * 3 + g) * WT * 2;
+    const float* pq = pos + ((int64_t)cva_q_window(b2, pair) * 3 + g) * WT * 2;
     if (threadIdx.x < WT) {
         const int p = threadIdx.x;
         const float py = pq[p * 2], px = pq[p * 2 + 1];
@@ -251,20 +256,45 @@ extern "C" int mumpy_dwconv5_window_bwd(const float* x, const float* w, const fl
     return 0;
 }
 
-extern "C" int mumpy_deform_sample_bwd(const float* x2, const float* pos, const float* dsampled, float* dx2, float* dpos_part,
-                                       int64_t B2, int C, int nq, void* stream) {
-    MUMPY_REQUIRE(x2 && pos && dsampled && dx2 && dpos_part, MUMPY_ENULL, "deform_sample_bwd: null pointer");
-    MUMPY_REQUIRE(B2 > 0 && B2 < (1ll << 31) && C > 0 && C % 12 == 0 && C <= 768 && nq > 0, MUMPY_EINVAL, "deform_sample_bwd: bad shape (C %% 12)");
-    MUMPY_REQUIRE(aligned16(x2) && aligned16(dsampled), MUMPY_EALIGN, "deform_sample_bwd: x2 and dsampled must be 16-byte aligned");
-    const size_t lds = (2 * WT * (C / 3) + WT * 2 + WT * 4 + WT + 2 * WT * WT) * sizeof(float);      // slices, pos, corners, counts, lists
-    MUMPY_REQUIRE(lds <= 160 * 1024, MUMPY_ERANGE, "deform_sample_bwd: window does not fit LDS");
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(deform_sample_bwd_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        MUMPY_REQUIRE(e == hipSuccess, (int)e, "deform_sample_bwd: cannot raise the dynamic LDS limit: %s", hipGetErrorString(e));
+// one validation + launch body for the frozen entry (groups = 1: the <GROUPED = false> kernel, no refusal added) and the grouped one
+template <bool GROUPED>
+static int sample_bwd_launch(const char* who, const float* x2, const float* pos, const float* dsampled, float* dx2, float* dpos_part,
+                             int64_t B2, int C, int nq, int groups, void* stream) {
+    MUMPY_REQUIRE(x2 && pos && dsampled && dx2 && dpos_part, MUMPY_ENULL, "%s: null pointer", who);
+    MUMPY_REQUIRE(B2 > 0 && B2 < (1ll << 31) && C > 0 && C % 12 == 0 && C <= 768 && nq > 0, MUMPY_EINVAL, "%s: bad shape (C %% 12)", who);
+    MUMPY_REQUIRE(aligned16(x2) && aligned16(dsampled), MUMPY_EALIGN, "%s: x2 and dsampled must be 16-byte aligned", who);
+    CvaPairing<GROUPED> pair;
+    if constexpr (GROUPED) {
+        const int bad = cva_grouping_windows(who, B2, nq, groups, &pair);
+        if (bad) return bad;
+    } else {
+        pair.nq = nq;
     }
-    hipLaunchKernelGGL(deform_sample_bwd_kernel, dim3((unsigned)B2, 3), dim3(256), lds, as_stream(stream), x2, pos, dsampled, dx2,
-                       dpos_part, C, nq);
-    MUMPY_CHECK_LAUNCH("deform_sample_bwd");
+    const size_t lds = (2 * WT * (C / 3) + WT * 2 + WT * 4 + WT + 2 * WT * WT) * sizeof(float);      // slices, pos, corners, counts, lists
+    MUMPY_REQUIRE(lds <= 160 * 1024, MUMPY_ERANGE, "%s: window does not fit LDS", who);
+    if (lds > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(deform_sample_bwd_kernel<GROUPED>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        MUMPY_REQUIRE(e == hipSuccess, (int)e, "%s: cannot raise the dynamic LDS limit: %s", who, hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(deform_sample_bwd_kernel<GROUPED>, dim3((unsigned)B2, 3), dim3(256), lds, as_stream(stream), x2, pos, dsampled,
+                       dx2, dpos_part, C, pair);
+    MUMPY_CHECK_LAUNCH(who);
     return 0;
 }
+
+extern "C" int mumpy_deform_sample_bwd(const float* x2, const float* pos, const float* dsampled, float* dx2, float* dpos_part,
+                                       int64_t B2, int C, int nq, void* stream) {
+    return sample_bwd_launch<false>("deform_sample_bwd", x2, pos, dsampled, dx2, dpos_part, B2, C, nq, 1, stream);
+}
+
+// include/mumpy_hip_ext9.h: groups == 1 is the frozen entry's launch, after the grouped entry's own refusals
+extern "C" int mumpy_deform_sample_grouped_bwd(const float* x2, const float* pos, const float* dsampled, float* dx2, float* dpos_part,
+                                               int64_t B2, int C, int nq, int groups, void* stream) {
+    const char* who = "deform_sample_grouped_bwd";
+    MUMPY_REQUIRE(groups >= 1, MUMPY_EINVAL, "%s: groups=%d must be at least 1", who, groups);
+    if (groups == 1) return sample_bwd_launch<false>(who, x2, pos, dsampled, dx2, dpos_part, B2, C, nq, 1, stream);
+    return sample_bwd_launch<true>(who, x2, pos, dsampled, dx2, dpos_part, B2, C, nq, groups, stream);
+}
+
+extern "C" int mumpy_ext9_version(void) { return MUMPY_EXT9_VERSION; }

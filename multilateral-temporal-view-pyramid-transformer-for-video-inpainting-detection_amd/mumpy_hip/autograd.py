@@ -617,11 +617,13 @@ class DWConv5Fn(torch.autograd.Function):
 
 
 def _refuse_clip_coupling(who):
-    """The backward kernels pair kv window b2 with q window b2 % nq only: under ops.set_clip_coupling("clip") the tape would
-    differentiate another function than the one the inference forward computes.  Refused before anything is launched."""
+    """The batch-coupled tape pairs kv window b2 with q window b2 % nq: under ops.set_clip_coupling("clip") it would differentiate
+    another function than the one the module's forward computes.  Refused before anything is launched; the tape never follows the
+    switch, per-clip pairing is asked for by argument."""
     if ops.clip_coupling() != "batch":
-        raise RuntimeError(f"{who}: the training tape has no per-clip pairing (ops.set_clip_coupling(\"clip\") is an inference "
-                           "setting; its backward kernels keep the batch-coupled rule) -- set_clip_coupling(\"batch\") to train")
+        raise RuntimeError(f"{who}: this call trains the batch-coupled pairing while ops.set_clip_coupling(\"clip\") is in force; "
+                           "the tape takes per-clip pairing by explicit argument -- encoder_train(enc, x, coupling=\"clip\") "
+                           "(groups= on the functions below it) -- or set_clip_coupling(\"batch\") to train the batch-coupled rule")
 
 
 class DeformSampleFn(torch.autograd.Function):
@@ -664,6 +666,45 @@ class DeformAttentionFn(torch.autograd.Function):
         return dq, dkv, None
 
 
+class DeformSampleGroupedFn(torch.autograd.Function):
+    """DeformSampleFn with the pairing rule applied inside each of `groups` equal slices of the windows (ops.cva_pairing; groups =
+    number of clips: per-clip pairing), forward and backward.  An explicit argument: it does not consult ops.clip_coupling()."""
+
+    @staticmethod
+    def forward(ctx, x2w, pos, groups):
+        ctx.save_for_backward(x2w, pos)
+        ctx.groups = groups
+        b2, _, c = x2w.shape
+        return ops.deform_sample(x2w.reshape(b2, 49, c), pos, b2, 7, 7, c, pos.shape[0], groups=groups)
+
+    @staticmethod
+    def backward(ctx, ds):
+        x2w, pos = ctx.saved_tensors
+        dx2, dpos = ops.deform_sample_bwd(x2w, pos, ds.contiguous(), groups=ctx.groups)
+        return dx2, dpos, None
+
+
+class DeformAttentionGroupedFn(torch.autograd.Function):
+    """DeformAttentionFn with the pairing rule applied inside each of `groups` equal slices of the windows, forward and backward; the
+    arithmetic is ops.cva_math() at the forward, carried to the backward, as there."""
+
+    @staticmethod
+    def forward(ctx, q, kv, scale, groups):
+        b1, _, c = q.shape
+        r = kv.shape[0] // b1
+        ctx.save_for_backward(q, kv)
+        ctx.cfg = (r, scale)
+        ctx.math = ops.cva_math()
+        ctx.groups = groups
+        return ops.deform_attention(q, kv, ops.pad_mask(q.device), b1, 7, 7, c, r, scale, math=ctx.math, groups=groups)
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, kv = ctx.saved_tensors
+        dq, dkv = ops.deform_attention_bwd(q, kv, dout.contiguous(), *ctx.cfg, math=ctx.math, groups=ctx.groups)
+        return dq, dkv, None, None
+
+
 _REF_POINTS = {}
 
 
@@ -675,11 +716,13 @@ def _ref_points(device):
     return _REF_POINTS[key]
 
 
-def swin_dattention_train(att, x1w, x2w):
+def swin_dattention_train(att, x1w, x2w, groups=1):
     """SwinDAttention.forward (deform:324-405) with a backward, window form: x1w (B1,49,C) q windows, x2w (B2,49,C) kv windows
     (already through `pre`), B2 = r*B1 -> y (B1,49,C) including the un-permuted (C,49) -> (49,C) reshape of deform:403.
     The offset network runs unfused (depthwise conv, LayerNorm, GELU, 1x1 conv as kernels; tanh / scaling / reference points
-    on the (B1,3,49,2) positions are a few KB of torch arithmetic)."""
+    on the (B1,3,49,2) positions are a few KB of torch arithmetic).  groups = 1: the reference's pairing over the whole batch
+    (DeformSampleFn / DeformAttentionFn, which refuse to run under ops.set_clip_coupling("clip")); groups = G > 1: the same rule
+    inside each of G equal slices of the windows (the Grouped functions; G = number of clips is per-clip pairing)."""
     b1, _, c = x1w.shape
     g, cg = att.n_groups, att.n_group_channels
     q = LinearFn.apply(x1w, att.proj_q.weight, att.proj_q.bias)          # (C,C,1,1) leaf: dW accumulates in its grad slot
@@ -690,11 +733,14 @@ def swin_dattention_train(att, x1w, x2w):
     wpw = torch.nn.functional.pad(off[3].weight.reshape(2, cg), (0, 0, 0, 30))            # N = 2 padded to the GEMM's multiple of 32
     o2 = LinearFn.apply(a.reshape(-1, cg), wpw, None)[:, :2].reshape(b1, g, 49, 2)
     pos = torch.tanh(o2) * (2.0 / 7.0) + _ref_points(x1w.device)                           # deform:339-349, (y, x)
-    samp = DeformSampleFn.apply(x2w.contiguous(), pos.contiguous())
+    if groups == 1:
+        samp = DeformSampleFn.apply(x2w.contiguous(), pos.contiguous())
+    else:
+        samp = DeformSampleGroupedFn.apply(x2w.contiguous(), pos.contiguous(), groups)
     wkv = torch.cat([att.proj_k.weight.reshape(c, c), att.proj_v.weight.reshape(c, c)], 0)
     bkv = torch.cat([att.proj_k.bias, att.proj_v.bias])
     kv = LinearFn.apply(samp, wkv, bkv)
-    o = DeformAttentionFn.apply(q, kv, att.scale)
+    o = DeformAttentionFn.apply(q, kv, att.scale) if groups == 1 else DeformAttentionGroupedFn.apply(q, kv, att.scale, groups)
     yt = LinearFn.apply(o, att.proj_out.weight, att.proj_out.bias)
     return yt.transpose(1, 2).reshape(b1, 49, c)
 
@@ -722,9 +768,10 @@ def _windows(x, hs, w):
     return x.view(b, hs // 7, 7, w // 7, 7, c).permute(0, 1, 3, 2, 4, 5).reshape(-1, 49, c)
 
 
-def cross_swin_block_train(blk, x1, x2):
+def cross_swin_block_train(blk, x1, x2, groups=1):
     """CrossSwinBlock.forward (mTVE:228-291) with a backward -> (x1_new, out); `out` is the W-MSA output before the residual,
-    which the next view's cross attention consumes (mTVE:275, 347-349).  x2 is ignored for the last view."""
+    which the next view's cross attention consumes (mTVE:275, 347-349).  x2 is ignored for the last view.  groups: the pairing of the
+    cross-view attention (swin_dattention_train); _windows() is clip-major, so groups = B makes group g clip g."""
     _, w = blk.input_resolution
     b, l1, c1 = x1.shape
     hs1 = l1 // w
@@ -741,20 +788,29 @@ def cross_swin_block_train(blk, x1, x2):
         # stochastic depth applies twice on this branch, as in the reference: CVAModule drops D per WINDOW (its input's
         # leading axis is B*nW, mTVE:138), the block drops the window-major y per clip (mTVE:286); rates dpr[2,4,22] of
         # stages 1-3 are non-zero (mTVE:553)
-        d = drop_path_train(blk.cva.drop_path, swin_dattention_train(blk.cva.crossattn, x1w, x2w))
+        d = drop_path_train(blk.cva.drop_path, swin_dattention_train(blk.cva.crossattn, x1w, x2w, groups))
         yw = AddFn.apply(x1w, d)                                          # CVAModule: x1 + drop_path(D) (mTVE:138)
         x1 = AddFn.apply(x1, drop_path_train(blk.drop_path, yw.reshape(b, l1, c1)))       # window-major y added to raster x1 (mTVE:285-286)
     x1, z = ResidualLayerNormFn.apply(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
     return _mlp_residual(x1, blk.drop_path, z, blk.mlp.fc1, blk.mlp.fc2), out
 
 
-def encoder_train(enc, x):
+def encoder_train(enc, x, coupling=None):
     """Encoder.forward (encoder.py:11-18; ThreeViewSwinTransformer.forward mTVE:732-746) with a backward:
     x (B,T,3,224,224) -> (final_x (B,2304,7,7), view_x[4][3] of (B,1,L,C), dct_x (B,9,224,224)).  The DCT features carry no
-    parameters and are computed without a tape."""
-    _refuse_clip_coupling("encoder_train")
+    parameters and are computed without a tape.
+    coupling: None or "batch" -- the reference's batch-wide pairing of the cross-view attention (refused while
+    ops.set_clip_coupling("clip") is in force: the tape does not follow the switch); "clip" -- per-clip pairing (groups = B at every
+    cross block, whatever the switch says): the function VideoPredictor(coupling="clip") and a batch-1 forward compute, whose loss
+    gradient is a sum over clips.  For a captured step:
+    GraphedTrainStep(lambda x: decoder_train(dec, *encoder_train(enc, x, coupling="clip"))[0], ...)."""
+    if coupling not in (None, "batch", "clip"):
+        raise ValueError(f"encoder_train: unknown coupling {coupling!r} (None, \"batch\" or \"clip\")")
+    if coupling != "clip":
+        _refuse_clip_coupling("encoder_train")
     m = enc.base
     b = x.shape[0]
+    groups = b if coupling == "clip" else 1
     with torch.no_grad():
         dct_x = m.faf.forward_frame(x, 1)
     tok = m.tokenize
@@ -765,8 +821,8 @@ def encoder_train(enc, x):
         for i, blk in enumerate(layer.blocks):
             if i == 0:                                                    # cross block: view 3 -> 2 -> 1 (mTVE:345-350)
                 xs[2], out2 = cross_swin_block_train(blk.block3, xs[2], None)
-                xs[1], out1 = cross_swin_block_train(blk.block2, xs[1], out2)
-                xs[0], _ = cross_swin_block_train(blk.block1, xs[0], out1)
+                xs[1], out1 = cross_swin_block_train(blk.block2, xs[1], out2, groups)
+                xs[0], _ = cross_swin_block_train(blk.block1, xs[0], out1, groups)
             else:
                 for v in range(3):
                     sub = getattr(blk, f"block{v + 1}")

@@ -6,7 +6,9 @@ The forward couples the samples of a micro-batch (SwinDAttention pairs windows a
 the partition unit is the MICRO-BATCH: rank r owns a contiguous slice of the global batch and its result equals the
 reference forward run on that slice alone — not a slice of a whole-batch forward.  Under
 ops.set_clip_coupling("clip") the inference forward pairs windows inside each clip, no clip's result depends on
-its batch, and the partition no longer matters: any split of the clips over ranks gives the same per-clip results."""
+its batch, and the partition no longer matters: any split of the clips over ranks gives the same per-clip results.
+The training tape gets the same property from autograd.encoder_train(enc, x, coupling="clip"): the loss gradient is a sum
+over clips, whatever the cut."""
 import os
 from typing import Tuple
 

@@ -183,6 +183,15 @@ EXT8_SIGNATURES = {
 }
 EXT8_VERSION = 1
 
+# ... and after that one; mirrors include/mumpy_hip_ext9.h one to one (tests/test_clip_coupling_train_host.py checks it): the frozen
+# backward siblings' arguments plus `int groups` before the stream
+EXT9_SIGNATURES = {
+    "mumpy_deform_sample_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
+    "mumpy_deform_attention_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_i, c_f],
+    "mumpy_deform_attention_mm16_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_i, c_f],
+}
+EXT9_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -257,8 +266,12 @@ def load_library():
     lib.mumpy_ext8_version.argtypes = []
     if lib.mumpy_ext8_version() != EXT8_VERSION:
         raise RuntimeError(f"{path}: eighth extension version {lib.mumpy_ext8_version()} != binding {EXT8_VERSION}; rebuild")
+    lib.mumpy_ext9_version.restype = c_i
+    lib.mumpy_ext9_version.argtypes = []
+    if lib.mumpy_ext9_version() != EXT9_VERSION:
+        raise RuntimeError(f"{path}: ninth extension version {lib.mumpy_ext9_version()} != binding {EXT9_VERSION}; rebuild")
     for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES,
-                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES, **EXT8_SIGNATURES}.items():
+                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES, **EXT8_SIGNATURES, **EXT9_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

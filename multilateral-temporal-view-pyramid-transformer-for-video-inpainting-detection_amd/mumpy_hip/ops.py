@@ -247,14 +247,16 @@ _CLIP_COUPLING = _clip_coupling_from_env()       # read once, at import
 
 
 def set_clip_coupling(mode: str) -> None:
-    """How the cross-view attention (SwinDAttention) pairs windows across the clips of a batch in the INFERENCE forward.
+    """How the cross-view attention (SwinDAttention) pairs windows across the clips of a batch in the module's forward.
     "batch" (default): the reference's rule -- kv window i attends with q window i mod B1 (`x1.repeat`, deform:330), B1 counting the
     q windows of EVERY clip, so a clip's result depends on the batch it travels in.  "clip": the same rule applied inside each clip
     (groups = batch size on the grouped kernels, include/mumpy_hip_ext8.h): every clip is computed as the reference computes a batch
     of one, whatever the batch size, the order of the clips or the padding of a tail; the launches are the full-batch ones.
     For a batch of one, and wherever r = 1, the two coincide.  The ops never follow the switch by themselves (their groups= defaults
-    to 1); the module does.  The training tape has no grouped backward: encoder_train and the deform autograd functions refuse
-    "clip".  The initial value is the environment variable MUMPY_CLIP_COUPLING, read when this module is imported.  Read at launch
+    to 1); the module does.  The training tape does NOT follow this switch: it trains the per-clip function by explicit argument,
+    autograd.encoder_train(enc, x, coupling="clip") (the grouped backward entries of include/mumpy_hip_ext9.h), and its default
+    call refuses to run while the switch says "clip" rather than differentiate another function than the one the forward computes.
+    The initial value is the environment variable MUMPY_CLIP_COUPLING, read when this module is imported.  Read at launch
     time: a GraphedForward keeps the pairing it was captured with (its coupling= argument pins it)."""
     global _CLIP_COUPLING
     if mode not in ("batch", "clip"):
@@ -301,6 +303,22 @@ def cva_pairing(nkv: int, nq: int, groups: int = 1):
     i = np.arange(nkv, dtype=np.int64)
     g = i // (r * nqg)
     return g * nqg + (i - g * r * nqg) % nqg, i // r
+
+
+def cva_pairing_members(nkv: int, nq: int, groups: int = 1):
+    """The inverse of cva_pairing, as the backward walks it: -> an (nq, r) numpy int64 array, row qw = the kv windows that attend with
+    q window qw in the order their contributions to it are summed (ascending).  With nqg = nq // groups, g = qw // nqg and
+    j = qw - g nqg, the m-th one is g r nqg + j + m nqg; groups = 1: qw + m nq."""
+    import numpy as np
+    nkv, nq, groups = int(nkv), int(nq), int(groups)
+    if nq < 1 or nkv < 1 or nkv % nq:
+        raise ValueError(f"cva_pairing_members: {nkv} kv windows are not a positive multiple of {nq} q windows")
+    if groups < 1 or nq % groups:
+        raise ValueError(f"cva_pairing_members: groups={groups} must be at least 1 and divide the {nq} q windows")
+    r, nqg = nkv // nq, nq // groups
+    qw = np.arange(nq, dtype=np.int64)[:, None]
+    g = qw // nqg
+    return g * (r * nqg) + (qw - g * nqg) + np.arange(r, dtype=np.int64)[None, :] * nqg
 
 
 def _mlp_fusion_from_env() -> bool:
@@ -932,7 +950,7 @@ def deform_attention(q, kv, padmask, b, h, w, c, r, scale, math="fp32", groups=1
     follow the switch (the module's inference forward, and the training tape's DeformAttentionFn, which carries the mode to its
     backward) pass it.  math="bf16": q / k / v rounded to bf16 in registers, both products on the bf16 MFMA, fp32 softmax and
     accumulation; its backward is deform_attention_bwd(..., math="bf16").  groups: the pairing rule (cva_pairing): 1 is the
-    reference's `i mod B1`, b is per-clip pairing; the backward has no grouped form."""
+    reference's `i mod B1`, b is per-clip pairing; the backward is deform_attention_bwd(..., groups=groups)."""
     b1w = b * (h // 7) * (w // 7)
     entry, extra = _grouped(_mm16("mumpy_deform_attention_fwd", math), groups, b, b1w, "deform_attention")
     q, kv = _rd(q, "q", b * h * w * c, "deform_attention"), _rd(kv, "kv", b1w * r * 49 * 2 * c, "deform_attention")
@@ -1721,8 +1739,18 @@ def dwconv5_window_bwd(x, w25, du):
     return dx, transpose(dw_t[:25].contiguous()), db
 
 
-def deform_sample_bwd(x2w, pos, dsampled):
-    """window form: x2w, dsampled (B2,49,C), pos (nq,3,49,2) -> (dx2 (B2,49,C), dpos (nq,3,49,2))."""
+def _grouped_bwd(entry, groups, nq, who):
+    """_grouped() for the backward ops, which see window counts and no batch: -> (C-ABI entry, trailing arguments before the stream)
+    for groups = 1 (the frozen entry, called exactly as before) or more (its _grouped form, include/mumpy_hip_ext9.h)."""
+    if not isinstance(groups, int) or isinstance(groups, bool) or groups < 1 or not isinstance(nq, int) or nq < 1 or nq % groups:
+        raise ValueError(f"{who}: groups={groups!r} must be a positive int that divides the {nq} q windows")
+    return (entry, ()) if groups == 1 else (entry.replace("_bwd", "_grouped_bwd"), (groups,))
+
+
+def deform_sample_bwd(x2w, pos, dsampled, groups=1):
+    """window form: x2w, dsampled (B2,49,C), pos (nq,3,49,2) -> (dx2 (B2,49,C), dpos (nq,3,49,2)).  groups: the pairing rule of the
+    forward this differentiates (cva_pairing): 1 is the reference's `i mod nq`."""
+    entry, extra = _grouped_bwd("mumpy_deform_sample_bwd", groups, pos.shape[0] if pos.dim() else 0, "deform_sample_bwd")
     x2w, pos = _chk(x2w, "x2"), _chk(pos, "pos")
     b2, p49, c = x2w.shape
     nq = pos.shape[0]
@@ -1731,18 +1759,25 @@ def deform_sample_bwd(x2w, pos, dsampled):
     dsampled = _rd(dsampled, "dsampled", x2w.numel(), "deform_sample_bwd")
     dx2 = torch.empty_like(x2w)
     part = torch.empty(b2, 3, 49, 2, device=x2w.device, dtype=torch.float32)
-    _call("mumpy_deform_sample_bwd", _p(x2w), _p(pos), _p(dsampled), _p(dx2), _p(part), b2, c, nq, _stream(), work=12.0 * x2w.numel())
-    # kv windows qw + m*nq share q window qw: a (r, nq, ...) view summed over r (a few KB: left to torch)
-    return dx2, part.view(b2 // nq, nq, 3, 49, 2).sum(0)
+    _call(entry, _p(x2w), _p(pos), _p(dsampled), _p(dx2), _p(part), b2, c, nq, *extra, _stream(), work=12.0 * x2w.numel())
+    if groups == 1:
+        # kv windows qw + m*nq share q window qw: a (r, nq, ...) view summed over r (a few KB: left to torch)
+        return dx2, part.view(b2 // nq, nq, 3, 49, 2).sum(0)
+    # per group the same: slots (g, m, j) share q window g*nqg + j (cva_pairing_members)
+    return dx2, part.view(groups, b2 // nq, nq // groups, 3, 49, 2).sum(1).reshape(nq, 3, 49, 2)
 
 
-def deform_attention_bwd(q, kv, dout, r, scale, math="fp32"):
+def deform_attention_bwd(q, kv, dout, r, scale, math="fp32", groups=1):
     """window form: q (B1,49,C), kv (B1*r,49,2C), dout (B1,49,C) -> (dq (B1,49,C), dkv (B1*r,49,2C)).  math: "fp32" (default; it does
     NOT follow set_cva_math) or "bf16", the backward of deform_attention(..., math="bf16") (mumpy_deform_attention_mm16_bwd): the
     operands rounded to bf16 in registers, every product on the bf16 MFMA, softmax / D / dS and accumulation in fp32, and dq summed
-    over its r kv windows on the device in a fixed order (no partial slices, no add launches)."""
+    over its r kv windows on the device in a fixed order (no partial slices, no add launches).  groups: the pairing rule of the
+    forward this differentiates (cva_pairing): 1 is the reference's `i mod B1`; G > 1 sums, per group, the same r contributions in
+    the same order as groups = 1 does on that group alone."""
     if math not in ("fp32", "bf16"):
         raise ValueError(f"unknown cross-view attention math mode {math!r}")
+    entry, extra = _grouped_bwd("mumpy_deform_attention_mm16_bwd" if math == "bf16" else "mumpy_deform_attention_bwd", groups,
+                                q.shape[0] if q.dim() else 0, "deform_attention_bwd")
     q = _chk(q, "q")
     b1, p49, c = q.shape
     b2 = b1 * r
@@ -1753,19 +1788,25 @@ def deform_attention_bwd(q, kv, dout, r, scale, math="fp32"):
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         wsb = _ws_bytes(("cvabwd16", b1, r, c), "mumpy_deform_attention_mm16_bwd_workspace_bytes", b1, r, c)
         ws = _ws(wsb, q.device)
-        _call("mumpy_deform_attention_mm16_bwd", _p(q), _p(kv), _p(dout), _p(dq), _p(dkv), _p(ws), wsb, b1, r, c, scale, _stream(),
+        _call(entry, _p(q), _p(kv), _p(dout), _p(dq), _p(dkv), _p(ws), wsb, b1, r, c, scale, *extra, _stream(),
               work=5 * 153664.0 * b2 * (c // 32))
         return dq, dkv
     part = torch.empty(b2, 49, c, device=q.device, dtype=torch.float32)
     dkv = torch.empty_like(kv)
     wsb = int(_lib().mumpy_deform_attention_bwd_workspace_bytes(b2, c))
     ws = _ws(wsb, q.device)
-    _call("mumpy_deform_attention_bwd", _p(q), _p(kv), _p(dout), _p(part), _p(dkv), _p(ws), wsb, b1, r, c, scale, _stream(),
+    _call(entry, _p(q), _p(kv), _p(dout), _p(part), _p(dkv), _p(ws), wsb, b1, r, c, scale, *extra, _stream(),
           work=5 * 153664.0 * b2 * (c // 32))
-    dq = part[:b1]
-    for m in range(1, r):                                                 # kv windows qw + m*B1 pair with q window qw: fixed order
-        dq = add(dq.contiguous(), part[m * b1:(m + 1) * b1].contiguous())
-    return dq.contiguous(), dkv
+    if groups == 1:
+        dq = part[:b1]
+        for m in range(1, r):                                             # kv windows qw + m*B1 pair with q window qw: fixed order
+            dq = add(dq.contiguous(), part[m * b1:(m + 1) * b1].contiguous())
+        return dq.contiguous(), dkv
+    slots = part.view(groups, r, b1 // groups, 49, c)                     # slots (g, m, j) pair with q window g*nqg + j: same order
+    dq = slots[:, 0]
+    for m in range(1, r):
+        dq = add(dq.contiguous(), slots[:, m].contiguous())
+    return dq.reshape(b1, 49, c).contiguous(), dkv
 
 
 def adamw_hyper(step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):

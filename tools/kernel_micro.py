@@ -21,6 +21,10 @@
                                                 its r - 1 add launches included) against the bf16-MFMA pair (math="bf16"), and the two
                                                 forwards, on the same input; each one's REPS calls captured in one graph, the four graphs
                                                 replayed alternately for ROUNDS rounds
+  | kernel_micro.py cva_bwd_grouped G B1w r C     window form: the cross-view backward ops with groups=G (the _grouped entries of
+                                                include/mumpy_hip_ext9.h; their dpos / dq reductions included) against the frozen ones --
+                                                deform_attention_bwd fp32 and bf16, deform_sample_bwd when C is a multiple of 96 -- on the
+                                                same input, same protocol; the frozen call is captured twice, so its own spread shows
   | kernel_micro.py mlp M C hidden                the launches of one MLP on the training tape, fused (ops.set_mlp_fusion) against the ones
                                                 they replace, MUMPY_MATH=fp32|bf16: fc1 as linear + gelu / linear_gelu_dual; fc2's
                                                 backward (dz, dW2, db2) as linear_bwd + gelu_bwd / the big-M pair (dX on the forward
@@ -155,6 +159,50 @@ if op == "cva_attn_bwd16":
     print(f"{op} {a}: " + ", ".join(f"{n} {med[n]:.2f} us [{min(t):.2f}..{max(t):.2f}]" for n, t in times.items())
           + f"; bwd fp32/bf16 = {med['bwd fp32'] / med['bwd bf16']:.2f}, fwd fp32/bf16 = {med['fwd fp32'] / med['fwd bf16']:.2f}"
           + f"  (median of {rounds} alternating replays of {reps} captured launches)")
+    sys.exit(0)
+if op == "cva_bwd_grouped":
+    groups, b1w, r, c = a
+    torch.manual_seed(0)
+    q = torch.randn(b1w, 49, c, device=dev); kv = torch.randn(b1w * r, 49, 2 * c, device=dev); dout = torch.randn(b1w, 49, c, device=dev)
+    x2 = torch.randn(b1w * r, 49, c, device=dev); pos = torch.rand(b1w, 3, 49, 2, device=dev) * 2.6 - 1.3
+    ds = torch.randn(b1w * r, 49, c, device=dev)
+    run = {}
+    for label, g in (("frozen", 1), ("frozen again", 1), ("grouped", groups)):       # frozen twice: the spread of one and the same call
+        kw = {} if g == 1 else {"groups": g}
+        for m in ("fp32", "bf16"):
+            run[f"attn {m} {label}"] = lambda m=m, kw=kw: ops.deform_attention_bwd(q, kv, dout, r, 32 ** -0.5, math=m, **kw)
+        if c % 96 == 0:
+            run[f"sample {label}"] = lambda kw=kw: ops.deform_sample_bwd(x2, pos, ds, **kw)
+    rounds = int(os.environ.get("ROUNDS", "12"))
+    graphs = {}
+    for name, fn in run.items():
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                fn()
+        side.synchronize()
+        graphs[name] = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graphs[name], stream=side):
+            for _ in range(reps):
+                fn()
+        graphs[name].replay()
+    torch.cuda.synchronize()
+    times = {name: [] for name in run}
+    for _ in range(rounds):
+        for name in run:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); graphs[name].replay(); e1.record(); torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1e3 / reps)
+    med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+    parts = []
+    for kind in sorted({n.rsplit(" frozen", 1)[0] for n in run if " frozen" in n}):
+        f1, f2, g = med[kind + " frozen"], med[kind + " frozen again"], med[kind + " grouped"]
+        lo = min(times[kind + " frozen"] + times[kind + " frozen again"]); hi = max(times[kind + " frozen"] + times[kind + " frozen again"])
+        parts.append(f"{kind}: frozen {f1:.2f} / {f2:.2f} us [{lo:.2f}..{hi:.2f}], grouped {g:.2f} us "
+                     f"[{min(times[kind + ' grouped']):.2f}..{max(times[kind + ' grouped']):.2f}], grouped/frozen = {g / f1:.3f}"
+                     + ("" if lo <= g <= hi else "  OUTSIDE the frozen spread"))
+    print(f"{op} groups={groups} {a[1:]}: " + "; ".join(parts) + f"  (medians of {rounds} alternating replays of {reps} captured calls)")
     sys.exit(0)
 if op == "mlp":
     m, c, hid = a
