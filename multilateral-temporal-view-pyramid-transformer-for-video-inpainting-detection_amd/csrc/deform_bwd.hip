@@ -89,18 +89,21 @@ __global__ __launch_bounds__(128) void dwconv5_bwd_kernel(const float* __restric
     pn[(int64_t)25 * C] = sb;
 }
 
-// fixed-order sum over windows: out[i] = sum_n part[n * width + i]   (16 lane groups, as partial_reduce in backward.hip)
+// fixed-order sum over windows: out[i] = sum_n part[n * width + i] for i < count   (16 lane groups, as partial_reduce in backward.hip).
+// count is the number of columns THIS launch owns, width the row stride of part: the db launch starts at column 25 C of a 26 C wide
+// row, so bounding i by width let its last block (C not a multiple of 64: Cg = 32 at C = 96) write up to 32 floats past db and read
+// as many past the end of the workspace.
 __global__ __launch_bounds__(1024) void window_partial_reduce_kernel(const float* __restrict__ part, float* __restrict__ out,
-                                                                     int64_t nparts, int64_t width) {
+                                                                     int64_t nparts, int64_t width, int64_t count) {
     __shared__ float red[16][64];
     const int col = threadIdx.x & 63, grp = threadIdx.x >> 6;
     const int64_t i = (int64_t)blockIdx.x * 64 + col;
     float s = 0.f;
-    if (i < width && grp < nparts)
+    if (i < count && grp < nparts)
         s = ordered_sum(part[grp * width + i], part + (grp + 16) * width + i, 16 * width, (int)((nparts - grp + 15) / 16) - 1);
     red[grp][col] = s;
     __syncthreads();
-    if (grp == 0 && i < width) {
+    if (grp == 0 && i < count) {
         float t = 0.f;
 #pragma unroll
         for (int g = 0; g < 16; ++g) t += red[g][col];
@@ -248,10 +251,10 @@ extern "C" int mumpy_dwconv5_window_bwd(const float* x, const float* w, const fl
     // part rows are [tap 0..24][C] then [bias][C]; dw is (C, 25) like the module's (C,1,5,5) weight: reduce to a (26, C) image,
     // the caller transposes the first 25 rows (mumpy_hip/autograd.py)
     hipLaunchKernelGGL(window_partial_reduce_kernel, dim3((unsigned)((25 * C + 63) / 64)), dim3(1024), 0, as_stream(stream), part, dw, N,
-                       (int64_t)26 * C);
+                       (int64_t)26 * C, (int64_t)25 * C);
     MUMPY_CHECK_LAUNCH("dwconv5_bwd(reduce dw)");
     hipLaunchKernelGGL(window_partial_reduce_kernel, dim3((unsigned)((C + 63) / 64)), dim3(1024), 0, as_stream(stream), part + 25 * C, db,
-                       N, (int64_t)26 * C);
+                       N, (int64_t)26 * C, (int64_t)C);
     MUMPY_CHECK_LAUNCH("dwconv5_bwd(reduce db)");
     return 0;
 }

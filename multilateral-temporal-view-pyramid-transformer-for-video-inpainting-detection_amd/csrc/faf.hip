@@ -15,6 +15,7 @@
 // v_mfma_f32_32x32x2_f32: exact fp32.  Replaces the round-1 row-block kernel (one 4-byte LDS read + one 4-byte global
 // read per MFMA: 135 + 169 us per forward at B = 8) -- measured: see DESIGN.md.
 #include "common.h"
+#include "../../include/mumpy_hip_ext10.h"
 using namespace mumpy;
 
 namespace {
@@ -156,7 +157,132 @@ __global__ __launch_bounds__(64 * NW) void faf_colblock_kernel(FafArgs a) {
     }
 }
 
+// The backward's first half (include/mumpy_hip_ext10.h): the summed, masked spectrum
+//     S'[:, cb] = sum_band M_band o ( D . (g_band . D[cb, :]^T) )            g_band = dout[b, band*3 + rgb]
+// of one plane (b, rgb): the forward's column-block double product with the mask on the OUTPUT, once per band, the three results
+// summed in registers in the order low, mid, high and stored once (every element of S' is written, the 18,759 coefficients of no band
+// as zeros).  Band sparsity: a band whose limit lies left of the column block is skipped whole, and of the others only the row tiles
+// of the second product that meet [lo, hi]; the first product is dense (g is).  The second half, D^T S' D, is the unmasked
+// faf_colblock_kernel -- one inverse transform per (b, rgb), not one per band.
+// The fragment helpers restate the lambdas of faf_colblock_kernel, which stays as measured.
+struct FafFrag {
+    f32x4 bf[NCH][4];
+    __device__ __forceinline__ void load_b(const float* Ls, int c, int h) {
+#pragma unroll
+        for (int kc = 0; kc < NCH; ++kc)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bf[kc][q] = *reinterpret_cast<const f32x4*>(&Ls[c * LDT + 32 * kc + 16 * h + 4 * q]);
+    }
+    // one 224-deep row-tile product: acc = A[rows of the lane] . B, A fragments one chunk ahead of the MFMAs
+    __device__ __forceinline__ void row_tile(const float* arow, f32x16& acc) const {
+        f32x4 av[2][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) av[0][q] = *reinterpret_cast<const f32x4*>(arow + 4 * q);
+#pragma unroll
+        for (int kc = 0; kc < NCH; ++kc) {
+            if (kc + 1 < NCH) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) av[(kc + 1) & 1][q] = *reinterpret_cast<const f32x4*>(arow + 32 * (kc + 1) + 4 * q);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[kc & 1][q][e], bf[kc][q][e], acc, 0, 0, 0);
+        }
+    }
+};
+
+constexpr int NS = (NCH + NW - 1) / NW;      // row tiles per wave
+
+__global__ __launch_bounds__(64 * NW) void faf_bwd_spectrum_kernel(const float* __restrict__ D, const float* __restrict__ dout,
+                                                                   float* __restrict__ S, int lo_hi, int mid_lo, int mid_hi) {
+    __shared__ __attribute__((aligned(16))) float Rs[32 * LDT];
+    __shared__ __attribute__((aligned(16))) float Wt[32 * LDT];
+    const int cb = blockIdx.x, plane = blockIdx.y;
+    const int b = plane / 3, ch = plane - 3 * b;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    constexpr int64_t P = (int64_t)N * N;
+
+    for (int idx = tid; idx < 32 * (N / 4); idx += 64 * NW) {                // D[cb rows] -> LDS, 16-B coalesced
+        const int r = idx / (N / 4), q = idx - r * (N / 4);
+        *reinterpret_cast<f32x4*>(&Rs[r * LDT + 4 * q]) = *reinterpret_cast<const f32x4*>(D + (int64_t)(cb * 32 + r) * N + 4 * q);
+    }
+    __syncthreads();
+
+    f32x16 tot[NS];
+#pragma unroll
+    for (int s = 0; s < NS; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tot[s][r] = 0.f;
+    FafFrag f;
+    for (int band = 0; band < 3; ++band) {
+        const int lo = band == 0 ? 0 : (band == 1 ? mid_lo : N);
+        const int hi = band == 0 ? lo_hi : (band == 1 ? mid_hi : 2 * N);
+        if (32 * cb > hi || 32 * cb + 31 + N - 1 < lo) continue;             // (block-uniform) no coefficient of the band in this column block
+        const float* In = dout + ((int64_t)b * 9 + band * 3 + ch) * P;
+        // phase 1: W[224 x 32] = g . D[cb]^T, to LDS transposed (all of Wt[c][0 .. 223] is rewritten)
+        f.load_b(Rs, c, h);
+        for (int t = wave; t < NCH; t += NW) {
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            f.row_tile(In + (int64_t)(32 * t + c) * N + 16 * h, acc);
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+                *reinterpret_cast<f32x4*>(&Wt[c * LDT + 32 * t + 8 * g + 4 * h]) = f32x4{acc[4 * g], acc[4 * g + 1], acc[4 * g + 2], acc[4 * g + 3]};
+        }
+        __syncthreads();
+        f.load_b(Wt, c, h);
+        __syncthreads();                                                     // Wt is in registers: the next band may overwrite it
+        // phase 2: the row tiles of D . W that meet the band, masked on i + j and added to the running sum
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int t = wave + s * NW;
+            if (t >= NCH || 32 * (t + cb) > hi || 32 * (t + cb) + 62 < lo) continue;
+            f32x16 acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+            f.row_tile(D + (int64_t)(32 * t + c) * N + 16 * h, acc);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int sidx = 32 * t + (r & 3) + 8 * (r >> 2) + 4 * h + 32 * cb + c;
+                tot[s][r] += (sidx >= lo && sidx <= hi) ? acc[r] : 0.f;
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        const int t = wave + s * NW;
+        if (t >= NCH) continue;
+        float* o = S + plane * P + (int64_t)(32 * t + 4 * h) * N + 32 * cb + c;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[((r & 3) + 8 * (r >> 2)) * N] = tot[s][r];
+    }
+}
+
 }  // namespace
+
+extern "C" int mumpy_faf_bwd(const float* dout, const float* D, const float* Dt, float* scratch, float* dxf, int B, int lo_hi,
+                             int mid_lo, int mid_hi, void* stream) {
+    MUMPY_REQUIRE(dout && D && Dt && scratch && dxf, MUMPY_ENULL, "faf_bwd: null pointer");
+    MUMPY_REQUIRE(aligned16(dout) && aligned16(D) && aligned16(Dt) && aligned16(scratch) && aligned16(dxf), MUMPY_EALIGN,
+                  "faf_bwd: pointers must be 16-byte aligned");
+    MUMPY_REQUIRE(B > 0, MUMPY_EINVAL, "faf_bwd: B=%d must be positive", B);
+    MUMPY_REQUIRE(lo_hi >= 0 && mid_lo >= 0 && mid_hi >= mid_lo && mid_hi < 2 * N, MUMPY_EINVAL, "faf_bwd: bad band limits");
+    const int64_t P = (int64_t)N * N;
+    hipLaunchKernelGGL(faf_bwd_spectrum_kernel, dim3(NCH, B * 3, 1), dim3(64 * NW), 0, as_stream(stream), D, dout, scratch, lo_hi,
+                       mid_lo, mid_hi);
+    MUMPY_CHECK_LAUNCH("faf_bwd(spectrum)");
+    FafArgs g;                                   // dxf = D^T S' D: the column-block product with L = R = D^T, no mask
+    g.L = Dt; g.R = Dt; g.In = scratch; g.Out = dxf;
+    g.i_batch_stride = 3 * P; g.i_plane_stride = P;
+    g.o_batch_stride = 3 * P; g.o_plane_stride = P; g.o_band_stride = 0;
+    g.masked = 0; g.lo_hi = lo_hi; g.mid_lo = mid_lo; g.mid_hi = mid_hi;
+    hipLaunchKernelGGL(faf_colblock_kernel, dim3(NCH, B * 3, 1), dim3(64 * NW), 0, as_stream(stream), g);
+    MUMPY_CHECK_LAUNCH("faf_bwd(inverse)");
+    return 0;
+}
 
 extern "C" int mumpy_faf_fwd(const float* x, const float* D, const float* Dt, float* scratch, float* out, int B, int T,
                              int frame, int lo_hi, int mid_lo, int mid_hi, void* stream) {

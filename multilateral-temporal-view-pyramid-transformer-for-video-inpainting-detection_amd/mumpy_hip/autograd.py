@@ -749,17 +749,58 @@ def swin_dattention_train(att, x1w, x2w, groups=1):
 def _tubelet_tokens(x, proj, norm):
     """One view of CrossThreeViewTokenize (mTVE:605-618): Conv3d(3 -> C, k = s = (t,4,4)) as a per-tubelet Linear + LayerNorm.
     x (B,T,3,H,W) -> (B, (T//t)*(H/4)*(W/4), C), frames stacked on the token axis."""
-    w = proj.weight                                                       # (C, 3, t, 4, 4)
-    cout, ch, t, p, _ = w.shape
-    b, T, _, hh, ww = x.shape
+    _, _, t, p, _ = proj.weight.shape                                     # (C, 3, t, 4, 4)
+    return _tokens_of_columns(_tubelet_columns(x, t, p), x.shape[0], proj, norm)
+
+
+def _tubelet_columns(x, t, p=4):
+    """The padded column matrix of one view: x (B,T,3,H,W) -> (B * tt * (H/p) * (W/p), K padded to a multiple of 32), one row per
+    tubelet patch, columns ordered (ch, t, py, px) like the Conv3d weight."""
+    b, T, ch, hh, ww = x.shape
     tt = (T - t) // t + 1
     cols = x[:, :tt * t].permute(0, 2, 1, 3, 4).reshape(b, ch, tt, t, hh // p, p, ww // p, p).permute(0, 2, 4, 6, 1, 3, 5, 7)
     cols = cols.reshape(b * tt * (hh // p) * (ww // p), ch * t * p * p)
-    k = cols.shape[1]
-    pad = (-k) % 32
-    y = LinearFn.apply(torch.nn.functional.pad(cols, (0, pad)).contiguous(), torch.nn.functional.pad(w.reshape(cout, k), (0, pad)),
-                       proj.bias)
+    return torch.nn.functional.pad(cols, (0, (-cols.shape[1]) % 32)).contiguous()
+
+
+def _tokens_of_columns(cols, b, proj, norm):
+    """The per-tubelet Linear (the Conv3d weight as an (C, K) matrix, padded like the columns) + LayerNorm of one view."""
+    w = proj.weight
+    cout = w.shape[0]
+    k = w.numel() // cout
+    y = LinearFn.apply(cols, torch.nn.functional.pad(w.reshape(cout, k), (0, cols.shape[1] - k)), proj.bias)
     return LayerNormFn.apply(y, norm.weight, norm.bias, norm.eps).reshape(b, -1, cout)
+
+
+class ClipInputFn(torch.autograd.Function):
+    """The two places where the clip enters the three-view model, as one node: x (B,T,3,224,224) -> the three views' padded column
+    matrices (_tubelet_columns) and dct_x = FAF(frame 1).  The forward is the expression encoder_train evaluates without the node
+    (the same torch permutes and pad, the same faf launch), so logits and parameter gradients do not depend on it.  The backward is
+    ops.faf_bwd (two launches; skipped when nothing flows into dct_x) and ops.tokenize_dx (one launch that writes every element of
+    dx): no ATen kernel, deterministic."""
+
+    @staticmethod
+    def forward(ctx, x, faf, tubelets):
+        ctx.faf, ctx.tubelets, ctx.xshape = faf, tuple(tubelets), tuple(x.shape)
+        ctx.set_materialize_grads(False)
+        cols = tuple(_tubelet_columns(x, t) for t in tubelets)
+        return (*cols, faf.forward_frame(x, 1))
+
+    @staticmethod
+    def backward(ctx, dc0, dc1, dc2, ddct):
+        b, t, _, h, w = ctx.xshape
+        faf = ctx.faf
+        dxf = None
+        if ddct is not None:
+            d, dt = faf._mats(ddct.device)
+            dxf = ops.faf_bwd(ddct, d, dt, faf.lo_hi, faf.mid_lo, faf.mid_hi)
+        dcols = []
+        for dc, tv in zip((dc0, dc1, dc2), ctx.tubelets):
+            if dc is None:                                                # (a view nothing was computed from: never in the three-view model)
+                rows = b * ((t - tv) // tv + 1) * (h // 4) * (w // 4)
+                dc = torch.zeros(rows, 48 * tv + (-48 * tv) % 32, device=(ddct if ddct is not None else dc0).device, dtype=torch.float32)
+            dcols.append(dc)
+        return ops.tokenize_dx(dcols, ctx.tubelets, b, t, h, w, dxf=dxf, frame=1), None, None
 
 
 def _windows(x, hs, w):
@@ -795,10 +836,13 @@ def cross_swin_block_train(blk, x1, x2, groups=1):
     return _mlp_residual(x1, blk.drop_path, z, blk.mlp.fc1, blk.mlp.fc2), out
 
 
-def encoder_train(enc, x, coupling=None):
+def encoder_train(enc, x, coupling=None, input_grad=False):
     """Encoder.forward (encoder.py:11-18; ThreeViewSwinTransformer.forward mTVE:732-746) with a backward:
     x (B,T,3,224,224) -> (final_x (B,2304,7,7), view_x[4][3] of (B,1,L,C), dct_x (B,9,224,224)).  The DCT features carry no
-    parameters and are computed without a tape.
+    parameters and are computed without a tape, unless
+    input_grad=True: the clip enters through ClipInputFn, whose backward returns the complete dL/dx (tokenizer and FAF branch) in
+    three launches; x must be float32 and require grad.  Logits and parameter gradients are the same bits either way.  A clip that
+    requires grad is refused without it (the FAF branch would be missing from x.grad).
     coupling: None or "batch" -- the reference's batch-wide pairing of the cross-view attention (refused while
     ops.set_clip_coupling("clip") is in force: the tape does not follow the switch); "clip" -- per-clip pairing (groups = B at every
     cross block, whatever the switch says): the function VideoPredictor(coupling="clip") and a batch-1 forward compute, whose loss
@@ -808,13 +852,25 @@ def encoder_train(enc, x, coupling=None):
         raise ValueError(f"encoder_train: unknown coupling {coupling!r} (None, \"batch\" or \"clip\")")
     if coupling != "clip":
         _refuse_clip_coupling("encoder_train")
+    if input_grad:
+        if not (torch.is_tensor(x) and x.dtype == torch.float32 and x.requires_grad):
+            raise RuntimeError("encoder_train: input_grad=True needs a float32 clip x with x.requires_grad_() set")
+    elif torch.is_tensor(x) and x.requires_grad:
+        raise RuntimeError("encoder_train: x requires grad, but this tape does not differentiate the FAF branch with respect to the "
+                           "clip: x.grad would silently miss it.  Pass input_grad=True (or detach x)")
     m = enc.base
     b = x.shape[0]
     groups = b if coupling == "clip" else 1
-    with torch.no_grad():
-        dct_x = m.faf.forward_frame(x, 1)
     tok = m.tokenize
-    xs = [_tubelet_tokens(x, getattr(tok, f"project{v + 1}"), getattr(tok, f"norm{v + 1}")) for v in range(3)]
+    projs = [getattr(tok, f"project{v + 1}") for v in range(3)]
+    norms = [getattr(tok, f"norm{v + 1}") for v in range(3)]
+    if input_grad:
+        *cols, dct_x = ClipInputFn.apply(x, m.faf, [p.weight.shape[2] for p in projs])
+        xs = [_tokens_of_columns(c, b, p, n) for c, p, n in zip(cols, projs, norms)]
+    else:
+        with torch.no_grad():
+            dct_x = m.faf.forward_frame(x, 1)
+        xs = [_tubelet_tokens(x, p, n) for p, n in zip(projs, norms)]
     tdims = m.input_token_temporal_dims
     view_x = []
     for layer in m.layers.layers:

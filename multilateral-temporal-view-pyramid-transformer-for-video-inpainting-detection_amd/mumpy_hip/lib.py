@@ -192,6 +192,15 @@ EXT9_SIGNATURES = {
 }
 EXT9_VERSION = 1
 
+# ... and after that one; mirrors include/mumpy_hip_ext10.h one to one (tests/test_input_grad_host.py checks it).  eps3 / lo3 / hi3: HOST
+EXT10_SIGNATURES = {
+    "mumpy_faf_bwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+    "mumpy_tokenize_dx": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+    "mumpy_pgd_step": [c_f, c_f, c_f, c_l, c_l, c_fl, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                       ctypes.POINTER(ctypes.c_float), c_f],
+}
+EXT10_VERSION = 1
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -270,8 +279,13 @@ def load_library():
     lib.mumpy_ext9_version.argtypes = []
     if lib.mumpy_ext9_version() != EXT9_VERSION:
         raise RuntimeError(f"{path}: ninth extension version {lib.mumpy_ext9_version()} != binding {EXT9_VERSION}; rebuild")
+    lib.mumpy_ext10_version.restype = c_i
+    lib.mumpy_ext10_version.argtypes = []
+    if lib.mumpy_ext10_version() != EXT10_VERSION:
+        raise RuntimeError(f"{path}: tenth extension version {lib.mumpy_ext10_version()} != binding {EXT10_VERSION}; rebuild")
     for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES,
-                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES, **EXT8_SIGNATURES, **EXT9_SIGNATURES}.items():
+                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES, **EXT8_SIGNATURES, **EXT9_SIGNATURES,
+                       **EXT10_SIGNATURES}.items():
         fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
         fn.argtypes = args
         fn.restype = c_l if name.endswith("_bytes") else c_i

@@ -981,6 +981,77 @@ def faf(x, d, dt, frame, lo_hi, mid_lo, mid_hi):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- input-clip gradients (mumpy_hip_ext10.h)
+def faf_bwd(dout, d, dt, lo_hi, mid_lo, mid_hi, out=None):
+    """The gradient of `faf` with respect to the frame it read: dout (B,9,224,224) -> dxf (B,3,224,224)
+    = D^T (sum_band M_band o (D dout[band,rgb] D^T)) D.  Two launches, deterministic."""
+    if dout.dim() != 4 or tuple(dout.shape[1:]) != (9, 224, 224) or dout.shape[0] < 1:
+        raise RuntimeError(f"faf_bwd: expects dout (B,9,224,224), got {tuple(dout.shape)}")
+    b = dout.shape[0]
+    dout = _rd(dout, "dout", b * 9 * 224 * 224, "faf_bwd")
+    d, dt = _rd(d, "D", 224 * 224, "faf_bwd"), _rd(dt, "Dt", 224 * 224, "faf_bwd")
+    scratch = torch.empty(b, 3, 224, 224, device=dout.device, dtype=torch.float32)
+    out = torch.empty(b, 3, 224, 224, device=dout.device, dtype=torch.float32) if out is None else \
+        _wr(out, "out", b * 3 * 224 * 224, "faf_bwd")
+    _call("mumpy_faf_bwd", _p(dout), _p(d), _p(dt), _p(scratch), _p(out), b, int(lo_hi), int(mid_lo), int(mid_hi), _stream(),
+          work=2.0 * 224 ** 3 * 2 * 4 * 3 * b)
+    return out
+
+
+def tokenize_dx(dcols, tubelets, b, t, h, w, dxf=None, frame=1, out=None):
+    """One launch: the three views' column gradients (+ the FAF gradient of frame `frame`) -> dx (B,T,3,H,W).  dcols[v]: a 2-D
+    (B * tt_v * (H/4) * (W/4), ld_v) matrix with columns (ch, t, py, px), tt_v = (T - t_v) // t_v + 1, ld_v >= 48 t_v (the padded K; the
+    pad columns are not read).  Every element of dx is written; frames a view's tubelets do not reach get nothing from it."""
+    if len(dcols) != 3 or len(tubelets) != 3:
+        raise RuntimeError("tokenize_dx: needs the column gradients and tubelet lengths of three views")
+    b, t, h, w, frame = int(b), int(t), int(h), int(w), int(frame)
+    if b < 1 or t < 1 or h < 4 or w < 4 or h % 4 or w % 4:
+        raise RuntimeError(f"tokenize_dx: bad sizes B={b} T={t}, {h}x{w} (H and W must be positive multiples of 4)")
+    cols, lds = [], []
+    for v, (c, tv) in enumerate(zip(dcols, tubelets)):
+        tv = int(tv)
+        if not 1 <= tv <= t:
+            raise RuntimeError(f"tokenize_dx: tubelet {tv} of view {v} outside [1, T={t}]")
+        rows = b * ((t - tv) // tv + 1) * (h // 4) * (w // 4)
+        if c.dim() != 2 or c.shape[0] != rows or c.shape[1] < 48 * tv or c.shape[1] % 4:
+            raise RuntimeError(f"tokenize_dx: view {v} needs dcols of shape ({rows}, ld >= {48 * tv}, ld % 4 == 0), got {tuple(c.shape)}")
+        cols.append(_rd(c, f"dcols[{v}]", rows * c.shape[1], "tokenize_dx"))
+        lds.append(int(c.shape[1]))
+    if dxf is not None:
+        if not 0 <= frame < t:
+            raise RuntimeError(f"tokenize_dx: frame {frame} outside clip of {t}")
+        dxf = _rd(dxf, "dxf", b * 3 * h * w, "tokenize_dx")
+    out = torch.empty(b, t, 3, h, w, device=cols[0].device, dtype=torch.float32) if out is None else \
+        _wr(out, "out", b * t * 3 * h * w, "tokenize_dx")
+    _call("mumpy_tokenize_dx", _p(cols[0]), _p(cols[1]), _p(cols[2]), _p(dxf), _p(out), b, t, h, w, int(tubelets[0]), int(tubelets[1]),
+          int(tubelets[2]), lds[0], lds[1], lds[2], frame, _stream(), work=4.0 * out.numel() * 4)
+    return out
+
+
+def pgd_step(x_adv, g, x0, alpha, eps3, lo3, hi3):
+    """One projected signed-gradient step IN PLACE on x_adv (..., 3, H, W):
+    x_adv <- clamp(clamp(x_adv + alpha * sgn(g), x0 - eps_c, x0 + eps_c), lo_c, hi_c), per channel c, in fp32 in this order.
+    sgn(0) = 0, a NaN gradient counts as 0, +-inf as +-1; alpha may be negative.  eps3 / lo3 / hi3: three host floats each
+    (mumpy_hip.inputgrad.pgd_bounds).  Returns x_adv."""
+    import ctypes
+    import math
+    if x_adv.dim() < 3 or x_adv.shape[-3] != 3:
+        raise RuntimeError(f"pgd_step: expects clips (..., 3, H, W), got {tuple(x_adv.shape)}")
+    n, hw = x_adv.numel(), x_adv.shape[-1] * x_adv.shape[-2]
+    if hw < 1:
+        raise RuntimeError(f"pgd_step: empty planes in {tuple(x_adv.shape)}")
+    x_adv = _wr(x_adv, "x_adv", n, "pgd_step")
+    g, x0 = _rd(g, "g", n, "pgd_step"), _rd(x0, "x0", n, "pgd_step")
+    eps3, lo3, hi3 = [tuple(float(v) for v in a) for a in (eps3, lo3, hi3)]
+    if len(eps3) != 3 or len(lo3) != 3 or len(hi3) != 3 or not all(e >= 0.0 for e in eps3) or not all(l <= h for l, h in zip(lo3, hi3)):
+        raise RuntimeError(f"pgd_step: needs three eps >= 0 and three lo <= hi, got {eps3}, {lo3}, {hi3}")
+    if not math.isfinite(alpha):
+        raise RuntimeError(f"pgd_step: alpha must be finite, got {alpha}")
+    f3 = ctypes.c_float * 3
+    _call("mumpy_pgd_step", _p(x_adv), _p(g), _p(x0), n, hw, float(alpha), f3(*eps3), f3(*lo3), f3(*hi3), _stream(), work=16.0 * n)
+    return x_adv
+
+
 def patch_embed(x, wt, bias, gamma, beta, t, eps=1e-5):
     """x (B,T,3,H,W), wt (48t, C) -> (B, t_out*H/4*W/4, C)."""
     x = _chk(x, "x")
