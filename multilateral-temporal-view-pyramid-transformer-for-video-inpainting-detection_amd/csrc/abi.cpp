@@ -1,8 +1,18 @@
-// abi.cpp — version / error plumbing of the C ABI (include/mumpy_hip.h).
+// abi.cpp — version / error plumbing of the C ABI (include/mumpy_hip.h and every mumpy_hip_ext*.h: each header's version function).
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 #include "common.h"
+#include "../../include/mumpy_hip_ext.h"
+#include "../../include/mumpy_hip_ext2.h"
+#include "../../include/mumpy_hip_ext3.h"
+#include "../../include/mumpy_hip_ext4.h"
+#include "../../include/mumpy_hip_ext5.h"
+#include "../../include/mumpy_hip_ext6.h"
+#include "../../include/mumpy_hip_ext7.h"
+#include "../../include/mumpy_hip_ext8.h"
+#include "../../include/mumpy_hip_ext9.h"
+#include "../../include/mumpy_hip_ext10.h"
 
 namespace mumpy {
 static thread_local char g_err[512] = "";
@@ -65,5 +75,15 @@ extern "C" int mumpy_tuning_build(void) {
 }
 
 extern "C" int mumpy_abi_version(void) { return MUMPY_ABI_VERSION; }
+extern "C" int mumpy_ext_version(void) { return MUMPY_EXT_VERSION; }
+extern "C" int mumpy_ext2_version(void) { return MUMPY_EXT2_VERSION; }
+extern "C" int mumpy_ext3_version(void) { return MUMPY_EXT3_VERSION; }
+extern "C" int mumpy_ext4_version(void) { return MUMPY_EXT4_VERSION; }
+extern "C" int mumpy_ext5_version(void) { return MUMPY_EXT5_VERSION; }
+extern "C" int mumpy_ext6_version(void) { return MUMPY_EXT6_VERSION; }
+extern "C" int mumpy_ext7_version(void) { return MUMPY_EXT7_VERSION; }
+extern "C" int mumpy_ext8_version(void) { return MUMPY_EXT8_VERSION; }
+extern "C" int mumpy_ext9_version(void) { return MUMPY_EXT9_VERSION; }
+extern "C" int mumpy_ext10_version(void) { return MUMPY_EXT10_VERSION; }
 extern "C" const char* mumpy_last_error(void) { return mumpy::g_err; }
 extern "C" const char* mumpy_last_route(void) { return mumpy::format_route(); }

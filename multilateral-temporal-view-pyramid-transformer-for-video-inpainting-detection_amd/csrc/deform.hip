@@ -340,8 +340,6 @@ extern "C" int mumpy_deform_sample_grouped_fwd(const float* x2, const float* pos
     return sample_launch("deform_sample_grouped", x2, pos, out, B, Hs2, W, C, nq, groups, stream);
 }
 
-extern "C" int mumpy_ext8_version(void) { return MUMPY_EXT8_VERSION; }
-
 extern "C" int mumpy_deform_combine_fwd(const float* x1, const float* Yt, float* out, int B, int H, int W, int C,
                                         void* stream) {
     MUMPY_REQUIRE(x1 && Yt && out, MUMPY_ENULL, "deform_combine: null pointer");

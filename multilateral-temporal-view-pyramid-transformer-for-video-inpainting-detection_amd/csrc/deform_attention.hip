@@ -730,8 +730,6 @@ extern "C" int mumpy_deform_attention_grouped_bwd(const float* q, const float* k
 }
 
 // ---- include/mumpy_hip_ext2.h ----
-extern "C" int mumpy_ext2_version(void) { return MUMPY_EXT2_VERSION; }
-
 // 0 when (B1w, r, C) is a shape mumpy_deform_attention_mm16_bwd takes, else the code it refuses it with.  The range limits: the grids
 // (B1w r C/32 kv units, 2 B1w C/32 q units, four to a block) and the 32-bit byte offset of a row inside a kv window (49 rows of 8C bytes).
 static int mm16_bwd_shape(int64_t B1w, int r, int C) {

@@ -299,5 +299,3 @@ extern "C" int mumpy_deform_sample_grouped_bwd(const float* x2, const float* pos
     if (groups == 1) return sample_bwd_launch<false>(who, x2, pos, dsampled, dx2, dpos_part, B2, C, nq, 1, stream);
     return sample_bwd_launch<true>(who, x2, pos, dsampled, dx2, dpos_part, B2, C, nq, groups, stream);
 }
-
-extern "C" int mumpy_ext9_version(void) { return MUMPY_EXT9_VERSION; }

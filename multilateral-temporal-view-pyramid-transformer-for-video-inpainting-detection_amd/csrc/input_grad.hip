@@ -11,8 +11,6 @@
 #include "../../include/mumpy_hip_ext10.h"
 using namespace mumpy;
 
-extern "C" int mumpy_ext10_version(void) { return MUMPY_EXT10_VERSION; }
-
 namespace {
 
 struct DxView {

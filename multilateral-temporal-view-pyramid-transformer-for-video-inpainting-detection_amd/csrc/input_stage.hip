@@ -18,8 +18,6 @@
 #include "../../include/mumpy_hip_ext3.h"
 using namespace mumpy;
 
-extern "C" int mumpy_ext3_version(void) { return MUMPY_EXT3_VERSION; }
-
 namespace {
 
 constexpr int TS = 32, TROW = TS + 4;

@@ -22,8 +22,6 @@
 #include "../../include/mumpy_hip_ext4.h"
 using namespace mumpy;
 
-extern "C" int mumpy_ext4_version(void) { return MUMPY_EXT4_VERSION; }
-
 namespace {
 
 constexpr int TS = 32, TROW = TS + 4;

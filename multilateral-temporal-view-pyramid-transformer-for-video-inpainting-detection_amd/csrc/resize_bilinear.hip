@@ -15,8 +15,6 @@
 #include "../../include/mumpy_hip_ext6.h"
 using namespace mumpy;
 
-extern "C" int mumpy_ext6_version(void) { return MUMPY_EXT6_VERSION; }
-
 namespace {
 
 constexpr int BAND = 16;             // output rows per workgroup, halved until the band's intermediate rows fit MUMPY_RESIZE_BAND_BYTES

@@ -15,8 +15,6 @@
 #include "../../include/mumpy_hip_ext7.h"
 using namespace mumpy;
 
-extern "C" int mumpy_ext7_version(void) { return MUMPY_EXT7_VERSION; }
-
 namespace {
 
 constexpr int NBIN = MUMPY_SWEEP_MAX_THRESHOLDS + 1;        // bins per class at the cap

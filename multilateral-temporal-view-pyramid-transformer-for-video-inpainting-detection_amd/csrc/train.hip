@@ -712,8 +712,6 @@ bool aligned_to(const void* p, unsigned bytes) { return (reinterpret_cast<uintpt
 
 }  // namespace
 
-extern "C" int mumpy_ext_version(void) { return MUMPY_EXT_VERSION; }
-
 extern "C" int mumpy_adamw_gate_hyper(double* out4_host, double lr, double beta1, double beta2, int step) {
     MUMPY_REQUIRE(out4_host, MUMPY_ENULL, "adamw_gate_hyper: null pointer");
     MUMPY_REQUIRE(step >= 1 && beta1 >= 0. && beta1 < 1. && beta2 >= 0. && beta2 < 1., MUMPY_EINVAL, "adamw_gate_hyper: bad arguments");

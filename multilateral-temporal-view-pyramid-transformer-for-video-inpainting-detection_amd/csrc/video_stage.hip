@@ -14,8 +14,6 @@
 #include "../../include/mumpy_hip_ext5.h"
 using namespace mumpy;
 
-extern "C" int mumpy_ext5_version(void) { return MUMPY_EXT5_VERSION; }
-
 namespace {
 
 // The clamps are unconditional: the tables are device memory that nobody validated.

@@ -628,50 +628,14 @@ def _refuse_clip_coupling(who):
 
 class DeformSampleFn(torch.autograd.Function):
     """Bilinear sampling of kv windows at the learned positions (grid_sample semantics of deform:353-356), window form:
-    x2w (B2,49,C), pos (nq,3,49,2) -> (B2,49,C); kv window b2 uses pos[b2 % nq]."""
+    x2w (B2,49,C), pos (nq,3,49,2) -> (B2,49,C); kv window b2 uses pos[b2 % nq].  groups = G > 1 applies that rule inside each of G
+    equal slices of the windows (ops.cva_pairing; G = number of clips: per-clip pairing), forward and backward: an explicit
+    argument that does not consult ops.clip_coupling().  groups = 1, the batch-coupled rule, refuses to run under "clip"."""
 
     @staticmethod
-    def forward(ctx, x2w, pos):
-        _refuse_clip_coupling("DeformSampleFn")
-        ctx.save_for_backward(x2w, pos)
-        b2, _, c = x2w.shape
-        return ops.deform_sample(x2w.reshape(b2, 49, c), pos, b2, 7, 7, c, pos.shape[0])
-
-    @staticmethod
-    def backward(ctx, ds):
-        x2w, pos = ctx.saved_tensors
-        return ops.deform_sample_bwd(x2w, pos, ds.contiguous())
-
-
-class DeformAttentionFn(torch.autograd.Function):
-    """softmax(q k^T * scale) v per kv window with the reference's pairing (q window = kv window mod B1, deform:330) and the sum
-    over adjacent r-tuples (deform:394-395), window form: q (B1,49,C), kv (B1*r,49,2C) -> (B1,49,C).  The arithmetic is
-    ops.cva_math() AT THE FORWARD: "bf16" runs the bf16-MFMA forward and, whatever the switch says by then, its own backward.  The
-    saved tensors are the fp32 q and kv either way."""
-
-    @staticmethod
-    def forward(ctx, q, kv, scale):
-        _refuse_clip_coupling("DeformAttentionFn")
-        b1, _, c = q.shape
-        r = kv.shape[0] // b1
-        ctx.save_for_backward(q, kv)
-        ctx.cfg = (r, scale)
-        ctx.math = ops.cva_math()
-        return ops.deform_attention(q, kv, ops.pad_mask(q.device), b1, 7, 7, c, r, scale, math=ctx.math)
-
-    @staticmethod
-    def backward(ctx, dout):
-        q, kv = ctx.saved_tensors
-        dq, dkv = ops.deform_attention_bwd(q, kv, dout.contiguous(), *ctx.cfg, math=ctx.math)
-        return dq, dkv, None
-
-
-class DeformSampleGroupedFn(torch.autograd.Function):
-    """DeformSampleFn with the pairing rule applied inside each of `groups` equal slices of the windows (ops.cva_pairing; groups =
-    number of clips: per-clip pairing), forward and backward.  An explicit argument: it does not consult ops.clip_coupling()."""
-
-    @staticmethod
-    def forward(ctx, x2w, pos, groups):
+    def forward(ctx, x2w, pos, groups=1):
+        if groups == 1:
+            _refuse_clip_coupling("DeformSampleFn")
         ctx.save_for_backward(x2w, pos)
         ctx.groups = groups
         b2, _, c = x2w.shape
@@ -684,12 +648,16 @@ class DeformSampleGroupedFn(torch.autograd.Function):
         return dx2, dpos, None
 
 
-class DeformAttentionGroupedFn(torch.autograd.Function):
-    """DeformAttentionFn with the pairing rule applied inside each of `groups` equal slices of the windows, forward and backward; the
-    arithmetic is ops.cva_math() at the forward, carried to the backward, as there."""
+class DeformAttentionFn(torch.autograd.Function):
+    """softmax(q k^T * scale) v per kv window with the reference's pairing (q window = kv window mod B1, deform:330) and the sum
+    over adjacent r-tuples (deform:394-395), window form: q (B1,49,C), kv (B1*r,49,2C) -> (B1,49,C).  The arithmetic is
+    ops.cva_math() AT THE FORWARD: "bf16" runs the bf16-MFMA forward and, whatever the switch says by then, its own backward.  The
+    saved tensors are the fp32 q and kv either way.  groups: as in DeformSampleFn."""
 
     @staticmethod
-    def forward(ctx, q, kv, scale, groups):
+    def forward(ctx, q, kv, scale, groups=1):
+        if groups == 1:
+            _refuse_clip_coupling("DeformAttentionFn")
         b1, _, c = q.shape
         r = kv.shape[0] // b1
         ctx.save_for_backward(q, kv)
@@ -721,8 +689,8 @@ def swin_dattention_train(att, x1w, x2w, groups=1):
     (already through `pre`), B2 = r*B1 -> y (B1,49,C) including the un-permuted (C,49) -> (49,C) reshape of deform:403.
     The offset network runs unfused (depthwise conv, LayerNorm, GELU, 1x1 conv as kernels; tanh / scaling / reference points
     on the (B1,3,49,2) positions are a few KB of torch arithmetic).  groups = 1: the reference's pairing over the whole batch
-    (DeformSampleFn / DeformAttentionFn, which refuse to run under ops.set_clip_coupling("clip")); groups = G > 1: the same rule
-    inside each of G equal slices of the windows (the Grouped functions; G = number of clips is per-clip pairing)."""
+    (DeformSampleFn / DeformAttentionFn then refuse to run under ops.set_clip_coupling("clip")); groups = G > 1: the same rule
+    inside each of G equal slices of the windows (G = number of clips is per-clip pairing)."""
     b1, _, c = x1w.shape
     g, cg = att.n_groups, att.n_group_channels
     q = LinearFn.apply(x1w, att.proj_q.weight, att.proj_q.bias)          # (C,C,1,1) leaf: dW accumulates in its grad slot
@@ -733,14 +701,11 @@ def swin_dattention_train(att, x1w, x2w, groups=1):
     wpw = torch.nn.functional.pad(off[3].weight.reshape(2, cg), (0, 0, 0, 30))            # N = 2 padded to the GEMM's multiple of 32
     o2 = LinearFn.apply(a.reshape(-1, cg), wpw, None)[:, :2].reshape(b1, g, 49, 2)
     pos = torch.tanh(o2) * (2.0 / 7.0) + _ref_points(x1w.device)                           # deform:339-349, (y, x)
-    if groups == 1:
-        samp = DeformSampleFn.apply(x2w.contiguous(), pos.contiguous())
-    else:
-        samp = DeformSampleGroupedFn.apply(x2w.contiguous(), pos.contiguous(), groups)
+    samp = DeformSampleFn.apply(x2w.contiguous(), pos.contiguous(), groups)
     wkv = torch.cat([att.proj_k.weight.reshape(c, c), att.proj_v.weight.reshape(c, c)], 0)
     bkv = torch.cat([att.proj_k.bias, att.proj_v.bias])
     kv = LinearFn.apply(samp, wkv, bkv)
-    o = DeformAttentionFn.apply(q, kv, att.scale) if groups == 1 else DeformAttentionGroupedFn.apply(q, kv, att.scale, groups)
+    o = DeformAttentionFn.apply(q, kv, att.scale, groups)
     yt = LinearFn.apply(o, att.proj_out.weight, att.proj_out.bias)
     return yt.transpose(1, 2).reshape(b1, 49, c)
 

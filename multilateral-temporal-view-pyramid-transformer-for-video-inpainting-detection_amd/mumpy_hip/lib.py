@@ -2,6 +2,7 @@
 import ctypes
 import os
 import subprocess
+from typing import NamedTuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PKG = os.path.dirname(_HERE)
@@ -13,193 +14,180 @@ c_l = ctypes.c_int64
 c_fl = ctypes.c_float
 c_d = ctypes.c_double
 
-# name -> argtypes; mirrors include/mumpy_hip.h one to one (tests/test_abi.py checks the header against this)
-SIGNATURES = {
-    "mumpy_layernorm_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_fl, c_f],
-    "mumpy_layernorm_bf16_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_fl, c_f],
-    "mumpy_linear_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
-    "mumpy_linear_bf16s_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_window_attention_bf16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_window_attention_bf16mm_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_linear_ws_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_linear_wsz_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_linear_rd_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
-    "mumpy_window_attention_bg_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_linear_workspace_bytes": [c_l, c_i, c_i],
-    "mumpy_tuning_build": [],
-    "mumpy_workspace_status": [c_f, ctypes.POINTER(ctypes.c_int)],
-    "mumpy_linear_ln_tiles": [c_l, c_i, c_i],
-    "mumpy_linear_lnx_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f, c_f, c_i, c_f, c_fl, c_f],
-    "mumpy_linear_rows_fwd": [c_f, c_l, c_l, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_linear_rows_kseg_fwd": [c_f, c_l, c_l, c_i, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_gn_stats_nhwc_fwd": [c_f, c_f, c_i, c_l, c_i, c_i, c_i, c_f],
-    "mumpy_gn_apply_resample_nhwc_fwd": [c_f, c_f, c_i, c_f, c_f, c_i, c_fl, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_i,
-                                         c_i, c_i, c_i, c_i, c_f],
-    "mumpy_conv2d_nhwc_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_conv2d_workspace_bytes": [c_i, c_i, c_i, c_i, c_i, c_i, c_i],
-    "mumpy_avgpool2_pad_nhwc_fwd": [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_copy_rows_fwd": [c_f, c_l, c_f, c_l, c_l, c_i, c_f],
-    "mumpy_merge_views_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_trunk_head_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_final_conv_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_window_attention_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_deform_offsets_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_sample_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_attention_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_deform_sample_kv_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_out_combine_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_attention_mm16_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_window_attention_plan": [c_i, c_i, c_i, c_i],
-    "mumpy_window_attention_bf16_plan": [c_i, c_i, c_i, c_i],
-    "mumpy_deform_attention_plan": [c_i, c_i, c_i, c_i, c_i],
-    "mumpy_deform_sample_kv_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_out_combine_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_combine_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_faf_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_patch_embed_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_patch_merge_ln_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_temporal_attention_fwd": [c_f, c_f, c_l, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_attention_probs_fwd": [c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_fl, c_f],
-    "mumpy_temporal_attention_q_fwd": [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_sigmoid_threshold_fwd": [c_f, c_f, c_l, c_fl, c_f],
-    "mumpy_add_fwd": [c_f, c_f, c_f, c_l, c_f],
-    "mumpy_normalize_u8_fwd": [c_f, c_f, c_l, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f],
-    "mumpy_resize_nearest_table": [c_i, c_i, ctypes.POINTER(ctypes.c_int32)],
-    "mumpy_resize_normalize_u8_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f],
-    "mumpy_mask_loss_workspace_bytes": [c_i, c_l],
-    "mumpy_mask_loss_fwd_bwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_fl, c_fl, c_f],
-    "mumpy_layernorm_bwd_workspace_bytes": [c_l, c_i],
-    "mumpy_layernorm_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_fl, c_i, c_f],
-    "mumpy_gelu_fwd": [c_f, c_f, c_l, c_f],
-    "mumpy_gelu_bwd": [c_f, c_f, c_f, c_l, c_f],
-    "mumpy_transpose_fwd": [c_f, c_f, c_l, c_l, c_f],
-    "mumpy_col_sum_workspace_bytes": [c_l, c_i],
-    "mumpy_col_sum_fwd": [c_f, c_f, c_f, c_l, c_l, c_i, c_f],
-    "mumpy_final_conv_bwd_workspace_bytes": [c_i, c_i, c_i],
-    "mumpy_final_conv_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_patch_gather_fwd": [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_conv_weight_dgrad_fwd": [c_f, c_f, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_conv2d_wgrad_workspace_bytes": [c_i, c_i, c_i, c_i, c_i, c_i, c_i],
-    "mumpy_conv2d_wgrad_nhwc": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_linear_bwd_workspace_bytes": [c_l, c_i, c_i],
-    "mumpy_linear_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_window_attention_bwd_workspace_bytes": [c_i, c_i, c_i, c_i],
-    "mumpy_window_attention_bwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
-    "mumpy_window_attention_bwd_csr": [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
-    "mumpy_window_attention_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_window_attention_mm16_bwd_workspace_bytes": [c_i, c_i, c_i, c_i],
-    "mumpy_window_attention_mm16_bwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
-    "mumpy_relpos_bias_expand_fwd": [c_f, c_f, c_f, c_i, c_f],
-    "mumpy_gn_bwd_workspace_bytes": [c_i, c_l, c_i],
-    "mumpy_gn_bwd_nhwc": [c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_fl, c_i, c_f],
-    "mumpy_upsample_bwd_nhwc": [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_temporal_attention_bwd": [c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_fl, c_f],
-    "mumpy_scale_samples_fwd": [c_f, c_f, c_f, c_i, c_l, c_f],
-    "mumpy_dwconv5_window_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_f],
-    "mumpy_dwconv5_window_bwd_workspace_bytes": [c_l, c_i],
-    "mumpy_dwconv5_window_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_f],
-    "mumpy_deform_attention_bwd_workspace_bytes": [c_l, c_i],
-    "mumpy_deform_attention_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_f],
-    "mumpy_deform_sample_bwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_f],
-    "mumpy_adamw_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_d, c_i, c_d],
-    "mumpy_adamw_step_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f],
-    "mumpy_adamw_step": [c_f, c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_d, c_i, c_d, c_f],
-    "mumpy_sgd_step": [c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_i, c_d, c_f],
-    "mumpy_sgd_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_i, c_d],
-    "mumpy_sgd_step_dev": [c_f, c_f, c_f, c_l, c_f, c_i, c_f],
-    "mumpy_rmsprop_step": [c_f, c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_d, c_d, c_f],
-    "mumpy_rmsprop_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_d, c_d],
-    "mumpy_rmsprop_step_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f],
-    "mumpy_grad_norm_partials": [c_l],
-    "mumpy_grad_norm_partial": [c_f, c_l, c_f, c_f],
-    "mumpy_grad_norm_finish": [c_f, c_f, c_f, c_f, c_i, c_i, c_d, c_f, c_f],      # (the first four: HOST tables, one entry per group)
-}
-ABI_VERSION = 2
 
-# entry points added after that surface was frozen; mirrors include/mumpy_hip_ext.h one to one (tests/test_update_guard.py checks it)
-EXT_SIGNATURES = {
-    "mumpy_adamw_gate_hyper": [ctypes.POINTER(ctypes.c_double), c_d, c_d, c_d, c_i],
-    "mumpy_update_gate": [c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f],       # (stats, hyper_dev, optimizer_kind: HOST tables)
-    "mumpy_adamw_step_gated_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f, c_f],
-    "mumpy_sgd_step_gated_dev": [c_f, c_f, c_f, c_l, c_f, c_i, c_f, c_f],
-    "mumpy_rmsprop_step_gated_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f, c_f],
-}
-EXT_VERSION = 1
+class Surface(NamedTuple):
+    """One public header of include/ and its binding.  `version_fn` is the export that answers the header's version define."""
+    header: str
+    version_fn: str
+    version: int
+    signatures: dict        # name -> argtypes; the return type is int64_t for a *_bytes query and int for everything else
 
-# ... and after that one was; mirrors include/mumpy_hip_ext2.h one to one (tests/test_cva_bf16mm_train.py checks it)
-EXT2_SIGNATURES = {
-    "mumpy_deform_attention_mm16_bwd_workspace_bytes": [c_l, c_i, c_i],
-    "mumpy_deform_attention_mm16_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_f],
-    "mumpy_linear_gelu_dual_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
-    "mumpy_linear_gelu_bwd_workspace_bytes": [c_l, c_i, c_i],
-    "mumpy_linear_gelu_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
-}
-EXT2_VERSION = 2
 
-# ... and after that one; mirrors include/mumpy_hip_ext3.h one to one (tests/test_augment_host.py checks it).  mean3 / std3: HOST arrays
-EXT3_SIGNATURES = {
-    "mumpy_augment_stage_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float),
-                                   ctypes.POINTER(ctypes.c_float), c_f],
-}
-EXT3_VERSION = 1
-
-# ... and after that one; mirrors include/mumpy_hip_ext4.h one to one (tests/test_augment_warp_host.py checks it).  mean3 / std3: HOST
-EXT4_SIGNATURES = {
-    "mumpy_augment_warp_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i,
-                                  ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f],
-}
-EXT4_VERSION = 1
-
-# ... and after that one; mirrors include/mumpy_hip_ext5.h one to one (tests/test_video_host.py checks it).  mean3 / std3: HOST
-EXT5_SIGNATURES = {
-    "mumpy_clip_window_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float),
-                                 ctypes.POINTER(ctypes.c_float), c_f],
-    "mumpy_mask_score_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_l, c_f],
-    "mumpy_frame_metrics_fwd": [c_f, c_l, c_l, c_f, c_i, c_f],
-}
-EXT5_VERSION = 1
-
-# ... and after that one; mirrors include/mumpy_hip_ext6.h one to one (tests/test_annot_resize_host.py checks it)
-EXT6_SIGNATURES = {
-    "mumpy_resize_bilinear_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-}
-EXT6_VERSION = 1
-
-# ... and after that one; mirrors include/mumpy_hip_ext7.h one to one (tests/test_threshold_sweep_host.py checks it)
-EXT7_SIGNATURES = {
-    "mumpy_score_exceed_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_l, c_i, c_f],
-    "mumpy_sweep_metrics_fwd": [c_f, c_l, c_l, c_i, c_f, c_f, c_i, c_f],
-}
-EXT7_VERSION = 1
-
-# ... and after that one; mirrors include/mumpy_hip_ext8.h one to one (tests/test_clip_coupling_host.py checks it): the frozen
-# siblings' arguments plus `int groups` before the stream
-EXT8_SIGNATURES = {
-    "mumpy_deform_sample_grouped_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_sample_kv_grouped_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_sample_kv_mm16_grouped_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_deform_attention_grouped_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
-    "mumpy_deform_attention_mm16_grouped_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
-}
-EXT8_VERSION = 1
-
-# ... and after that one; mirrors include/mumpy_hip_ext9.h one to one (tests/test_clip_coupling_train_host.py checks it): the frozen
-# backward siblings' arguments plus `int groups` before the stream
-EXT9_SIGNATURES = {
-    "mumpy_deform_sample_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
-    "mumpy_deform_attention_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_i, c_f],
-    "mumpy_deform_attention_mm16_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_i, c_f],
-}
-EXT9_VERSION = 1
-
-# ... and after that one; mirrors include/mumpy_hip_ext10.h one to one (tests/test_input_grad_host.py checks it).  eps3 / lo3 / hi3: HOST
-EXT10_SIGNATURES = {
-    "mumpy_faf_bwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_tokenize_dx": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
-    "mumpy_pgd_step": [c_f, c_f, c_f, c_l, c_l, c_fl, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
-                       ctypes.POINTER(ctypes.c_float), c_f],
-}
-EXT10_VERSION = 1
+# One record per header, oldest first: a surface is frozen once the next one exists.  Each table mirrors its header one to one
+# (tests/test_abi.py holds every record to its header and to both libraries' exports).
+SURFACES = [
+    Surface("mumpy_hip.h", "mumpy_abi_version", 2, {
+        "mumpy_layernorm_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_fl, c_f],
+        "mumpy_layernorm_bf16_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_fl, c_f],
+        "mumpy_linear_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
+        "mumpy_linear_bf16s_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_window_attention_bf16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_window_attention_bf16mm_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_linear_ws_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_linear_wsz_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_linear_rd_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
+        "mumpy_window_attention_bg_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_linear_workspace_bytes": [c_l, c_i, c_i],
+        "mumpy_tuning_build": [],
+        "mumpy_workspace_status": [c_f, ctypes.POINTER(ctypes.c_int)],
+        "mumpy_linear_ln_tiles": [c_l, c_i, c_i],
+        "mumpy_linear_lnx_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f, c_f, c_i, c_f, c_fl, c_f],
+        "mumpy_linear_rows_fwd": [c_f, c_l, c_l, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_linear_rows_kseg_fwd": [c_f, c_l, c_l, c_i, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_gn_stats_nhwc_fwd": [c_f, c_f, c_i, c_l, c_i, c_i, c_i, c_f],
+        "mumpy_gn_apply_resample_nhwc_fwd": [c_f, c_f, c_i, c_f, c_f, c_i, c_fl, c_i, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_i, c_i,
+                                             c_i, c_i, c_i, c_i, c_f],
+        "mumpy_conv2d_nhwc_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_conv2d_workspace_bytes": [c_i, c_i, c_i, c_i, c_i, c_i, c_i],
+        "mumpy_avgpool2_pad_nhwc_fwd": [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_copy_rows_fwd": [c_f, c_l, c_f, c_l, c_l, c_i, c_f],
+        "mumpy_merge_views_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_trunk_head_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_final_conv_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_window_attention_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_deform_offsets_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_sample_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_attention_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_deform_sample_kv_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_out_combine_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_attention_mm16_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_window_attention_plan": [c_i, c_i, c_i, c_i],
+        "mumpy_window_attention_bf16_plan": [c_i, c_i, c_i, c_i],
+        "mumpy_deform_attention_plan": [c_i, c_i, c_i, c_i, c_i],
+        "mumpy_deform_sample_kv_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_out_combine_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_combine_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_faf_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_patch_embed_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_patch_merge_ln_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_temporal_attention_fwd": [c_f, c_f, c_l, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_attention_probs_fwd": [c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_fl, c_f],
+        "mumpy_temporal_attention_q_fwd": [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_sigmoid_threshold_fwd": [c_f, c_f, c_l, c_fl, c_f],
+        "mumpy_add_fwd": [c_f, c_f, c_f, c_l, c_f],
+        "mumpy_normalize_u8_fwd": [c_f, c_f, c_l, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f],
+        "mumpy_resize_nearest_table": [c_i, c_i, ctypes.POINTER(ctypes.c_int32)],
+        "mumpy_resize_normalize_u8_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f],
+        "mumpy_mask_loss_workspace_bytes": [c_i, c_l],
+        "mumpy_mask_loss_fwd_bwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_fl, c_fl, c_f],
+        "mumpy_layernorm_bwd_workspace_bytes": [c_l, c_i],
+        "mumpy_layernorm_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_fl, c_i, c_f],
+        "mumpy_gelu_fwd": [c_f, c_f, c_l, c_f],
+        "mumpy_gelu_bwd": [c_f, c_f, c_f, c_l, c_f],
+        "mumpy_transpose_fwd": [c_f, c_f, c_l, c_l, c_f],
+        "mumpy_col_sum_workspace_bytes": [c_l, c_i],
+        "mumpy_col_sum_fwd": [c_f, c_f, c_f, c_l, c_l, c_i, c_f],
+        "mumpy_final_conv_bwd_workspace_bytes": [c_i, c_i, c_i],
+        "mumpy_final_conv_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_patch_gather_fwd": [c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_conv_weight_dgrad_fwd": [c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_conv2d_wgrad_workspace_bytes": [c_i, c_i, c_i, c_i, c_i, c_i, c_i],
+        "mumpy_conv2d_wgrad_nhwc": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_linear_bwd_workspace_bytes": [c_l, c_i, c_i],
+        "mumpy_linear_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_window_attention_bwd_workspace_bytes": [c_i, c_i, c_i, c_i],
+        "mumpy_window_attention_bwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
+        "mumpy_window_attention_bwd_csr": [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
+        "mumpy_window_attention_mm16_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_window_attention_mm16_bwd_workspace_bytes": [c_i, c_i, c_i, c_i],
+        "mumpy_window_attention_mm16_bwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
+        "mumpy_relpos_bias_expand_fwd": [c_f, c_f, c_f, c_i, c_f],
+        "mumpy_gn_bwd_workspace_bytes": [c_i, c_l, c_i],
+        "mumpy_gn_bwd_nhwc": [c_f, c_f, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_fl, c_i, c_f],
+        "mumpy_upsample_bwd_nhwc": [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_temporal_attention_bwd": [c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_fl, c_f],
+        "mumpy_scale_samples_fwd": [c_f, c_f, c_f, c_i, c_l, c_f],
+        "mumpy_dwconv5_window_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_f],
+        "mumpy_dwconv5_window_bwd_workspace_bytes": [c_l, c_i],
+        "mumpy_dwconv5_window_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_f],
+        "mumpy_deform_attention_bwd_workspace_bytes": [c_l, c_i],
+        "mumpy_deform_attention_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_f],
+        "mumpy_deform_sample_bwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_f],
+        "mumpy_adamw_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_d, c_i, c_d],
+        "mumpy_adamw_step_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f],
+        "mumpy_adamw_step": [c_f, c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_d, c_i, c_d, c_f],
+        "mumpy_sgd_step": [c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_i, c_d, c_f],
+        "mumpy_sgd_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_i, c_d],
+        "mumpy_sgd_step_dev": [c_f, c_f, c_f, c_l, c_f, c_i, c_f],
+        "mumpy_rmsprop_step": [c_f, c_f, c_f, c_f, c_l, c_d, c_d, c_d, c_d, c_d, c_d, c_f],
+        "mumpy_rmsprop_hyper": [ctypes.POINTER(ctypes.c_float), c_d, c_d, c_d, c_d, c_d, c_d],
+        "mumpy_rmsprop_step_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f],
+        "mumpy_grad_norm_partials": [c_l],
+        "mumpy_grad_norm_partial": [c_f, c_l, c_f, c_f],
+        "mumpy_grad_norm_finish": [c_f, c_f, c_f, c_f, c_i, c_i, c_d, c_f, c_f],      # (the first four: HOST tables, one entry per group)
+    }),
+    Surface("mumpy_hip_ext.h", "mumpy_ext_version", 1, {
+        "mumpy_adamw_gate_hyper": [ctypes.POINTER(ctypes.c_double), c_d, c_d, c_d, c_i],
+        "mumpy_update_gate": [c_f, c_i, c_f, c_f, c_f, c_i, c_f, c_f, c_f],       # (stats, hyper_dev, optimizer_kind: HOST tables)
+        "mumpy_adamw_step_gated_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f, c_f],
+        "mumpy_sgd_step_gated_dev": [c_f, c_f, c_f, c_l, c_f, c_i, c_f, c_f],
+        "mumpy_rmsprop_step_gated_dev": [c_f, c_f, c_f, c_f, c_l, c_f, c_f, c_f],
+    }),
+    Surface("mumpy_hip_ext2.h", "mumpy_ext2_version", 2, {
+        "mumpy_deform_attention_mm16_bwd_workspace_bytes": [c_l, c_i, c_i],
+        "mumpy_deform_attention_mm16_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_f],
+        "mumpy_linear_gelu_dual_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+        "mumpy_linear_gelu_bwd_workspace_bytes": [c_l, c_i, c_i],
+        "mumpy_linear_gelu_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f, c_l, c_f],
+    }),
+    # mean3 / std3: HOST arrays
+    Surface("mumpy_hip_ext3.h", "mumpy_ext3_version", 1, {
+        "mumpy_augment_stage_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float),
+                                       ctypes.POINTER(ctypes.c_float), c_f],
+    }),
+    # mean3 / std3: HOST arrays
+    Surface("mumpy_hip_ext4.h", "mumpy_ext4_version", 1, {
+        "mumpy_augment_warp_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i,
+                                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), c_f],
+    }),
+    # mean3 / std3: HOST arrays
+    Surface("mumpy_hip_ext5.h", "mumpy_ext5_version", 1, {
+        "mumpy_clip_window_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_l, c_i, c_i, c_i, c_i, ctypes.POINTER(ctypes.c_float),
+                                     ctypes.POINTER(ctypes.c_float), c_f],
+        "mumpy_mask_score_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_l, c_f],
+        "mumpy_frame_metrics_fwd": [c_f, c_l, c_l, c_f, c_i, c_f],
+    }),
+    Surface("mumpy_hip_ext6.h", "mumpy_ext6_version", 1, {
+        "mumpy_resize_bilinear_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+    }),
+    Surface("mumpy_hip_ext7.h", "mumpy_ext7_version", 1, {
+        "mumpy_score_exceed_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_l, c_i, c_f],
+        "mumpy_sweep_metrics_fwd": [c_f, c_l, c_l, c_i, c_f, c_f, c_i, c_f],
+    }),
+    # the frozen siblings' arguments plus `int groups` before the stream
+    Surface("mumpy_hip_ext8.h", "mumpy_ext8_version", 1, {
+        "mumpy_deform_sample_grouped_fwd": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_sample_kv_grouped_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_sample_kv_mm16_grouped_fwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_deform_attention_grouped_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
+        "mumpy_deform_attention_mm16_grouped_fwd": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_fl, c_i, c_f],
+    }),
+    # the frozen backward siblings' arguments plus `int groups` before the stream
+    Surface("mumpy_hip_ext9.h", "mumpy_ext9_version", 1, {
+        "mumpy_deform_sample_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
+        "mumpy_deform_attention_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_i, c_f],
+        "mumpy_deform_attention_mm16_grouped_bwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_fl, c_i, c_f],
+    }),
+    # eps3 / lo3 / hi3: HOST arrays
+    Surface("mumpy_hip_ext10.h", "mumpy_ext10_version", 1, {
+        "mumpy_faf_bwd": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_tokenize_dx": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+        "mumpy_pgd_step": [c_f, c_f, c_f, c_l, c_l, c_fl, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float),
+                           ctypes.POINTER(ctypes.c_float), c_f],
+    }),
+]
+ABI_VERSION = SURFACES[0].version
+SIGNATURES = {name: args for s in SURFACES for name, args in s.signatures.items()}      # every bound entry, whichever header declares it
 
 
 def library_path() -> str:
@@ -237,57 +225,17 @@ def load_library():
             f"libmumpy_hip.so not found at {path}: the HIP kernels are the only implementation of this package "
             "(no CPU/torch fallback). Build it with `python __graft_entry__.py` or `make -C <pkg>/csrc`.")
     lib = ctypes.CDLL(path)
-    lib.mumpy_abi_version.restype = c_i
     lib.mumpy_last_error.restype = ctypes.c_char_p
-    lib.mumpy_last_route.restype = ctypes.c_char_p      # (AttributeError = stale library, as below)
+    lib.mumpy_last_route.restype = ctypes.c_char_p      # (AttributeError here or below = the library is stale: fail loudly)
     lib.mumpy_last_route.argtypes = []
-    if lib.mumpy_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"{path}: ABI version {lib.mumpy_abi_version()} != binding {ABI_VERSION}; rebuild")
-    lib.mumpy_ext_version.restype = c_i                 # (AttributeError = stale library, as below)
-    lib.mumpy_ext_version.argtypes = []
-    if lib.mumpy_ext_version() != EXT_VERSION:
-        raise RuntimeError(f"{path}: extension version {lib.mumpy_ext_version()} != binding {EXT_VERSION}; rebuild")
-    lib.mumpy_ext2_version.restype = c_i
-    lib.mumpy_ext2_version.argtypes = []
-    if lib.mumpy_ext2_version() != EXT2_VERSION:
-        raise RuntimeError(f"{path}: second extension version {lib.mumpy_ext2_version()} != binding {EXT2_VERSION}; rebuild")
-    lib.mumpy_ext3_version.restype = c_i
-    lib.mumpy_ext3_version.argtypes = []
-    if lib.mumpy_ext3_version() != EXT3_VERSION:
-        raise RuntimeError(f"{path}: third extension version {lib.mumpy_ext3_version()} != binding {EXT3_VERSION}; rebuild")
-    lib.mumpy_ext4_version.restype = c_i
-    lib.mumpy_ext4_version.argtypes = []
-    if lib.mumpy_ext4_version() != EXT4_VERSION:
-        raise RuntimeError(f"{path}: fourth extension version {lib.mumpy_ext4_version()} != binding {EXT4_VERSION}; rebuild")
-    lib.mumpy_ext5_version.restype = c_i
-    lib.mumpy_ext5_version.argtypes = []
-    if lib.mumpy_ext5_version() != EXT5_VERSION:
-        raise RuntimeError(f"{path}: fifth extension version {lib.mumpy_ext5_version()} != binding {EXT5_VERSION}; rebuild")
-    lib.mumpy_ext6_version.restype = c_i
-    lib.mumpy_ext6_version.argtypes = []
-    if lib.mumpy_ext6_version() != EXT6_VERSION:
-        raise RuntimeError(f"{path}: sixth extension version {lib.mumpy_ext6_version()} != binding {EXT6_VERSION}; rebuild")
-    lib.mumpy_ext7_version.restype = c_i
-    lib.mumpy_ext7_version.argtypes = []
-    if lib.mumpy_ext7_version() != EXT7_VERSION:
-        raise RuntimeError(f"{path}: seventh extension version {lib.mumpy_ext7_version()} != binding {EXT7_VERSION}; rebuild")
-    lib.mumpy_ext8_version.restype = c_i
-    lib.mumpy_ext8_version.argtypes = []
-    if lib.mumpy_ext8_version() != EXT8_VERSION:
-        raise RuntimeError(f"{path}: eighth extension version {lib.mumpy_ext8_version()} != binding {EXT8_VERSION}; rebuild")
-    lib.mumpy_ext9_version.restype = c_i
-    lib.mumpy_ext9_version.argtypes = []
-    if lib.mumpy_ext9_version() != EXT9_VERSION:
-        raise RuntimeError(f"{path}: ninth extension version {lib.mumpy_ext9_version()} != binding {EXT9_VERSION}; rebuild")
-    lib.mumpy_ext10_version.restype = c_i
-    lib.mumpy_ext10_version.argtypes = []
-    if lib.mumpy_ext10_version() != EXT10_VERSION:
-        raise RuntimeError(f"{path}: tenth extension version {lib.mumpy_ext10_version()} != binding {EXT10_VERSION}; rebuild")
-    for name, args in {**SIGNATURES, **EXT_SIGNATURES, **EXT2_SIGNATURES, **EXT3_SIGNATURES, **EXT4_SIGNATURES,
-                       **EXT5_SIGNATURES, **EXT6_SIGNATURES, **EXT7_SIGNATURES, **EXT8_SIGNATURES, **EXT9_SIGNATURES,
-                       **EXT10_SIGNATURES}.items():
-        fn = getattr(lib, name)          # AttributeError here = the library is stale: fail loudly
-        fn.argtypes = args
-        fn.restype = c_l if name.endswith("_bytes") else c_i
+    for s in SURFACES:
+        version = getattr(lib, s.version_fn)
+        version.restype, version.argtypes = c_i, []
+        if version() != s.version:
+            raise RuntimeError(f"{path}: {s.version_fn}() is {version()}, the binding of include/{s.header} expects {s.version}; rebuild")
+        for name, args in s.signatures.items():
+            fn = getattr(lib, name)
+            fn.argtypes = args
+            fn.restype = c_l if name.endswith("_bytes") else c_i
     _LIB = lib
     return lib

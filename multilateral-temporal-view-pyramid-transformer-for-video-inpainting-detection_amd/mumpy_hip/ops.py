@@ -170,14 +170,27 @@ def linear_bf16s(x16, w16, bias=None, act=ACT_NONE, residual=None, out_bf16=True
     return out
 
 
-def _attn_math_from_env() -> str:
-    mode = os.environ.get("MUMPY_ATTN_MATH", "") or "fp32"
-    if mode not in ("fp32", "bf16"):
-        raise ValueError(f"MUMPY_ATTN_MATH: unknown attention math mode {mode!r}")
-    return mode
+def _choice(value, choices, what, var=None):
+    """`value` if it is one of `choices`, else a ValueError saying what it was to be (and the environment variable it came from)."""
+    if value not in choices:
+        raise ValueError(f"{var}: unknown {what} {value!r}" if var else f"unknown {what} {value!r}")
+    return value
 
 
-_ATTN_MATH = _attn_math_from_env()       # read once, at import
+def _env_choice(var, choices, default, what):
+    """Initial value of a process-wide switch: the environment variable `var`; unset or empty means `default`."""
+    return _choice(os.environ.get(var, "") or default, choices, what, var)
+
+
+# the process-wide switches: one tuple of values each, for the environment reader, the setter and the ops' explicit arguments
+_ATTN_MATHS, _ATTN_WHAT = ("fp32", "bf16"), "attention math mode"
+_CVA_MATHS, _CVA_WHAT = ("fp32", "bf16"), "cross-view attention math mode"
+_COUPLINGS, _COUPLING_WHAT = ("batch", "clip"), "clip coupling"
+# each read once, at import
+_ATTN_MATH = _env_choice("MUMPY_ATTN_MATH", _ATTN_MATHS, "fp32", _ATTN_WHAT)
+_CVA_MATH = _env_choice("MUMPY_CVA_MATH", _CVA_MATHS, "fp32", _CVA_WHAT)
+_CLIP_COUPLING = _env_choice("MUMPY_CLIP_COUPLING", _COUPLINGS, "batch", _COUPLING_WHAT)
+_MLP_FUSED = _env_choice("MUMPY_MLP_FUSED", ("0", "1"), "0", "MLP fusion setting (\"0\" or \"1\")") == "1"
 
 
 def set_attention_math(mode: str) -> None:
@@ -193,23 +206,11 @@ def set_attention_math(mode: str) -> None:
     this module is imported.  Like set_storage it is read at launch time: set it BEFORE a GraphedForward or a graphed training step
     is captured -- a captured graph keeps the kernels it was captured with."""
     global _ATTN_MATH
-    if mode not in ("fp32", "bf16"):
-        raise ValueError(f"unknown attention math mode {mode!r}")
-    _ATTN_MATH = mode
+    _ATTN_MATH = _choice(mode, _ATTN_MATHS, _ATTN_WHAT)
 
 
 def attention_math() -> str:
     return _ATTN_MATH
-
-
-def _cva_math_from_env() -> str:
-    mode = os.environ.get("MUMPY_CVA_MATH", "") or "fp32"
-    if mode not in ("fp32", "bf16"):
-        raise ValueError(f"MUMPY_CVA_MATH: unknown cross-view attention math mode {mode!r}")
-    return mode
-
-
-_CVA_MATH = _cva_math_from_env()         # read once, at import
 
 
 def set_cva_math(mode: str) -> None:
@@ -227,23 +228,11 @@ def set_cva_math(mode: str) -> None:
     MUMPY_CVA_MATH, read when this module is imported.  Read at launch time: set it BEFORE a GraphedForward or a graphed training step
     is captured -- a captured graph keeps the kernels it was captured with."""
     global _CVA_MATH
-    if mode not in ("fp32", "bf16"):
-        raise ValueError(f"unknown cross-view attention math mode {mode!r}")
-    _CVA_MATH = mode
+    _CVA_MATH = _choice(mode, _CVA_MATHS, _CVA_WHAT)
 
 
 def cva_math() -> str:
     return _CVA_MATH
-
-
-def _clip_coupling_from_env() -> str:
-    mode = os.environ.get("MUMPY_CLIP_COUPLING", "") or "batch"
-    if mode not in ("batch", "clip"):
-        raise ValueError(f"MUMPY_CLIP_COUPLING: unknown clip coupling {mode!r}")
-    return mode
-
-
-_CLIP_COUPLING = _clip_coupling_from_env()       # read once, at import
 
 
 def set_clip_coupling(mode: str) -> None:
@@ -259,9 +248,7 @@ def set_clip_coupling(mode: str) -> None:
     The initial value is the environment variable MUMPY_CLIP_COUPLING, read when this module is imported.  Read at launch
     time: a GraphedForward keeps the pairing it was captured with (its coupling= argument pins it)."""
     global _CLIP_COUPLING
-    if mode not in ("batch", "clip"):
-        raise ValueError(f"unknown clip coupling {mode!r}")
-    _CLIP_COUPLING = mode
+    _CLIP_COUPLING = _choice(mode, _COUPLINGS, _COUPLING_WHAT)
 
 
 def clip_coupling() -> str:
@@ -273,9 +260,7 @@ class clip_coupling_as:
     the body raises.  None leaves the switch alone (the body follows whatever it says)."""
 
     def __init__(self, mode: Optional[str]):
-        if mode not in (None, "batch", "clip"):
-            raise ValueError(f"unknown clip coupling {mode!r}")
-        self.mode = mode
+        self.mode = _choice(mode, (None,) + _COUPLINGS, _COUPLING_WHAT)
 
     def __enter__(self):
         self.prev = _CLIP_COUPLING
@@ -321,16 +306,6 @@ def cva_pairing_members(nkv: int, nq: int, groups: int = 1):
     return g * (r * nqg) + (qw - g * nqg) + np.arange(r, dtype=np.int64)[None, :] * nqg
 
 
-def _mlp_fusion_from_env() -> bool:
-    v = os.environ.get("MUMPY_MLP_FUSED", "") or "0"
-    if v not in ("0", "1"):
-        raise ValueError(f"MUMPY_MLP_FUSED: expected \"0\" or \"1\", got {v!r}")
-    return v == "1"
-
-
-_MLP_FUSED = _mlp_fusion_from_env()      # read once, at import
-
-
 def set_mlp_fusion(on: bool) -> None:
     """The MLP of a transformer block ON THE TRAINING TAPE (autograd.MlpFn: the Swin, global and cross-view blocks).  Off (default):
     fc1, GELU, fc2 as three tape nodes -- five launches a step that touch the hidden tensor.  On: fc1 writes z and a = gelu(z) from one
@@ -351,9 +326,7 @@ def mlp_fusion() -> bool:
 
 def _mm16(entry, math):
     """C-ABI entry of a cross-view attention op for math= "fp32" (the entry itself) or "bf16" (its _mm16 form)."""
-    if math not in ("fp32", "bf16"):
-        raise ValueError(f"unknown cross-view attention math mode {math!r}")
-    return entry.replace("_fwd", "_mm16_fwd") if math == "bf16" else entry
+    return entry.replace("_fwd", "_mm16_fwd") if _choice(math, _CVA_MATHS, _CVA_WHAT) == "bf16" else entry
 
 
 def _window_attention(entry, chk, dtype, who, qkv, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id, out=None):
@@ -390,10 +363,7 @@ def _chk_mask(mask_tab, mask_id, nwin, who):
 def window_attention_bf16(qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab=None, mask_id=None, math=None):
     """bf16 qkv (B, hs*w, 3C) -> bf16 (B, hs*w, C).  math: None follows attention_math(); "fp32" / "bf16" force the fp32-flow /
     the bf16-MFMA kernel."""
-    if math is None:
-        math = _ATTN_MATH
-    elif math not in ("fp32", "bf16"):
-        raise ValueError(f"unknown attention math mode {math!r}")
+    math = _ATTN_MATH if math is None else _choice(math, _ATTN_MATHS, _ATTN_WHAT)
     return _window_attention("mumpy_window_attention_bf16mm_fwd" if math == "bf16" else "mumpy_window_attention_bf16_fwd", _chk16,
                              torch.bfloat16, "window_attention_bf16", qkv16, bias_pad, b, hs, w, c, shift, scale, mask_tab, mask_id)
 
@@ -1690,8 +1660,7 @@ def window_attention_bwd(qkv, dout, bias_pad, rel_index32, b, hs, w, c, shift, s
     dtable_out: a gradient buffer to ACCUMULATE into (the returned dtable is then None).  rel_csr = rel_index_csr(index): the table
     gradient reads its pairs through the inverse index instead of scanning the index.  math: "fp32" (default; it does NOT follow
     set_attention_math) or "bf16", the backward of window_attention_mm16 (mumpy_window_attention_mm16_bwd)."""
-    if math not in ("fp32", "bf16"):
-        raise ValueError(f"unknown attention math mode {math!r}")
+    _choice(math, _ATTN_MATHS, _ATTN_WHAT)
     qkv, dout = _chk(qkv, "qkv"), _chk(dout, "dout")
     if qkv.numel() != b * hs * w * 3 * c or dout.numel() != b * hs * w * c:
         raise RuntimeError("window_attention_bwd: shape mismatch")
@@ -1845,8 +1814,7 @@ def deform_attention_bwd(q, kv, dout, r, scale, math="fp32", groups=1):
     over its r kv windows on the device in a fixed order (no partial slices, no add launches).  groups: the pairing rule of the
     forward this differentiates (cva_pairing): 1 is the reference's `i mod B1`; G > 1 sums, per group, the same r contributions in
     the same order as groups = 1 does on that group alone."""
-    if math not in ("fp32", "bf16"):
-        raise ValueError(f"unknown cross-view attention math mode {math!r}")
+    _choice(math, _CVA_MATHS, _CVA_WHAT)
     entry, extra = _grouped_bwd("mumpy_deform_attention_mm16_bwd" if math == "bf16" else "mumpy_deform_attention_bwd", groups,
                                 q.shape[0] if q.dim() else 0, "deform_attention_bwd")
     q = _chk(q, "q")
@@ -1882,22 +1850,13 @@ def deform_attention_bwd(q, kv, dout, r, scale, math="fp32", groups=1):
 
 def adamw_hyper(step, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0):
     """The 8 fp32 constants of one AdamW step as a pinned host tensor (for adamw_step_dev under hipGraph replay)."""
-    import ctypes
-    out = torch.empty(8, dtype=torch.float32).pin_memory()
-    rc = _lib().mumpy_adamw_hyper(ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_float)), lr, betas[0], betas[1], eps,
-                                  weight_decay, int(step), grad_scale)
-    if rc != 0:
-        raise RuntimeError(f"mumpy_adamw_hyper failed (rc={rc}): {_lib().mumpy_last_error().decode()}")
-    return out
+    return _hyper_out("mumpy_adamw_hyper", 8, lr, betas[0], betas[1], eps, weight_decay, int(step), grad_scale)
 
 
 def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, hyper_dev):
     """AdamW over flat buffers with the step constants in the device tensor `hyper_dev` (8 floats): capturable."""
     n = param.numel()
-    for name, t in (("param", param), ("grad", grad), ("exp_avg", exp_avg), ("exp_avg_sq", exp_avg_sq)):
-        _chk(t, name)
-        if t.numel() != n or not t.is_contiguous():
-            raise RuntimeError(f"adamw_step_dev: {name} must be a contiguous buffer of {n} elements (in-place update)")
+    _flat_bufs("adamw_step_dev", n, param=param, grad=grad, exp_avg=exp_avg, exp_avg_sq=exp_avg_sq)
     _call("mumpy_adamw_step_dev", _p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), n, _p(_chk_hyper("adamw_step_dev", hyper_dev, 8)), _stream(),
           work=28.0 * n)
     return param
@@ -1920,10 +1879,12 @@ def _flat_bufs(fn, n, **bufs):
             raise RuntimeError(f"{fn}: {name} must be a contiguous buffer of {n} elements (in-place update)")
 
 
-def _hyper_out(fn, count, *args):
+def _hyper_out(fn, count, *args, dtype=torch.float32):
+    """The `count` host constants that the C function `fn` derives from `args`, as a pinned tensor (float32, or float64)."""
     import ctypes
-    out = torch.empty(count, dtype=torch.float32).pin_memory()
-    rc = getattr(_lib(), fn)(ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_float)), *args)
+    out = torch.empty(count, dtype=dtype).pin_memory()
+    ctype = ctypes.c_double if dtype == torch.float64 else ctypes.c_float
+    rc = getattr(_lib(), fn)(ctypes.cast(out.data_ptr(), ctypes.POINTER(ctype)), *args)
     if rc != 0:
         raise RuntimeError(f"{fn} failed (rc={rc}): {_lib().mumpy_last_error().decode()}")
     return out
@@ -2042,12 +2003,7 @@ GATE_WORDS = 8             # [skip, skipped, consecutive, updates, longest, 0, 0
 def adamw_gate_hyper(step, lr, betas=(0.9, 0.999)):
     """The 4 doubles {lr, beta1, beta2, step} mumpy_update_gate re-derives AdamW's bias corrections from, as a pinned host tensor
     (staged beside adamw_hyper's 8 floats; `step` is the nominal count those were derived from)."""
-    import ctypes
-    out = torch.empty(4, dtype=torch.float64).pin_memory()
-    rc = _lib().mumpy_adamw_gate_hyper(ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_double)), lr, betas[0], betas[1], int(step))
-    if rc != 0:
-        raise RuntimeError(f"mumpy_adamw_gate_hyper failed (rc={rc}): {_lib().mumpy_last_error().decode()}")
-    return out
+    return _hyper_out("mumpy_adamw_gate_hyper", 4, lr, betas[0], betas[1], int(step), dtype=torch.float64)
 
 
 def _chk_gate(fn, gate):

@@ -1,67 +1,74 @@
-"""CPU: the C-ABI library builds/loads and exports every symbol include/mumpy_hip.h declares, with the arity the
-ctypes binding assumes.  No compute calls (no GPU here)."""
+"""CPU: every public header of include/ against its record in lib.SURFACES and against the exports of the shipped and the tuning
+library; the version-mismatch path of load_library.  No compute calls (no GPU here)."""
 import ctypes
+import glob
+import itertools
 import os
-import re
 
 import pytest
 
-from conftest import PKG, ROOT
+import abi_surface as S
+from conftest import ROOT
+from mumpy_hip import lib as L
 
-
-def header_decls():
-    src = open(os.path.join(ROOT, "include", "mumpy_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    decls = {}
-    for m in re.finditer(r"\b(?:int64_t|int|const char\*)\s+(mumpy_\w+)\s*\(([^)]*)\)\s*;", src):
-        args = [a.strip() for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        decls[m.group(1)] = args
-    return decls
+# literals, so that a header and its record cannot drift together unnoticed (mumpy_hip.h: 2 since mumpy_layernorm_bwd grew dx_add /
+# accumulate; ext2: 2 since the fused-MLP entries)
+VERSIONS = {"mumpy_hip.h": 2, "mumpy_hip_ext.h": 1, "mumpy_hip_ext2.h": 2, "mumpy_hip_ext3.h": 1, "mumpy_hip_ext4.h": 1,
+            "mumpy_hip_ext5.h": 1, "mumpy_hip_ext6.h": 1, "mumpy_hip_ext7.h": 1, "mumpy_hip_ext8.h": 1, "mumpy_hip_ext9.h": 1,
+            "mumpy_hip_ext10.h": 1}
+HAND_BOUND = {"mumpy_hip.h": {"mumpy_last_error", "mumpy_last_route"}}          # load_library binds these two itself
 
 
 def test_header_declares_expected_entry_points():
-    d = header_decls()
+    d = S.decls("mumpy_hip.h")
     for name in ("mumpy_window_attention_fwd", "mumpy_deform_sample_fwd", "mumpy_deform_attention_fwd", "mumpy_faf_fwd",
                  "mumpy_patch_embed_fwd", "mumpy_linear_fwd", "mumpy_layernorm_fwd", "mumpy_last_error"):
         assert name in d
 
 
-def test_library_exports_every_declared_symbol():
-    from mumpy_hip.lib import SIGNATURES, library_path, load_library
-    assert os.path.exists(library_path()), "build with `python __graft_entry__.py`"
-    lib = load_library()
-    decls = header_decls()
-    for name, args in decls.items():
-        assert hasattr(lib, name), f"{name} declared in the header but not exported"
-        if name in SIGNATURES:
-            assert len(SIGNATURES[name]) == len(args), f"{name}: binding has {len(SIGNATURES[name])} args, header {len(args)}"
-    for name in SIGNATURES:
-        assert name in decls, f"{name} bound but not declared in include/mumpy_hip.h"
-    from mumpy_hip.lib import ABI_VERSION
-    assert lib.mumpy_abi_version() == ABI_VERSION == 2          # bumped when mumpy_layernorm_bwd grew dx_add / accumulate
-
-
-def test_binding_argument_types_match_the_header():
-    """Every bound argument has the ctypes kind of its C declaration (a float/double or int/int64 slip corrupts the call)."""
-    from mumpy_hip.lib import SIGNATURES
-    decls = header_decls()
-
-    def kind(carg):
-        carg = carg.strip()
-        if "*" in carg:
-            return "ptr"
-        base = carg.rsplit(None, 1)[0] if " " in carg else carg
-        return {"int": "int", "int64_t": "i64", "float": "f32", "double": "f64"}[base.replace("const ", "").strip()]
-
-    def ckind(t):
-        if t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-            return "ptr"
-        return {ctypes.c_int: "int", ctypes.c_int64: "i64", ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
-
-    for name, args in SIGNATURES.items():
-        got = [ckind(t) for t in args]
-        want = [kind(a) for a in decls[name]]
+@pytest.mark.parametrize("s", L.SURFACES, ids=[s.header for s in L.SURFACES])
+def test_surface_header_binding_and_exports_agree(s):
+    """Per header: every declared name is exported by both libraries; the bound names are the declared ones minus the version
+    function (and what load_library binds by hand); every bound argument and the return type have the ctypes kind of the C
+    declaration (a float/double or int/int64 slip corrupts the call); the version agrees everywhere."""
+    assert os.path.exists(L.library_path()) and os.path.exists(L.tuning_library_path()), "build with `python __graft_entry__.py`"
+    declared = S.decls(s.header)
+    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
+    for name in declared:
+        assert hasattr(shipped, name) and hasattr(tuning, name), f"{name} declared in {s.header} but not exported"
+    assert set(s.signatures) == set(declared) - {s.version_fn} - HAND_BOUND.get(s.header, set())
+    for name, args in s.signatures.items():
+        got, want = [S.ckind(t) for t in args], [S.kind(a) for a in declared[name].args]
         assert got == want, f"{name}: binding {got} vs header {want}"
+        got, want = S.ckind(getattr(shipped, name).restype), S.kind(declared[name].ret)
+        assert got == want, f"{name}: binding returns {got}, header {want}"
+    assert declared[s.version_fn] == S.Decl("int", [])
+    getattr(tuning, s.version_fn).restype = ctypes.c_int
+    in_header = S.define(s.header, s.version_fn.upper())                        # mumpy_ext2_version <-> MUMPY_EXT2_VERSION
+    assert in_header == s.version == getattr(shipped, s.version_fn)() == getattr(tuning, s.version_fn)() == VERSIONS[s.header]
+
+
+def test_no_name_lives_in_two_surfaces_and_no_header_is_forgotten():
+    for a, b in itertools.combinations(L.SURFACES, 2):
+        assert not set(S.decls(a.header)) & set(S.decls(b.header)), f"declared in {a.header} and {b.header}"
+        assert not set(a.signatures) & set(b.signatures), f"bound for {a.header} and {b.header}"
+        assert a.version_fn != b.version_fn
+    assert len(L.SIGNATURES) == sum(len(s.signatures) for s in L.SURFACES) and L.ABI_VERSION == L.SURFACES[0].version
+    on_disk = sorted(os.path.basename(p) for p in glob.glob(os.path.join(ROOT, "include", "mumpy_hip*.h")))
+    assert on_disk == sorted(s.header for s in L.SURFACES) == sorted(VERSIONS)
+
+
+def test_version_mismatch_fails_loudly(monkeypatch):
+    """A library whose answer for one header differs from the binding's record is refused by name, with the way out."""
+    stale = L.SURFACES[4]
+    monkeypatch.setattr(L, "_LIB", None)
+    monkeypatch.setattr(L, "SURFACES", [s._replace(version=s.version + 1) if s is stale else s for s in L.SURFACES])
+    with pytest.raises(RuntimeError) as e:
+        L.load_library()
+    msg = str(e.value)
+    assert stale.header in msg and "rebuild" in msg and L.library_path() in msg
+    assert str(stale.version) in msg and str(stale.version + 1) in msg
+    assert L._LIB is None                                                       # nothing half-loaded is kept
 
 
 def test_argument_validation_without_gpu():

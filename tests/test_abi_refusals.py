@@ -24,9 +24,10 @@ import functools
 import json
 import math
 import os
-import re
 import subprocess
 import sys
+
+from abi_surface import arg_names, decls
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "multilateral-temporal-view-pyramid-transformer-for-video-inpainting-detection_amd")
@@ -170,27 +171,22 @@ EXCLUDED = {}            # entry -> reason; at most 8
 LNX_SHAPES = [(1960, 768, 768), (2000, 1024, 1024), (7840, 512, 512), (7840, 512, 2048)]
 
 
-def _decls():
-    src = open(os.path.join(ROOT, "include", "mumpy_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(?:int64_t|int|const char\*)\s+(mumpy_\w+)\s*\(([^)]*)\)\s*;", src):
-        args = [a.strip() for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        out[m.group(1)] = [(a.replace("*", " ").split()[-1], "*" in a) for a in args]          # (name, is pointer)
-    return out
+def _params():
+    """-> {entry of include/mumpy_hip.h: [(argument name, is pointer)]}"""
+    return {n: [(name, "*" in a) for name, a in zip(arg_names(d.args), d.args)] for n, d in decls("mumpy_hip.h").items()}
 
 
 def stream_entries():
-    return sorted(n for n, a in _decls().items() if a and a[-1] == ("stream", True))
+    return sorted(n for n, a in _params().items() if a and a[-1] == ("stream", True))
 
 
 # ------------------------------------------------------------------------------------------------------------ the child
 def _probes(lib):
     """-> [(entry, mutation, expectation, argument list)] for every table entry; expectation in {"pos", "neg", "nonpos"}."""
-    decls = _decls()
+    declared = _params()
     keep, probes = [], []
     for entry, spec in TABLE.items():
-        params = decls[entry][:-1]                                        # (the stream stays NULL)
+        params = declared[entry][:-1]                                     # (the stream stays NULL)
         v = dict(spec["v"])
         if entry == "mumpy_linear_lnx_fwd":
             m, n, k = next(s for s in LNX_SHAPES if lib.mumpy_linear_ln_tiles(*s) > 0)

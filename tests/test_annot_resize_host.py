@@ -5,18 +5,15 @@ include/mumpy_hip_ext6.h).
     on downscales from 1.07 x to 8.6 x, upscales, the identity, ragged and per-axis different ratios, for random bytes, a sparse
     0 / 255 mask (every byte at a mask edge) and a block of a single small value (the rounding around 0 that `> 0` then sees);
   * the taps stay inside the source, fit their table, and their fixed-point weights sum to 1 within one unit per tap;
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers; version 1 everywhere;
+  * the header declares exactly the entry and its version function, with the pinned argument names and limits;
   * every refusal named in the header, with nothing launched (sign convention of tests/test_abi_refusals.py: needs no GPU and must
     not run where one is visible; tests/test_annot_resize.py runs the same table against real buffers)."""
-import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, have_gpu
-from test_augment_host import _ckind, _decls, _kind
+from abi_surface import define, names_of
+from conftest import have_gpu
 
 EINVAL, EALIGN, ENULL, ERANGE = -1, -2, -3, -4
 ENTRY = "mumpy_resize_bilinear_u8_fwd"
@@ -98,29 +95,12 @@ def test_the_kernels_cap_covers_4320_pixel_sources():
             V().bilinear_taps(*bad)
 
 
-# ------------------------------------------------------------------------------------------------ header, binding, exports
-def test_ext6_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext6 = _decls("mumpy_hip_ext6.h")
-    older = [_decls(h) for h in ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h", "mumpy_hip_ext3.h", "mumpy_hip_ext4.h",
-                                 "mumpy_hip_ext5.h")]
-    assert set(ext6) == {ENTRY, "mumpy_ext6_version"}
-    for o in older:
-        assert not set(ext6) & set(o)                               # no name lives in two headers
-    assert set(L.EXT6_SIGNATURES) == set(ext6) - {"mumpy_ext6_version"}
-    assert not set(L.EXT6_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES) | set(L.EXT2_SIGNATURES) | set(L.EXT3_SIGNATURES)
-                                         | set(L.EXT4_SIGNATURES) | set(L.EXT5_SIGNATURES))
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT6_SIGNATURES.items():
-        assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext6[name]] == ARGS, name
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext6[name]], name
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext6.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT6_VERSION\s+1\b", header)
-    assert re.search(rf"#define\s+MUMPY_RESIZE_KMAX_CAP\s+{KMAX_CAP}\b", header)
-    assert re.search(rf"#define\s+MUMPY_RESIZE_BAND_BYTES\s+{BAND_BYTES}\b", header)
-    tuning.mumpy_ext6_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext6_version() == tuning.mumpy_ext6_version() == L.EXT6_VERSION == 1
+# ------------------------------------------------------------------------------------------------ the header's pinned names and limits
+def test_ext6_header_declares_exactly_the_pinned_names_and_limits():
+    """(tests/test_abi.py holds the header to its binding and to both libraries.)"""
+    assert names_of("mumpy_hip_ext6.h") == {ENTRY: ARGS, "mumpy_ext6_version": []}
+    assert define("mumpy_hip_ext6.h", "MUMPY_RESIZE_KMAX_CAP") == KMAX_CAP
+    assert define("mumpy_hip_ext6.h", "MUMPY_RESIZE_BAND_BYTES") == BAND_BYTES
 
 
 # ------------------------------------------------------------------------------------------------ refusals

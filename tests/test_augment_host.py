@@ -7,19 +7,19 @@
     (tests/golden/augment.npz, written by tests/golden/gen_augment_goldens.py);
   * the samplers follow the reference's distributions (5 standard deviations of the binomial over 70,000 seeded draws) and the box
     contract;
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers;
+  * the header declares the entry with the pinned argument names;
   * every refusal of mumpy_augment_stage_u8_fwd, with nothing launched (sign convention of tests/test_abi_refusals.py; needs no GPU and
     must not run where one is visible)."""
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
 from PIL import Image, ImageOps
 
-from conftest import GOLDEN, ROOT, have_gpu
+from abi_surface import names_of
+from conftest import GOLDEN, have_gpu
 
 ENTRY = "mumpy_augment_stage_u8_fwd"
 EINVAL, EALIGN, ENULL, ERANGE = -1, -2, -3, -4
@@ -188,47 +188,13 @@ def test_double_strategy_is_refused_whole_and_runs_restricted_to_the_crops():
     assert seen == set(A().OPS) - {"rot270+tb"}
 
 
-# ------------------------------------------------------------------------------------------------ header, binding, exports
-def _decls(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(?:int64_t|int|const char\*)\s+(mumpy_\w+)\s*\(([^)]*)\)\s*;", src):
-        out[m.group(1)] = [a.strip() for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-    return out
-
-
-def _kind(carg):
-    if "*" in carg:
-        return "ptr"
-    return {"int": "int", "int64_t": "i64", "float": "f32", "double": "f64"}[carg.rsplit(None, 1)[0].replace("const ", "").strip()]
-
-
-def _ckind(t):
-    if t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-        return "ptr"
-    return {ctypes.c_int: "int", ctypes.c_int64: "i64", ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
-
-
-def test_ext3_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext3 = _decls("mumpy_hip_ext3.h")
-    older = [_decls(h) for h in ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h")]
-    assert {ENTRY, "mumpy_ext3_version"} <= set(ext3)
-    for o in older:
-        assert not set(ext3) & set(o)                               # no name lives in two headers
-    assert set(L.EXT3_SIGNATURES) == set(ext3) - {"mumpy_ext3_version"}
-    assert not set(L.EXT3_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES) | set(L.EXT2_SIGNATURES))
-    assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext3[ENTRY]] == [
-        "frames", "masks", "out", "target", "tab_a", "tab_b", "swap", "nclips", "T", "nmasks", "Hs", "Ws", "L", "mean3", "std3", "stream"]
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT3_SIGNATURES.items():
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext3[name]], name
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext3.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT3_VERSION\s+1\b", header)
-    tuning.mumpy_ext3_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext3_version() == tuning.mumpy_ext3_version() == L.EXT3_VERSION == 1
+# ------------------------------------------------------------------------------------------------ the header's pinned names
+def test_ext3_header_declares_the_pinned_argument_names():
+    """(tests/test_abi.py holds the header to its binding and to both libraries.)"""
+    ext3 = names_of("mumpy_hip_ext3.h")
+    assert "mumpy_ext3_version" in ext3
+    assert ext3[ENTRY] == ["frames", "masks", "out", "target", "tab_a", "tab_b", "swap", "nclips", "T", "nmasks", "Hs", "Ws", "L", "mean3",
+                           "std3", "stream"]
 
 
 # ------------------------------------------------------------------------------------------------ refusals, without a GPU

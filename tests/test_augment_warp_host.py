@@ -7,20 +7,19 @@ include/mumpy_hip_ext4.h).
     fed with scale_crop_params reproduces every output recorded from the reference's own RandomScaleCrop
     (tests/golden/augment_warp.npz, written by tests/golden/gen_augment_warp_goldens.py): frames, mask and box;
   * corner_crop_box keeps the reference's bounds; sample_double_full follows its distribution; rotate_params at angle 0 and its range;
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers;
+  * the header declares exactly the entry and its version function, with the pinned argument names;
   * every refusal of mumpy_augment_warp_u8_fwd, with nothing launched (sign convention of tests/test_abi_refusals.py; needs no GPU and
     must not run where one is visible)."""
 import ctypes
 import functools
 import os
-import re
 
 import numpy as np
 import pytest
 from PIL import Image
 
-from conftest import GOLDEN, ROOT, have_gpu
-from test_augment_host import _ckind, _decls, _kind
+from abi_surface import names_of
+from conftest import GOLDEN, have_gpu
 
 ENTRY = "mumpy_augment_warp_u8_fwd"
 EINVAL, EALIGN, ENULL, ERANGE = -1, -2, -3, -4
@@ -258,27 +257,12 @@ def test_rotate_params_identity_range_and_crop():
     assert np.allclose(m @ [14, 14, 1], [14, 14], atol=1e-5) and np.allclose(m @ [15, 14, 1], [14, 15], atol=1e-5)
 
 
-# ------------------------------------------------------------------------------------------------ header, binding, exports
-def test_ext4_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext4 = _decls("mumpy_hip_ext4.h")
-    older = [_decls(h) for h in ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h", "mumpy_hip_ext3.h")]
-    assert set(ext4) == {ENTRY, "mumpy_ext4_version"}
-    for o in older:
-        assert not set(ext4) & set(o)                               # no name lives in two headers
-    assert set(L.EXT4_SIGNATURES) == set(ext4) - {"mumpy_ext4_version"}
-    assert not set(L.EXT4_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES) | set(L.EXT2_SIGNATURES) | set(L.EXT3_SIGNATURES))
-    assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext4[ENTRY]] == [
+# ------------------------------------------------------------------------------------------------ the header's pinned names
+def test_ext4_header_declares_exactly_the_pinned_names():
+    """(tests/test_abi.py holds the header to its binding and to both libraries.)"""
+    assert names_of("mumpy_hip_ext4.h") == {"mumpy_ext4_version": [], ENTRY: [
         "frames", "masks", "out", "target", "tab_a", "tab_b", "swap", "mode", "pos_y", "pos_x", "coef_y", "coef_x", "affine", "nclips",
-        "T", "nmasks", "Hs", "Ws", "L", "mean3", "std3", "stream"]
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT4_SIGNATURES.items():
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext4[name]], name
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext4.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT4_VERSION\s+1\b", header)
-    tuning.mumpy_ext4_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext4_version() == tuning.mumpy_ext4_version() == L.EXT4_VERSION == 1
+        "T", "nmasks", "Hs", "Ws", "L", "mean3", "std3", "stream"]}
 
 
 # ------------------------------------------------------------------------------------------------ refusals, without a GPU

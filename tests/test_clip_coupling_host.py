@@ -2,15 +2,13 @@
 
   * ops.cva_pairing, the host statement of the kernels' index rule, against a torch statement of the reference applied clip by clip:
     an index tensor sent through `.repeat(r)` (deform:330) and the `(b t) -> b t` regrouping whose t axis is summed (deform:394-395);
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers; version 1 everywhere;
+  * the header declares exactly the pinned names, each grouped entry its frozen sibling's arguments plus `int groups`;
   * every grouped entry refuses null pointers and a bad grouping with a negative code, nothing launched (the calls made here are
     refusals only, so the test is safe with or without a device);
   * the switch: values, the environment variable in a fresh process, the context manager, the constructors' refusals;
   * the oracle on the input the GPU tests use: the batch-coupled forward is far from the per-clip one (the input discriminates)."""
-import ctypes
 import itertools
 import os
-import re
 import subprocess
 import sys
 
@@ -18,8 +16,8 @@ import numpy as np
 import pytest
 import torch
 
+from abi_surface import decls, kind, names_of
 from conftest import PKG, ROOT, rel_err, rms_err
-from test_augment_host import _ckind, _decls, _kind
 
 EINVAL, ENULL = -1, -3
 SAMPLE = ["x2", "pos", "out", "B", "Hs2", "W", "C", "nq", "groups", "stream"]
@@ -33,8 +31,6 @@ ARGS = {
     "mumpy_deform_attention_mm16_grouped_fwd": CORE,
 }
 FROZEN = {name: name.replace("_grouped", "") for name in ARGS}
-OLDER = ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h", "mumpy_hip_ext3.h", "mumpy_hip_ext4.h", "mumpy_hip_ext5.h",
-         "mumpy_hip_ext6.h", "mumpy_hip_ext7.h")
 
 
 def _ops():
@@ -89,30 +85,16 @@ def test_cva_pairing_intermediate_groups_and_refusals():
             ops.cva_pairing(nkv, nq, g)
 
 
-# ------------------------------------------------------------------------------------------------ header, binding, exports
-def test_ext8_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext8 = _decls("mumpy_hip_ext8.h")
-    assert set(ext8) == set(ARGS) | {"mumpy_ext8_version"}
-    for h in OLDER:
-        assert not set(ext8) & set(_decls(h)), h                          # no name lives in two headers
-    assert set(L.EXT8_SIGNATURES) == set(ARGS)
-    assert not set(L.EXT8_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES) | set(L.EXT2_SIGNATURES) | set(L.EXT3_SIGNATURES)
-                                         | set(L.EXT4_SIGNATURES) | set(L.EXT5_SIGNATURES) | set(L.EXT6_SIGNATURES)
-                                         | set(L.EXT7_SIGNATURES))
-    frozen = _decls("mumpy_hip.h")
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT8_SIGNATURES.items():
-        assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext8[name]] == ARGS[name], name
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext8[name]], name
-        sib = frozen[FROZEN[name]]                                         # the sibling's arguments + `int groups` before the stream
-        assert [_kind(a) for a in ext8[name]] == [_kind(a) for a in sib[:-1]] + ["int", "ptr"], name
-        assert ext8[name][-2] == "int groups"
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext8.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT8_VERSION\s+1\b", header)
-    tuning.mumpy_ext8_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext8_version() == tuning.mumpy_ext8_version() == L.EXT8_VERSION == 1
+# ------------------------------------------------------------------------------------------------ the header's pinned names
+def test_ext8_grouped_entries_are_their_frozen_siblings_plus_groups():
+    """Exactly the pinned names, and each grouped entry takes its frozen sibling's arguments plus `int groups` before the stream
+    (tests/test_abi.py holds the header to its binding and to both libraries)."""
+    assert names_of("mumpy_hip_ext8.h") == dict(ARGS, mumpy_ext8_version=[])
+    ext8, frozen = decls("mumpy_hip_ext8.h"), decls("mumpy_hip.h")
+    for name in ARGS:
+        sib = frozen[FROZEN[name]].args
+        assert [kind(a) for a in ext8[name].args] == [kind(a) for a in sib[:-1]] + ["int", "ptr"], name
+        assert ext8[name].args[-2] == "int groups"
 
 
 # ------------------------------------------------------------------------------------------------ refusals through the C ABI

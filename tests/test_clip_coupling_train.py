@@ -240,6 +240,38 @@ def test_module_tape_matches_the_per_clip_oracle(b, nqc, r, c):
     assert all(v > 0.1 for v in miss.values()), miss
 
 
+def test_module_tape_at_one_group_launches_the_frozen_entries_and_keeps_its_refusal():
+    """The other half of the launch-name assertion above: swin_dattention_train(groups=1) runs the four frozen entries and none of
+    the grouped ones.  Under ops.set_clip_coupling("clip") the same call is refused when it reaches the first of the two Functions
+    (proj_q and the offset network, which pair nothing, have run by then): no cross-view entry, frozen or grouped, is launched, and
+    each Function called directly with groups = 1 is refused before anything at all is recorded."""
+    from mumpy_hip.autograd import DeformAttentionFn, DeformSampleFn
+    ops = _ops()
+    b, nqc, r, c = 2, 1, 3, 96
+    frozen = {"mumpy_deform_sample_fwd", "mumpy_deform_attention_fwd", "mumpy_deform_sample_bwd", "mumpy_deform_attention_bwd"}
+    s, a = ({k: v.to(DEV) for k, v in _inputs(e, b, nqc, r, c).items()} for e in ("sample", "attention"))
+    assert (ops.cva_math(), ops.clip_coupling()) == ("fp32", "batch")
+    was, ops.PROFILE = ops.PROFILE, {}
+    try:
+        _module_run(b, nqc, r, c, 1)
+        names = set(ops.PROFILE)
+        ops.PROFILE = {}
+        with ops.clip_coupling_as("clip"):
+            for call in (lambda: DeformSampleFn.apply(s["x2"], s["pos"], 1), lambda: DeformAttentionFn.apply(a["q"], a["kv"], SCALE, 1)):
+                with pytest.raises(RuntimeError, match="set_clip_coupling"):
+                    call()
+                assert ops.PROFILE == {}
+            with pytest.raises(RuntimeError, match="set_clip_coupling"):
+                _module_run(b, nqc, r, c, 1)
+        refused = set(ops.PROFILE)
+    finally:
+        ops.PROFILE = was
+    torch.cuda.synchronize()
+    assert frozen <= names and not names & {n.replace("_fwd", "_grouped_fwd").replace("_bwd", "_grouped_bwd") for n in frozen}
+    assert not any("deform_sample" in n or "deform_attention" in n for n in refused), sorted(refused)
+    assert ops.clip_coupling() == "batch"
+
+
 def test_module_tape_carries_bf16_to_the_grouped_backward():
     """Forward under ops.set_cva_math("bf16"), the switch set back BEFORE the backward: ctx.math and ctx.groups reach
     ops.deform_attention_bwd, and what it returns for the batch is, bit for bit, the frozen bf16 op on each clip's slice of the very

@@ -1,22 +1,17 @@
 """CPU only: the host half of training with per-clip cross-view pairing (include/mumpy_hip_ext9.h, ops.cva_pairing_members, the
 groups= argument of ops.deform_sample_bwd / ops.deform_attention_bwd, encoder_train(coupling=)).
 
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers; version 1 everywhere;
+  * the header declares exactly the pinned names, each grouped entry its frozen sibling's arguments plus `int groups`;
   * every grouped backward entry refuses null pointers and a bad grouping with a negative code, nothing launched (the calls made
     here are refusals only, so the test is safe with or without a device);
   * the backward ops refuse a bad groups before they look at a tensor;
   * ops.cva_pairing_members, the inverse the bf16 q kernel walks, against ops.cva_pairing;
   * encoder_train: an unknown coupling is a ValueError, and the default call still refuses the global "clip" setting."""
-import ctypes
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT
-from test_augment_host import _ckind, _decls, _kind
+from abi_surface import decls, kind, names_of
 
 EINVAL, ENULL = -1, -3
 SAMPLE = ["x2", "pos", "dsampled", "dx2", "dpos_part", "B2", "C", "nq", "groups", "stream"]
@@ -27,8 +22,6 @@ ARGS = {
     "mumpy_deform_attention_mm16_grouped_bwd": [a if a != "dq_part" else "dq" for a in CORE],
 }
 FROZEN = {name: (name.replace("_grouped", ""), "mumpy_hip_ext2.h" if "mm16" in name else "mumpy_hip.h") for name in ARGS}
-OLDER = ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h", "mumpy_hip_ext3.h", "mumpy_hip_ext4.h", "mumpy_hip_ext5.h",
-         "mumpy_hip_ext6.h", "mumpy_hip_ext7.h", "mumpy_hip_ext8.h")
 
 
 def _ops():
@@ -36,30 +29,17 @@ def _ops():
     return ops
 
 
-# ------------------------------------------------------------------------------------------------ header, binding, exports
-def test_ext9_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext9 = _decls("mumpy_hip_ext9.h")
-    assert set(ext9) == set(ARGS) | {"mumpy_ext9_version"}
-    for h in OLDER:
-        assert not set(ext9) & set(_decls(h)), h                          # no name lives in two headers
-    assert set(L.EXT9_SIGNATURES) == set(ARGS)
-    assert not set(L.EXT9_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES) | set(L.EXT2_SIGNATURES) | set(L.EXT3_SIGNATURES)
-                                         | set(L.EXT4_SIGNATURES) | set(L.EXT5_SIGNATURES) | set(L.EXT6_SIGNATURES)
-                                         | set(L.EXT7_SIGNATURES) | set(L.EXT8_SIGNATURES))
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT9_SIGNATURES.items():
-        assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext9[name]] == ARGS[name], name
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext9[name]], name
+# ------------------------------------------------------------------------------------------------ the header's pinned names
+def test_ext9_grouped_entries_are_their_frozen_siblings_plus_groups():
+    """Exactly the pinned names, and each grouped entry takes its frozen sibling's arguments plus `int groups` before the stream
+    (tests/test_abi.py holds the header to its binding and to both libraries)."""
+    assert names_of("mumpy_hip_ext9.h") == dict(ARGS, mumpy_ext9_version=[])
+    ext9 = decls("mumpy_hip_ext9.h")
+    for name in ARGS:
         sib_name, sib_header = FROZEN[name]
-        sib = _decls(sib_header)[sib_name]                                 # the sibling's arguments + `int groups` before the stream
-        assert [_kind(a) for a in ext9[name]] == [_kind(a) for a in sib[:-1]] + ["int", "ptr"], name
-        assert ext9[name][-2] == "int groups"
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext9.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT9_VERSION\s+1\b", header)
-    tuning.mumpy_ext9_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext9_version() == tuning.mumpy_ext9_version() == L.EXT9_VERSION == 1
+        sib = decls(sib_header)[sib_name].args
+        assert [kind(a) for a in ext9[name].args] == [kind(a) for a in sib[:-1]] + ["int", "ptr"], name
+        assert ext9[name].args[-2] == "int groups"
 
 
 # ------------------------------------------------------------------------------------------------ refusals through the C ABI

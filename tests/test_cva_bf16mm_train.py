@@ -9,17 +9,14 @@ dO of output window b2 // r:
   dV = r(P)^T r(dO), dK = scale r(dS)^T r(q), dQ[qw] = sum over m = 0 .. r-1 of scale r(dS_b2) r(k_b2), b2 = qw + m B1.
 Each output differs from the exact result of the rounded operands by ONE bf16 rounding (unit roundoff 2^-8) of the accumulator operand
 (P resp. dS), plus fp32 effects; the fp32 effects are measured on the existing fp32 kernels."""
-import ctypes
 import functools
 import inspect
-import os
-import re
 
 import pytest
 import torch
 
 import guarded_alloc as GA
-from conftest import ROOT, rel_err
+from conftest import rel_err
 from weight_fill import fill_module_, seeded_randn
 
 gpu = pytest.mark.gpu
@@ -40,47 +37,10 @@ if torch.cuda.is_available():
 
 
 # ------------------------------------------------------------------ CPU: header, binding and validation
-def _decls(header):
-    src = open(os.path.join(ROOT, "include", header)).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    out = {}
-    for m in re.finditer(r"\b(?:int64_t|int|const char\*)\s+(mumpy_\w+)\s*\(([^)]*)\)\s*;", src):
-        out[m.group(1)] = [a.strip() for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-    return out
-
-
-def _kind(carg):
-    if "*" in carg:
-        return "ptr"
-    return {"int": "int", "int64_t": "i64", "float": "f32", "double": "f64"}[carg.rsplit(None, 1)[0].replace("const ", "").strip()]
-
-
-def _ckind(t):
-    if t is ctypes.c_void_p or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
-        return "ptr"
-    return {ctypes.c_int: "int", ctypes.c_int64: "i64", ctypes.c_float: "f32", ctypes.c_double: "f64"}[t]
-
-
-def test_ext2_header_binding_and_exports_agree():
-    """Every declaration of mumpy_hip_ext2.h is exported by the shipped and the tuning library and bound in EXT2_SIGNATURES with the
-    arity and the argument kinds of its C declaration; nothing is bound that the header lacks; no name lives in two headers; the two
-    frozen surfaces keep their versions.  Neither the set of names nor the header's own version is pinned: the header grows."""
-    from mumpy_hip import lib as L
-    ext2, ext, old = _decls("mumpy_hip_ext2.h"), _decls("mumpy_hip_ext.h"), _decls("mumpy_hip.h")
-    assert {BWD, WSQ, "mumpy_ext2_version"} <= set(ext2)
-    assert not set(ext2) & (set(ext) | set(old))
-    assert not set(L.EXT2_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES))
-    assert set(L.EXT2_SIGNATURES) == set(ext2) - {"mumpy_ext2_version"}
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name in ext2:
-        assert hasattr(shipped, name) and hasattr(tuning, name), f"{name} declared in the header but not exported"
-    for name, args in L.EXT2_SIGNATURES.items():
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext2[name]], name
-    tuning.mumpy_ext2_version.restype = ctypes.c_int
-    tuning.mumpy_ext_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext2_version() == tuning.mumpy_ext2_version() == L.EXT2_VERSION
-    assert shipped.mumpy_abi_version() == L.ABI_VERSION == 2
-    assert shipped.mumpy_ext_version() == tuning.mumpy_ext_version() == L.EXT_VERSION == 1
+def test_ext2_header_declares_the_backward_and_its_query():
+    """(tests/test_abi.py holds mumpy_hip_ext2.h to its binding and to both libraries.)"""
+    from abi_surface import decls
+    assert {BWD, WSQ, "mumpy_ext2_version"} <= set(decls("mumpy_hip_ext2.h"))
 
 
 def test_refusals_need_no_gpu():

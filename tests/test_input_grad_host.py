@@ -1,22 +1,19 @@
 """CPU only: the host half of the input-clip gradient (include/mumpy_hip_ext10.h, mumpy_hip.inputgrad, encoder_train(input_grad=)).
 
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers; version 1 everywhere;
+  * the header declares exactly the pinned names; the error codes are the frozen header's;
   * every new entry refuses null, misaligned and out-of-range arguments with its code, nothing launched (the calls made here are
     refusals only, so the test is safe with or without a device);
   * faf_bwd_reference against autograd of the oracle's faf_frame1; tokenize_dx_reference against autograd of F.conv3d with the three
     strides; pgd_bounds; the new refusal of encoder_train and the unchanged old ones."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
-from conftest import ROOT
+from abi_surface import define, names_of
 from oracle import mumpy_oracle as O
-from test_augment_host import _ckind, _decls, _kind
 from weight_fill import seeded_randn
 
 TIGHT = 5e-5
@@ -27,8 +24,6 @@ ARGS = {
                           "stream"],
     "mumpy_pgd_step": ["x_adv", "g", "x0", "n", "hw", "alpha", "eps3", "lo3", "hi3", "stream"],
 }
-OLDER = ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h", "mumpy_hip_ext3.h", "mumpy_hip_ext4.h", "mumpy_hip_ext5.h",
-         "mumpy_hip_ext6.h", "mumpy_hip_ext7.h", "mumpy_hip_ext8.h", "mumpy_hip_ext9.h")
 
 
 def rel_err(a, b):
@@ -42,30 +37,13 @@ def tubelets_of(t):
 
 # ------------------------------------------------------------------------------------------------ header, binding, exports
 def test_error_codes_are_the_headers():
-    header = open(os.path.join(ROOT, "include", "mumpy_hip.h")).read()
     for name, code in (("MUMPY_EINVAL", EINVAL), ("MUMPY_EALIGN", EALIGN), ("MUMPY_ENULL", ENULL)):
-        assert re.search(rf"#define\s+{name}\s+\(?{code}\)?", header), name
+        assert define("mumpy_hip.h", name) == code, name
 
 
-def test_ext10_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext10 = _decls("mumpy_hip_ext10.h")
-    assert set(ext10) == set(ARGS) | {"mumpy_ext10_version"}
-    for h in OLDER:
-        assert not set(ext10) & set(_decls(h)), h                         # no name lives in two headers
-    assert set(L.EXT10_SIGNATURES) == set(ARGS)
-    older = [L.SIGNATURES, L.EXT_SIGNATURES, L.EXT2_SIGNATURES, L.EXT3_SIGNATURES, L.EXT4_SIGNATURES, L.EXT5_SIGNATURES,
-             L.EXT6_SIGNATURES, L.EXT7_SIGNATURES, L.EXT8_SIGNATURES, L.EXT9_SIGNATURES]
-    assert not any(set(L.EXT10_SIGNATURES) & set(t) for t in older)
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT10_SIGNATURES.items():
-        assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext10[name]] == ARGS[name], name
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext10[name]], name
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext10.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT10_VERSION\s+1\b", header)
-    tuning.mumpy_ext10_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext10_version() == tuning.mumpy_ext10_version() == L.EXT10_VERSION == 1
+def test_ext10_header_declares_exactly_the_pinned_names():
+    """(tests/test_abi.py holds the header to its binding and to both libraries.)"""
+    assert names_of("mumpy_hip_ext10.h") == dict(ARGS, mumpy_ext10_version=[])
 
 
 # ------------------------------------------------------------------------------------------------ refusals through the C ABI

@@ -7,15 +7,12 @@ mumpy_hip/evaluate.py::finalize_sweep, include/mumpy_hip_ext7.h).
   * exceed_counts at every k is {inter, sum p, sum g, union} of thresholding the probabilities directly;
   * sweep_table: the default values bitwise, every refusal;
   * finalize_sweep: the means, the tie rule of `best`, an AUC of exactly 1.0, 0.5 and 0.0, nan with an empty class;
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers; version 1 everywhere;
+  * the header declares exactly the two entries and its version function, with the pinned argument names and limit;
   * every refusal named in the header, with nothing launched (sign convention of tests/test_abi_refusals.py: needs no GPU and must
     not run where one is visible; tests/test_threshold_sweep.py runs the same table against real buffers);
   * the two ops wrappers under tests/handoff_audit.py's recorder: a valid call hands exactly the buffers given, a shorter exceed, a
     wrong dtype and a non-contiguous in-place buffer are refused before the first launch;
   * VideoPredictor(sweep=...) refuses a bad table before it looks for a device."""
-import ctypes
-import os
-import re
 import types
 
 import numpy as np
@@ -24,8 +21,8 @@ import torch
 
 import handoff_audit as HA
 import test_video_host as TVH
-from conftest import ROOT, have_gpu
-from test_augment_host import _ckind, _decls, _kind
+from abi_surface import define, names_of
+from conftest import have_gpu
 from test_video_host import metrics_reference, sweep_refusals
 
 EINVAL, EALIGN, ENULL, ERANGE = -1, -2, -3, -4
@@ -202,28 +199,11 @@ def test_finalize_sweep_auc_exact_cases():
     assert abs(auc([6, 2, 0], [4, 2, 1]) - (0.25 + 0.375 + 0.09375)) < 1e-15
 
 
-# ------------------------------------------------------------------------------------------------ header, binding, exports
-def test_ext7_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext7 = _decls("mumpy_hip_ext7.h")
-    older = [_decls(h) for h in ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h", "mumpy_hip_ext3.h", "mumpy_hip_ext4.h",
-                                 "mumpy_hip_ext5.h", "mumpy_hip_ext6.h")]
-    assert set(ext7) == set(ARGS) | {"mumpy_ext7_version"}
-    for o in older:
-        assert not set(ext7) & set(o)                               # no name lives in two headers
-    assert set(L.EXT7_SIGNATURES) == set(ext7) - {"mumpy_ext7_version"}
-    assert not set(L.EXT7_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES) | set(L.EXT2_SIGNATURES) | set(L.EXT3_SIGNATURES)
-                                         | set(L.EXT4_SIGNATURES) | set(L.EXT5_SIGNATURES) | set(L.EXT6_SIGNATURES))
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT7_SIGNATURES.items():
-        assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext7[name]] == ARGS[name], name
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext7[name]], name
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext7.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT7_VERSION\s+1\b", header)
-    assert re.search(rf"#define\s+MUMPY_SWEEP_MAX_THRESHOLDS\s+{KMAX}\b", header)
-    tuning.mumpy_ext7_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext7_version() == tuning.mumpy_ext7_version() == L.EXT7_VERSION == 1
+# ------------------------------------------------------------------------------------------------ the header's pinned names and limit
+def test_ext7_header_declares_exactly_the_pinned_names_and_limit():
+    """(tests/test_abi.py holds the header to its binding and to both libraries.)"""
+    assert names_of("mumpy_hip_ext7.h") == dict(ARGS, mumpy_ext7_version=[])
+    assert define("mumpy_hip_ext7.h", "MUMPY_SWEEP_MAX_THRESHOLDS") == KMAX
     from mumpy_hip import ops
     assert ops.SWEEP_MAX_THRESHOLDS == V().SWEEP_MAX_THRESHOLDS == KMAX
 

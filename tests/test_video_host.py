@@ -2,21 +2,19 @@
 
   * clip_frame_indices is the comprehension of the reference's loader (dataloaders/universaldataloader.py:41-46), its centre column is
     the frame itself, an even T is refused; batch_plan pads the tail with valid clips whose dest is -1;
-  * header, binding and the two libraries' exports agree; no name is shared with the older headers; version 1 everywhere;
+  * the header declares exactly the three entries and its version function, with the pinned argument names;
   * `window_reference`, `score_reference` and `metrics_reference`, the numpy statements of the three kernels written here from
     universaldataset.py:75-79 (PIL NEAREST) + test.py:22-25, test.py:100-111 and measure.py:57-62, 86-89 (tests/test_video_stage.py
     holds the kernels to them), checked on hand-made cases;
   * every refusal named in the header, with nothing launched (sign convention of tests/test_abi_refusals.py: needs no GPU and must
     not run where one is visible; tests/test_video_stage.py runs the same table against real buffers)."""
 import ctypes
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, have_gpu
-from test_augment_host import _ckind, _decls, _kind
+from abi_surface import names_of
+from conftest import have_gpu
 
 EINVAL, EALIGN, ENULL, ERANGE = -1, -2, -3, -4
 EVAL_MEAN, EVAL_STD = (0.4776, 0.479, 0.4465), (0.230, 0.2085, 0.2324)      # test.py:23-24
@@ -184,26 +182,10 @@ def test_metrics_reference_is_eval_metric_vector():
     assert np.allclose(got, want, rtol=1e-14, atol=0) and got[2] == 6
 
 
-# ------------------------------------------------------------------------------------------------ header, binding, exports
-def test_ext5_header_binding_and_exports_agree():
-    from mumpy_hip import lib as L
-    ext5 = _decls("mumpy_hip_ext5.h")
-    older = [_decls(h) for h in ("mumpy_hip.h", "mumpy_hip_ext.h", "mumpy_hip_ext2.h", "mumpy_hip_ext3.h", "mumpy_hip_ext4.h")]
-    assert set(ext5) == set(ARGS) | {"mumpy_ext5_version"}
-    for o in older:
-        assert not set(ext5) & set(o)                               # no name lives in two headers
-    assert set(L.EXT5_SIGNATURES) == set(ext5) - {"mumpy_ext5_version"}
-    assert not set(L.EXT5_SIGNATURES) & (set(L.SIGNATURES) | set(L.EXT_SIGNATURES) | set(L.EXT2_SIGNATURES) | set(L.EXT3_SIGNATURES)
-                                         | set(L.EXT4_SIGNATURES))
-    shipped, tuning = L.load_library(), ctypes.CDLL(L.tuning_library_path())
-    for name, args in L.EXT5_SIGNATURES.items():
-        assert [a.rsplit(None, 1)[-1].lstrip("*") for a in ext5[name]] == ARGS[name], name
-        assert hasattr(shipped, name) and hasattr(tuning, name), name
-        assert [_ckind(t) for t in args] == [_kind(a) for a in ext5[name]], name
-    header = open(os.path.join(ROOT, "include", "mumpy_hip_ext5.h")).read()
-    assert re.search(r"#define\s+MUMPY_EXT5_VERSION\s+1\b", header)
-    tuning.mumpy_ext5_version.restype = ctypes.c_int
-    assert shipped.mumpy_ext5_version() == tuning.mumpy_ext5_version() == L.EXT5_VERSION == 1
+# ------------------------------------------------------------------------------------------------ the header's pinned names
+def test_ext5_header_declares_exactly_the_pinned_names():
+    """(tests/test_abi.py holds the header to its binding and to both libraries.)"""
+    assert names_of("mumpy_hip_ext5.h") == dict(ARGS, mumpy_ext5_version=[])
 
 
 # ------------------------------------------------------------------------------------------------ refusals
