@@ -399,9 +399,18 @@ class AugmentedInput:
     only wait is the host's, for the upload issued two loads earlier from the same staging set -- long finished in a training loop.
     The tables live in device memory, so a captured launch (`launch()`) replays with the parameters uploaded last.
     warp=True: the launch is ops.augment_warp_u8, the parameter block holds every array of that call (still one upload), and a clip's
-    entry of params is either such a triple (a gather) or the WarpParams of clip_warp_params."""
+    entry of params is either such a triple (a gather) or the WarpParams of clip_warp_params.
+    perturb=True: ordinary post-processing as an augmentation (mumpy_hip.perturb; the reference's JPEGCompression and
+    RandomGaussianBlur act on the frame after its first img.resize(inputRes), universaldataset.py:67).  The object additionally owns
+    the canvas (B, T, L, L, 3) uint8 and the mask canvas (nmasks, L, L), one quantisation-table pair per clip, the per-frame table
+    choice and box rows -- all in the one parameter block, still one upload -- and the kernels' workspace; launch() becomes
+    ops.resize_nearest_u8 source -> canvas (frames and masks), ops.jpeg_roundtrip_u8 and ops.gaussian_blur_u8 in place on the canvas,
+    then the stage above reading the canvas: all of it capturable.  The per-clip tables are then CANVAS-relative --
+    clip_tables((L, L), L, op, box), clip_warp_params((L, L), L, draw) -- because the object does the source -> canvas resize itself.
+    load(..., perturb=[None | ("jpeg", q) | ("blur", r) per clip]): all T frames of a clip share the clip's setting; masks are never
+    perturbed.  perturb=False (the default) is the object as it was: the same buffers, the same single launch."""
 
-    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None, warp=False):
+    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None, warp=False, perturb=False):
         import torch
         from . import ops
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5 or x.shape[2] != 3 or x.shape[3] != x.shape[4] or not x.is_contiguous():
@@ -425,6 +434,13 @@ class AugmentedInput:
         shapes = dict(tab_a=(b, L), tab_b=(b, L), pos_y=(b, L), pos_x=(b, L), coef_y=(b, L, 4), coef_x=(b, L, 4), affine=(b, 8), swap=(b,),
                       mode=(b,))
         self._fields = tuple(shapes) if self.warp else ("tab_a", "tab_b", "swap")
+        self.perturb = bool(perturb)
+        if self.perturb:
+            # qtab: (b, 2, 64) uint16 = 64 words per clip; blur: {r, ww, fw, on} per frame; sel: the clip's table or -1 per frame.
+            # qtab and blur are loaded 16 bytes at a time: they go in front of the first one-word-per-clip array
+            shapes.update(qtab=(b, 64), blur=(b * t, 4), sel=(b * t,))
+            at = self._fields.index("swap")
+            self._fields = self._fields[:at] + ("qtab", "blur") + self._fields[at:] + ("sel",)
         self._where, n = {}, 0
         for name in self._fields:
             self._where[name] = (n, n + int(np.prod(shapes[name])), shapes[name])
@@ -437,6 +453,16 @@ class AugmentedInput:
                             masks=torch.empty(self.nmasks, hs, ws, dtype=u8).pin_memory() if target is not None else None,
                             params=torch.empty(n, dtype=i32).pin_memory(), done=torch.cuda.Event()) for _ in range(2)]
         self._turn = 0
+        if self.perturb:
+            self.qtab = self.qtab.view(torch.int16).view(b, 2, 64)         # the bits of the kernel's uint16
+            self.canvas = torch.empty(b, t, L, L, 3, dtype=u8, device=dev)
+            self.mask_canvas = torch.empty(self.nmasks, L, L, dtype=u8, device=dev) if target is not None else None
+            lib = ops._lib()
+            need = [int(lib.mumpy_jpeg_roundtrip_workspace_bytes(b * t, L, L)), int(lib.mumpy_gaussian_blur_workspace_bytes(b * t, L, L))]
+            if min(need) < 0:
+                raise RuntimeError(f"AugmentedInput: a canvas of {L}x{L} is refused: {lib.mumpy_last_error().decode()}")
+            self._perturb_ws = torch.empty(max(need), dtype=u8, device=dev)
+            ops._nearest_table(hs, L, dev), ops._nearest_table(ws, L, dev)  # uploaded here, not inside a capture
 
     def _upload(self, dst, src, pinned, what):
         import torch
@@ -449,9 +475,33 @@ class AugmentedInput:
             pinned.copy_(src)
             dst.copy_(pinned, non_blocking=True)
 
-    def load(self, frames_u8, masks_u8, params):
+    def _perturb_rows(self, perturb):
+        """-> (qtab (b, 64) words, blur (b * T, 4), sel (b * T,)) int32 of one setting per clip (None: the clip passes through)."""
+        from .perturb import box_params, check_spec, jpeg_tables
+        b, t = self.nclips, self.T
+        perturb = [None] * b if perturb is None else list(perturb)
+        if len(perturb) != b:
+            raise ValueError(f"AugmentedInput.load: perturb needs one entry per clip ({b}), got {len(perturb)}")
+        qtab = np.ones((b, 2, 64), np.uint16)
+        blur = np.tile(np.array([0, 1 << 24, 0, 0], np.int64), (b, t, 1))
+        sel = np.full((b, t), -1, np.int32)
+        for c, spec in enumerate(perturb):
+            steps = check_spec(spec, "AugmentedInput.load: perturb")
+            if len(steps) > 1:
+                raise ValueError("AugmentedInput.load: one setting per clip, (\"jpeg\", q) or (\"blur\", r), not a list")
+            for kind, value in steps:
+                if kind == "jpeg":
+                    qtab[c], sel[c] = jpeg_tables(value), c
+                else:
+                    blur[c] = box_params(value)
+        return qtab.reshape(b, 128).view(np.int32), blur.astype(np.int32).reshape(b * t, 4), sel.reshape(b * t)
+
+    def load(self, frames_u8, masks_u8, params, perturb=None):
         import torch
         b, L = self.nclips, self.L
+        if perturb is not None and not self.perturb:
+            raise RuntimeError("AugmentedInput.load: perturb= needs an input built with perturb=True")
+        extra = dict(zip(("qtab", "blur", "sel"), self._perturb_rows(perturb))) if self.perturb else {}
         st = self._stage[self._turn]
         self._turn ^= 1
         st["done"].synchronize()                 # host-side only: the upload of two loads ago has left this staging set
@@ -465,6 +515,7 @@ class AugmentedInput:
                        np.zeros((L, 4), np.int32), np.zeros(8, np.float32))
             rows = [tuple(p) + gather0 if len(p) == 3 and len(fields) != 3 else p for p in params]
             cols = {name: np.stack([np.asarray(r[k]) for r in rows]) for k, name in enumerate(fields)}
+        cols.update(extra)
         ta, tb, sw = cols["tab_a"], cols["tab_b"], cols["swap"]
         if ta.shape != (b, L) or tb.shape != (b, L) or sw.shape != (b,):
             raise RuntimeError(f"AugmentedInput.load: the tables must be ({b}, {L}) and the swap words ({b},), got {ta.shape}, {tb.shape}, {sw.shape}")
@@ -491,9 +542,17 @@ class AugmentedInput:
         """The one kernel launch on the current stream, reading the device-resident parameters (capturable)."""
         from . import ops
         target = None if self.target is None else self.target.view(self.nclips, self.L * self.L)
+        frames, masks = self.frames, self.masks
+        if self.perturb:
+            frames, masks, side = self.canvas, self.mask_canvas, (self.L, self.L)
+            ops.resize_nearest_u8(self.frames, side, out=frames)
+            if masks is not None:
+                ops.resize_nearest_u8(self.masks, side, out=masks, channels=1)
+            ops.jpeg_roundtrip_u8(frames, self.qtab, sel=self.sel, out=frames, workspace=self._perturb_ws)
+            ops.gaussian_blur_u8(frames, self.blur, out=frames, workspace=self._perturb_ws)
         if self.warp:
-            ops.augment_warp_u8(self.frames, self.tab_a, self.tab_b, self.swap, self.mode, self.pos_y, self.pos_x, self.coef_y, self.coef_x,
-                                self.affine, masks=self.masks, out=self.x, target=target, mean=self.mean, std=self.std)
+            ops.augment_warp_u8(frames, self.tab_a, self.tab_b, self.swap, self.mode, self.pos_y, self.pos_x, self.coef_y, self.coef_x,
+                                self.affine, masks=masks, out=self.x, target=target, mean=self.mean, std=self.std)
         else:
-            ops.augment_stage_u8(self.frames, self.tab_a, self.tab_b, self.swap, masks=self.masks, out=self.x, target=target,
+            ops.augment_stage_u8(frames, self.tab_a, self.tab_b, self.swap, masks=masks, out=self.x, target=target,
                                  mean=self.mean, std=self.std)

@@ -189,6 +189,18 @@ SURFACES = [
 ABI_VERSION = SURFACES[0].version
 SIGNATURES = {name: args for s in SURFACES for name, args in s.signatures.items()}      # every bound entry, whichever header declares it
 
+# include/mumpy_perturb.h: the ordinary perturbations of uint8 frames.  A surface outside the mumpy_hip.h / mumpy_hip_ext*.h family that
+# SURFACES lists (tests/test_abi.py pins that family's headers, versions and names with literals, and tests/test_input_grad_host.py
+# the names of the newest of them), bound and version-checked by load_library in the same way; tests/test_perturb_host.py holds it to
+# its header and to both libraries' exports.
+PERTURB = Surface("mumpy_perturb.h", "mumpy_perturb_version", 1, {
+    "mumpy_jpeg_roundtrip_workspace_bytes": [c_l, c_i, c_i],
+    "mumpy_jpeg_roundtrip_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_i, c_f],
+    "mumpy_gaussian_blur_workspace_bytes": [c_l, c_i, c_i],
+    "mumpy_gaussian_blur_u8_fwd": [c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_f],
+    "mumpy_resize_nearest_u8_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_f],
+})
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -228,7 +240,7 @@ def load_library():
     lib.mumpy_last_error.restype = ctypes.c_char_p
     lib.mumpy_last_route.restype = ctypes.c_char_p      # (AttributeError here or below = the library is stale: fail loudly)
     lib.mumpy_last_route.argtypes = []
-    for s in SURFACES:
+    for s in SURFACES + [PERTURB]:
         version = getattr(lib, s.version_fn)
         version.restype, version.argtypes = c_i, []
         if version() != s.version:

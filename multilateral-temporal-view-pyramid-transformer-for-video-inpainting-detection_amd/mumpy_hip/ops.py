@@ -1380,6 +1380,162 @@ def resize_bilinear_u8(src, size, out=None):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- perturbations (mumpy_perturb.h)
+PERTURB_CHUNK_BYTES = 64 << 20       # workspace the perturbation wrappers allocate for themselves at the most: they chunk over images
+_JPEG_TABLES = {}
+
+
+def _frames_u8(frames, who, channels=3):
+    """frames (..., H, W, channels) uint8, contiguous, on the GPU, read (or written) where it is -> (nimg, H, W)."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() < 3 \
+            or frames.shape[-1] != channels or not frames.is_contiguous():
+        raise RuntimeError(f"mumpy_hip: {who} needs a contiguous uint8 GPU tensor (..., H, W{', 3' if channels == 3 else ''}) (there is no CPU path), got "
+                           f"{getattr(frames, 'dtype', type(frames))} {tuple(getattr(frames, 'shape', ()))}")
+    h, w = frames.shape[-3:-1]
+    if h < 1 or w < 1:
+        raise RuntimeError(f"mumpy_hip: {who}: empty image {h}x{w}")
+    return frames.numel() // (channels * h * w), h, w
+
+
+def _perturb_out(frames, out, who):
+    if out is None:
+        return torch.empty_like(frames)
+    _chk_exact(out, "out", torch.uint8, frames.shape, who)
+    if out.data_ptr() != frames.data_ptr():
+        lo, hi = sorted(((frames.data_ptr(), frames.numel()), (out.data_ptr(), out.numel())))
+        if lo[0] + lo[1] > hi[0]:
+            raise RuntimeError(f"mumpy_hip: {who}: out may be frames itself but must not overlap it partially")
+    return out
+
+
+def _perturb_chunks(entry, nimg, h, w, workspace, who, device):
+    """-> (workspace, bytes per image, images per launch): the caller's workspace must hold all nimg images (one launch); without
+    one the wrapper allocates at most PERTURB_CHUNK_BYTES and walks the images in chunks."""
+    total = _ws_bytes((entry, nimg, h, w), entry, nimg, h, w)
+    if total < 0:
+        raise RuntimeError(f"mumpy_hip: {who}: {entry}({nimg}, {h}, {w}) refused (rc={total}): {_lib().mumpy_last_error().decode()}")
+    if workspace is not None:
+        if not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < total:
+            raise RuntimeError(f"mumpy_hip: {who} needs workspace as a contiguous uint8 GPU tensor of at least {total} bytes, got "
+                               f"{workspace.dtype} {tuple(workspace.shape)} on {workspace.device}")
+        return workspace, max(nimg, 1)
+    one = max(_ws_bytes((entry, 1, h, w), entry, 1, h, w), 16)
+    step = max(1, min(nimg, PERTURB_CHUNK_BYTES // one))
+    return torch.empty(max(_ws_bytes((entry, step, h, w), entry, step, h, w), 16), device=device, dtype=torch.uint8), step
+
+
+def jpeg_tables_u16(tables, device=None):
+    """(ntab, 2, 64) quantisation tables as the uint16 device tensor the kernel reads: from a numpy array / list of
+    mumpy_hip.perturb.jpeg_tables rows (uploaded) or a device tensor of uint16 / int16 (the same bits) taken where it is."""
+    if isinstance(tables, torch.Tensor):
+        t = tables
+    else:
+        import numpy as np
+        a = np.asarray(tables)
+        if a.size == 0 or a.size % 128 or a.min() < 1 or a.max() > 65535:
+            raise RuntimeError(f"mumpy_hip: jpeg tables must be (ntab, 2, 64) with entries in 1 .. 65535, got shape {a.shape}")
+        t = torch.from_numpy(np.ascontiguousarray(a.astype(np.uint16).reshape(-1, 2, 64))).to(device)
+    if not t.is_cuda or t.dtype not in (torch.uint16, torch.int16) or t.dim() != 3 or tuple(t.shape[1:]) != (2, 64) or t.shape[0] < 1 \
+            or not t.is_contiguous():
+        raise RuntimeError(f"mumpy_hip: jpeg tables must be a contiguous uint16 GPU tensor (ntab, 2, 64) with ntab >= 1, got {t.dtype} "
+                           f"{tuple(t.shape)} on {t.device}")
+    return t
+
+
+def jpeg_roundtrip_u8(frames, quality_or_tables, sel=None, out=None, workspace=None):
+    """The JPEG round trip on the GPU (mumpy_jpeg_roundtrip_u8_fwd, include/mumpy_perturb.h): frames (..., H, W, 3) uint8 -> the
+    same shape, every image what Pillow returns for save(format="JPEG", quality=q) + Image.open, bit for bit
+    (mumpy_hip.perturb.jpeg_roundtrip is the numpy statement).  quality_or_tables: an integer quality 1 .. 100 for every image (its
+    tables are uploaded once per quality and device: make the first call outside a graph capture), or a device tensor (ntab, 2, 64)
+    uint16 of mumpy_hip.perturb.jpeg_tables rows with sel (nimg) int32 on the device choosing the table per image -- a negative
+    (or too large) sel copies that image through; sel=None uses table 0 everywhere.  Tables and sel are read when the kernels run.
+    out= (contiguous uint8 of the same shape) may be frames itself.  workspace= (uint8, at least
+    mumpy_jpeg_roundtrip_workspace_bytes(nimg, H, W)) gives one pair of launches, as a capture wants; without it the wrapper
+    allocates at most PERTURB_CHUNK_BYTES and walks the images in chunks."""
+    who = "jpeg_roundtrip_u8"
+    nimg, h, w = _frames_u8(frames, who)
+    if isinstance(quality_or_tables, torch.Tensor):
+        qtab = jpeg_tables_u16(quality_or_tables)
+    else:
+        from .perturb import jpeg_tables
+        rows = jpeg_tables(quality_or_tables)                        # refuses a quality outside 1 .. 100
+        key = (int(quality_or_tables), str(frames.device))
+        qtab = _JPEG_TABLES.get(key)
+        if qtab is None:
+            qtab = _JPEG_TABLES[key] = jpeg_tables_u16(rows[None], frames.device)
+    if sel is None:
+        sel = torch.zeros(nimg, device=frames.device, dtype=torch.int32)
+    _chk_exact(sel, "sel", torch.int32, (nimg,), who)
+    out = _perturb_out(frames, out, who)
+    ws, step = _perturb_chunks("mumpy_jpeg_roundtrip_workspace_bytes", nimg, h, w, workspace, who, frames.device)
+    src, dst = frames.view(nimg, h, w, 3), out.view(nimg, h, w, 3)
+    for i in range(0, nimg, step):
+        m = min(step, nimg - i)
+        _call("mumpy_jpeg_roundtrip_u8_fwd", _p(src[i:i + m]), _p(dst[i:i + m]), _p(qtab), _p(sel[i:i + m]), _p(ws), ws.numel(), m,
+              qtab.shape[0], h, w, _stream(), work=float(6 * m * h * w))
+    return out
+
+
+def blur_params(radius_or_rows, nimg, device):
+    """(nimg, 4) int32 on the device, {r, ww, fw, on} per image: one radius for every image, or one per image (a sequence of nimg
+    radii; None means off) -- computed by mumpy_hip.perturb.box_params and uploaded."""
+    import numpy as np
+    from .perturb import box_params
+    off = (0, 1 << 24, 0, 0)
+    if np.ndim(radius_or_rows) == 0:
+        rows = [box_params(radius_or_rows)] * nimg
+    else:
+        rows = [off if r is None else box_params(r) for r in radius_or_rows]
+        if len(rows) != nimg:
+            raise RuntimeError(f"mumpy_hip: blur_params: {len(rows)} radii for {nimg} images")
+    return torch.from_numpy(np.asarray(rows, dtype=np.int64).astype(np.int32).reshape(nimg, 4)).to(device)
+
+
+def gaussian_blur_u8(frames, radius_or_params, out=None, workspace=None):
+    """ImageFilter.GaussianBlur(radius) of Pillow on the GPU (mumpy_gaussian_blur_u8_fwd, include/mumpy_perturb.h): frames
+    (..., H, W, 3) uint8 -> the same shape, bit for bit (mumpy_hip.perturb.gaussian_blur is the numpy statement).
+    radius_or_params: a radius for every image (its parameters are uploaded by this call: pass a tensor inside a graph capture), or
+    a device tensor (nimg, 4) int32 of {r, ww, fw, on} rows (`blur_params`, mumpy_hip.perturb.box_params), read when the kernels
+    run; on == 0 copies that image through.  out= and workspace= as in jpeg_roundtrip_u8 (mumpy_gaussian_blur_workspace_bytes)."""
+    who = "gaussian_blur_u8"
+    nimg, h, w = _frames_u8(frames, who)
+    params = radius_or_params if isinstance(radius_or_params, torch.Tensor) else blur_params(radius_or_params, nimg, frames.device)
+    _chk_exact(params, "params", torch.int32, (nimg, 4), who)
+    out = _perturb_out(frames, out, who)
+    ws, step = _perturb_chunks("mumpy_gaussian_blur_workspace_bytes", nimg, h, w, workspace, who, frames.device)
+    src, dst = frames.view(nimg, h, w, 3), out.view(nimg, h, w, 3)
+    for i in range(0, nimg, step):
+        m = min(step, nimg - i)
+        _call("mumpy_gaussian_blur_u8_fwd", _p(src[i:i + m]), _p(dst[i:i + m]), _p(params[i:i + m]), _p(ws), ws.numel(), m, h, w,
+              _stream(), work=float(12 * m * h * w))
+    return out
+
+
+def resize_nearest_u8(frames, size, out=None, channels=3):
+    """Image.resize((W, H), Image.NEAREST) of RGB frames on the GPU (mumpy_resize_nearest_u8_fwd, include/mumpy_perturb.h): frames
+    (..., Hs, Ws, 3) uint8 -> (..., H, W, 3) uint8, size = (H, W), through the tables of mumpy_resize_nearest_table (cached per
+    sizes and device: make the first call for a pair of sizes outside a graph capture).  channels=1: single-channel images (masks)
+    (..., Hs, Ws) -> (..., H, W).  out= is written in place and must be contiguous uint8 of exactly that shape, and must not
+    overlap frames."""
+    who = "resize_nearest_u8"
+    if channels not in (1, 3):
+        raise RuntimeError(f"mumpy_hip: resize_nearest_u8: channels={channels} must be 1 or 3")
+    src = frames.unsqueeze(-1) if channels == 1 and isinstance(frames, torch.Tensor) and frames.is_contiguous() else frames
+    nimg, hs, ws = _frames_u8(src, who, channels)
+    ho, wo = (int(v) for v in size)
+    if ho < 1 or wo < 1:
+        raise RuntimeError(f"mumpy_hip: resize_nearest_u8: empty output {ho}x{wo}")
+    shape = (*src.shape[:-3], ho, wo) + ((3,) if channels == 3 else ())
+    out = torch.empty(shape, device=src.device, dtype=torch.uint8) if out is None else _chk_exact(out, "out", torch.uint8, shape, who)
+    lo, hi = sorted(((src.data_ptr(), src.numel()), (out.data_ptr(), out.numel())))
+    if nimg and lo[0] + lo[1] > hi[0]:
+        raise RuntimeError("mumpy_hip: resize_nearest_u8: out overlaps frames")
+    ytab, xtab = _nearest_table(hs, ho, src.device), _nearest_table(ws, wo, src.device)
+    _call("mumpy_resize_nearest_u8_fwd", _p(src), _p(out), _p(ytab), _p(xtab), nimg, hs, ws, ho, wo, channels, _stream(),
+          work=float(2 * out.numel()))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- training tail (8f-2)
 def mask_loss(logits, target, need_grad=True, eps=0.0, loss_scale=1.0):
     """softIoULoss + WeightedFocalLoss as train.py:107-113 calls them (utils/loss.py:6-55).  logits (B,...) and 0/1 target of the

@@ -195,12 +195,24 @@ class VideoPredictor(GraphedForward):
     reference's batch-size-1 test.py computes it.  A frame's mask then depends neither on `batch`, nor on which clips share its
     batch or in what order, nor on the tail's padding clips -- up to the fp32 rounding of the GEMM routes, which are still chosen
     by the batch's row count (logits agree to ~1e-6 relative, not bit for bit).  The predictor sets the switch around its own
-    forwards only and leaves the global ops.clip_coupling() as it found it."""
+    forwards only and leaves the global ops.clip_coupling() as it found it.
+
+    perturb=("jpeg", q), ("blur", r) or a list of those, applied in order: every predict first runs that post-processing once, in
+    place, on the uploaded video at its own size (ops.jpeg_roundtrip_u8 / ops.gaussian_blur_u8: Pillow's save(format="JPEG",
+    quality=q) + re-open and ImageFilter.GaussianBlur(r), bit for bit), before the first batch -- what an unperturbed predictor
+    computes when it is fed the frames Pillow processed on the host.  A robustness table is
+    `for q in (90, 70, 50): VideoPredictor(..., perturb=("jpeg", q)).predict(frames, gt)`.  The predictor owns the tables and a
+    workspace of perturb_chunk frames; a bad spec is refused here.  perturb=None (the default) allocates nothing and launches
+    nothing: the captured graph, the masks, the bank, the counts and the metric vector are what they were without the option."""
 
     def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True, gt_hw=None, gt_chunk=64,
-                 sweep=None, coupling="batch"):
+                 sweep=None, coupling="batch", perturb=None, perturb_chunk=64):
+        from .perturb import check_spec, jpeg_tables
         if coupling not in ("batch", "clip"):
             raise ValueError(f"VideoPredictor: coupling must be \"batch\" or \"clip\", got {coupling!r}")
+        steps = check_spec(perturb, "VideoPredictor: perturb")      # refuses a bad spec
+        if steps and int(perturb_chunk) < 1:
+            raise ValueError(f"VideoPredictor: perturb_chunk={perturb_chunk} must be at least 1")
         T, batch, max_frames = int(T), int(batch), int(max_frames)
         clip_frame_indices(1, T)                                     # refuses an even T
         model_t = int(encoder.configs[-1]["num_frames"])
@@ -249,6 +261,24 @@ class VideoPredictor(GraphedForward):
         if self.gt_hw is not None:
             from . import ops
             ops._bilinear_tables(*self.gt_hw, SIDE, SIDE, dev)      # uploaded here, not in the first predict
+        # perturb: per step its device-side setting (one table pair, or one box row per frame of a chunk), and one workspace
+        self.perturb, self._perturb_ws = [], None
+        if steps:
+            from . import ops
+            chunk = min(int(perturb_chunk), max_frames)
+            lib, need = ops._lib(), [16]
+            for kind, value in steps:
+                if kind == "jpeg":
+                    need.append(int(lib.mumpy_jpeg_roundtrip_workspace_bytes(chunk, hs, ws)))
+                    self.perturb.append((kind, value, ops.jpeg_tables_u16(jpeg_tables(value)[None], dev),
+                                         torch.zeros(chunk, device=dev, dtype=torch.int32)))
+                else:
+                    need.append(int(lib.mumpy_gaussian_blur_workspace_bytes(chunk, hs, ws)))
+                    self.perturb.append((kind, value, ops.blur_params(value, chunk, dev), None))
+            if min(need) < 0:
+                raise ValueError(f"VideoPredictor: perturb: frames of {hs}x{ws} are refused: {lib.mumpy_last_error().decode()}")
+            self._perturb_ws = torch.empty(max(need), device=dev, dtype=torch.uint8)
+            self._perturb_chunk = chunk
         clips = torch.zeros(batch, T, 3, SIDE, SIDE, device=dev, dtype=torch.float32)
         if self.graphed:
             super().__init__(encoder, decoder, clips, with_mask=True, coupling=coupling)     # static_x is the clip batch
@@ -315,6 +345,8 @@ class VideoPredictor(GraphedForward):
         self._idx_host[:nb].copy_(torch.from_numpy(idx))
         self._dest_host[:nb].copy_(torch.from_numpy(dest))
         self.frames[:n].copy_(frames_u8, non_blocking=True)
+        if self.perturb:
+            self._perturb_frames(n)
         if gt_u8 is not None and self.gt_hw is None:
             self.gt[:n].copy_(gt_u8.reshape(n, SIDE * SIDE), non_blocking=True)
         elif gt_u8 is not None:
@@ -332,6 +364,19 @@ class VideoPredictor(GraphedForward):
             if self.table is not None:
                 ops.sweep_metrics(self.exceed, n, SIDE * SIDE, acc=self.sweep_acc, pooled=self.sweep_pooled, accumulate=True)
         return self.bank[:n].view(n, SIDE, SIDE)
+
+    def _perturb_frames(self, n):
+        """frames[:n] through every step of `perturb`, in place, issued on the current stream ahead of the first batch, one pair of
+        launches per step and chunk of perturb_chunk frames (the workspace holds one chunk)."""
+        from . import ops
+        for kind, _, setting, sel in self.perturb:
+            for i in range(0, n, self._perturb_chunk):
+                part = self.frames[i:min(i + self._perturb_chunk, n)]
+                m = part.shape[0]
+                if kind == "jpeg":
+                    ops.jpeg_roundtrip_u8(part, setting, sel=sel[:m], out=part, workspace=self._perturb_ws)
+                else:
+                    ops.gaussian_blur_u8(part, setting[:m], out=part, workspace=self._perturb_ws)
 
     def _resize_gt(self, gt_u8, n):
         """gt[:n] = Image.resize((224, 224), BILINEAR) of the annotations (ops.resize_bilinear_u8), issued on the current stream ahead
