@@ -85,7 +85,7 @@ def _frozen_by_slices(entry, t, c, b, h, w, hs2, groups):
 
 def _guarded(monkeypatch, entry, cpu, c, b, h, w, hs2, groups):
     """The grouped launch under tests/guarded_alloc.py: bands intact, every element of the output written, inputs unchanged.
-    -> the output of each of the two runs."""
+    -> the output of each guarded run (one per pass of GA.PASSES)."""
     def body(guard):
         return {"out": _launch(entry, {k: guard.tensor(v) for k, v in cpu.items()}, b, h, w, hs2, c, groups)}, (), None
     runs, unguarded = GA.run_both(monkeypatch, [_ops()], body, device=DEV, sync=torch.cuda.synchronize)

@@ -78,7 +78,7 @@ def _frozen_by_slices(entry, t, r, groups):
 def _guarded(monkeypatch, entry, cpu, r, groups):
     """The grouped launch under tests/guarded_alloc.py: bands intact, every element of the outputs written, inputs unchanged.
     dpos comes out of a torch reduction of the guarded slot buffer, which the proxy cannot see: the only output allowed to live
-    outside a guarded block (an unwritten slot would reach it as NaN under the first pattern).  -> the outputs of the two runs."""
+    outside a guarded block (an unwritten slot would reach it as NaN under the first pattern).  -> the outputs of each guarded run (one per pass of GA.PASSES)."""
     def body(guard):
         return _launch(entry, {k: guard.tensor(v) for k, v in cpu.items()}, r, groups), (), None
     runs, unguarded = GA.run_both(monkeypatch, [_ops()], body, device=DEV, sync=torch.cuda.synchronize)

@@ -6,16 +6,40 @@ intercepts the allocations mumpy_hip.ops / mumpy_hip.autograd already make and s
 
 CPU tests (no GPU): the proxy reproduces shapes / strides / dtypes, and the harness FAILS on a band write, an unwritten row, a
 modified input and a written `partial` region, and passes when an op legitimately stores the fill pattern.  They are the proof that
-the harness can fail; no kernel is ever made to write out of bounds for that.
+the harness can fail; no kernel is ever made to write out of bounds for that.  Three of them pin down what patterns A and B alone
+cannot see and the per-block third pass of tests/guarded_alloc.py can: a store past an output whose value was loaded from past an
+input -- summed (op_stray_sum), copied verbatim (op_stray_copy), and the db reduce of mumpy_dwconv5_window_bwd with the column bound
+it had before its fix, restated on the host at (n, cg) = (6, 32) (op_window_db_reduce; the old kernel is never rebuilt or run).
+Under 0xFF and under 0x7F every band compares intact, under per-block bytes the output's block is named.
 
 GPU test (marked gpu test by test, because this file also holds the CPU tests): one parametrised test over CASES.  Each case runs
-its call unguarded, then under the guard with pattern 0xFF (NaN), then with pattern 0x7F (3.39e38), in one process on the current
-stream, and asserts (a) bands, (b) full writes, (c) inputs kept, and that both guarded results are BITWISE equal to the unguarded
-one.  Values are not re-checked.  Shapes: only parametrisations an existing test already launches, the smallest and most ragged of
-each family (the test each comes from is named at the case).  Three families differ from a literal reading of their issue: the 7 x 7
+its call unguarded, then under the guard with pattern 0xFF (NaN), with pattern 0x7F (3.39e38) and with per-block bytes 0x3B..0x3F,
+in one process on the current stream, and asserts (a) bands, (b) full writes (decided by the first two), (c) inputs kept, and that
+all three guarded results are BITWISE equal to the unguarded one.  Values are not re-checked.  Shapes: parametrisations an existing
+test already launches, the smallest and most ragged of each family (the test each comes from is named at the case) -- and, for the
+cross-view chain, the four side-view widths C = 96, 192, 384, 768 (group width 32, 64, 128, 256) at the smallest window counts:
+dwconv5_window(_bwd) at (n, cg) with n in {1, 6}, deform_sample_bwd and deform_attention_bwd (fp32 and bf16) at (windows, r) = (2, 3)
+and with groups = 2 at (4, 3) for C = 96 and 768, deform_offsets / deform_sample_kv / deform_out_combine at C = 384 and 768; the
+values of the two backward ops at these widths are held by tests/test_swin_backward.py (..._side_view_widths, against fp64).
+Three families differ from a literal reading of their issue: the 7 x 7
 window-attention backward runs with shift 0 only (the existing tests force shift 0 on a one-window grid; the shifted backward is
 covered at 14 x 14), the fused cross-view GEMMs run at (C, side, r) = (96, 14, 1) and (192, 14, 3) (the existing set has no
 (96, 14, 3)), and deform_offsets runs in the one-window form its own test uses.
+
+GPU test of the whole model (test_whole_model_under_the_guard): the three-view model's eval forward (fp32; bf16 storage with bf16
+window and cross-view attention) at B = 1 and its training tape (fp32 at B = 1; bf16 window and cross-view attention, fused MLP and
+per-clip pairing at B = 2), T = 3, with the proxy in mumpy_hip.ops, mumpy_hip.autograd and the three models.* modules that allocate.
+Each configuration runs twice unguarded (bitwise equal: the precondition) and once per pass; every band of every block must be
+intact after a device-wide synchronise, the clip and the target unchanged, the logits and every parameter gradient bitwise those of
+the unguarded run.  Check (b) is not applied: intermediates are not outputs.  Seen on an MI355X (launches through ops._call; guarded
+blocks, the same under every pass, clip and target included):
+    eval-fp32-b1                               727 launches,   766 blocks
+    eval-bf16-storage-b1                       731 launches,   772 blocks
+    train-fp32-b1                             1693 launches,  3505 blocks   (logits + 1177 parameter gradients compared)
+    train-bf16-attention-fused-mlp-clip-b2    1561 launches,  3442 blocks   (the same)
+All of it passed as found: no kernel or wrapper needed a fix.  On a band failure the configuration runs once more with the damaged
+blocks watched after every launch (_watching_call; its report path has a CPU test beside it) and the failure names the first entry
+point after which a band changed, with its scalar arguments.
 
 `partial` exemptions (regions an op must NOT write; they must still hold the pattern):
   * gn_resample/out_coff: channels [0, 256) of the 384-channel map -- the op writes the slice [256, 384) of a concatenated map;
@@ -24,11 +48,17 @@ covered at 14 x 14), the fused cross-view GEMMs run at (C, side, r) = (96, 14, 1
 Padding that a kernel zero-fills counts as written and is checked as such: avgpool2_pad's channels [C, Cpad), transpose's columns
 [R, Rp), expand_relpos_bias's rows / key columns >= 49.
 Unguarded allocation sites: Tensor.new_zeros in autograd.py (channel padding of the generic final-conv backward), torch.full in
-ops.compact_attn_mask (host table), and the temporaries of tensor methods (.contiguous(), .sum(), slicing copies); an op's result
-that such a method produced (deform_sample_bwd's dpos = part.sum(0), the only one: UNGUARDED_RESULTS) is compared bitwise only -- an
-unwritten element of the guarded buffer behind it is NaN under pattern A and breaks that comparison.
-What the harness cannot see: out-of-bounds READS, and writes further than 4 KB from a buffer.
+ops.compact_attn_mask (host table), and the temporaries of tensor methods (.contiguous(), .sum(), slicing copies, and in the
+whole-model test everything torch's own autograd and torch.cat / repeat / reshape allocate); an op's result that such a method
+produced (deform_sample_bwd's dpos = part.sum(...), at every width: UNGUARDED_RESULTS) is compared bitwise only -- an unwritten
+element of the guarded buffer behind it is NaN under pattern A and breaks that comparison.
+What the harness sees since the third pass: a store within 4 KB of a buffer whatever its value was computed from, another block's
+band included.  What it still cannot see: out-of-bounds READS that reach no result (one that reaches a result changes it between
+the passes and breaks the bitwise comparison), writes further than 4 KB from a buffer, a stray store whose value was loaded from
+the band of the very block it lands in, and a verbatim copy between the bands of two blocks whose allocations lie a multiple of
+five apart (five bytes in the cycle).
 Out of scope: graph capture / replay, ops.background, the multi-stream pipeline, tests/gemm_route_worker.py (it has guard rows)."""
+import contextlib
 import functools
 import os
 import types
@@ -68,7 +98,40 @@ def _fake_module():
         out[:, coff:coff + x.shape[1] + overrun] = 1.0
         return out
 
+    def past(t):
+        """The element just past the end of a dense tensor: the first one of the band behind its block."""
+        return t.as_strided((1,), (1,), t.storage_offset() + t.numel())
+
+    def op_stray_sum(x):
+        """One wrong bound shared by a load and a store: x[n] + x[0] lands one element past out."""
+        out = op_full(x)
+        past(out).copy_(past(x) + x.reshape(-1)[:1])
+        return out
+
+    def op_stray_copy(x):
+        """... and a verbatim copy from the input's band into the output's band."""
+        out = op_full(x)
+        past(out).copy_(past(x))
+        return out
+
+    def op_window_db_reduce(part, n, c, bound):
+        """Host restatement of the db launch of window_partial_reduce (csrc/deform_bwd.hip): part is the (n, 26 c) image of per-window
+        partials, the launch starts at column 25 c of each row and runs (c + 63) / 64 blocks of 64 columns, db[i] = sum_n part[n][25 c
+        + i] in ascending n for every column i < bound.  bound = "count" is the kernel (i < c); bound = "width" is what it was before
+        its fix (i < 26 c, the row stride): at c = 32 the one block stores 32 floats past db, the last of its terms loaded from past
+        the end of part."""
+        db = fake.torch.empty(c, dtype=torch.float32)
+        width = 26 * c
+        cols = min((c + 63) // 64 * 64, {"count": c, "width": width}[bound])
+        src = part.as_strided((n, cols), (width, 1), part.storage_offset() + 25 * c)
+        acc = src[0].clone()
+        for k in range(1, n):
+            acc = acc + src[k]
+        db.as_strided((cols,), (1,), db.storage_offset()).copy_(acc)
+        return db
+
     fake.op_full, fake.op_skips_row, fake.op_scribbles, fake.op_slice = op_full, op_skips_row, op_scribbles, op_slice
+    fake.op_stray_sum, fake.op_stray_copy, fake.op_window_db_reduce = op_stray_sum, op_stray_copy, op_window_db_reduce
     return fake
 
 
@@ -139,8 +202,8 @@ def _body(fake, op, x, **kw):
 
 def test_harness_passes_a_clean_op(monkeypatch):
     fake, x = _fake_module(), seeded_randn(1, 6, 5)
-    (a, b), unguarded = GA.run_both(monkeypatch, [fake], _body(fake, "op_full", x))
-    assert GA.same_bits(a["y"], x * 2) and GA.same_bits(b["y"], x * 2) and unguarded == set()
+    runs, unguarded = GA.run_both(monkeypatch, [fake], _body(fake, "op_full", x))
+    assert len(runs) == len(GA.PASSES) == 3 and all(GA.same_bits(r["y"], x * 2) for r in runs) and unguarded == set()
 
     def body(guard):                                                     # a result that a tensor method allocated is reported as unseen
         return {"y": fake.op_full(guard.tensor(x)).sum(0)}, (), None
@@ -224,6 +287,105 @@ def test_a_declared_partial_region_must_stay_untouched(monkeypatch, overrun):
         fake.op_slice(guard.tensor(torch.ones(4, 6)), out, 2, 0)
         return {"out": out}, (), {"out": ((slice(None), slice(0, 2)), "the op fills columns [2, 8)")}
     GA.run_both(monkeypatch, [fake], body_ok)
+
+
+# ------------------------------------------------------------------------------------------------ CPU: the per-block third pass
+def test_per_block_bytes_differ_between_neighbours_and_read_as_ordinary_numbers():
+    guard = GA.Guard(GA.CYCLE)
+    assert GA.PASSES == (GA.PATTERN_A, GA.PATTERN_B, GA.CYCLE) and GA.CYCLE == (0x3B, 0x3C, 0x3D, 0x3E, 0x3F)
+    made = []
+    for i in range(13):                                                  # proxy allocations and tensor() blocks, interleaved
+        announced = guard.pattern                                        # the byte the next block gets
+        if i % 3 == 1:
+            made.append(("tensor", guard.tensor(seeded_randn(i, 3, 5))))
+        elif i % 3 == 2:
+            made.append(("zeros", guard.torch.zeros(7, dtype=torch.float32)))
+        else:
+            made.append(("empty", guard.torch.empty(2, 9, dtype=torch.bfloat16 if i % 2 else torch.float32)))
+        assert guard.log[-1].fill == announced
+    fills = [a.fill for a in guard.log]
+    assert len(fills) == 13 and set(fills) == set(GA.CYCLE)
+    assert all(x != y for x, y in zip(fills, fills[1:]))                 # consecutive allocations never share a byte
+    for (kind, view), a in zip(made, guard.log):
+        assert bool((a.raw[:a.lo] == a.fill).all()) and bool((a.raw[a.hi:] == a.fill).all())
+        if kind == "empty":                                              # the interior carries the block's byte too ...
+            assert bool((a.raw == a.fill).all())
+            assert bool(((view.float() > 2.8e-3) & (view.float() < 0.75)).all())          # ... an ordinary magnitude in fp32 and bf16
+        assert a.site == ("Guard.tensor" if kind == "tensor" else "test_per_block_bytes_differ_between_neighbours_and_read_as_ordinary_numbers")
+    assert guard.band_hits() == []
+    guard.check({"y": made[0][1]})                                       # (a) and (c) only: nothing said about the unwritten output
+    assert guard.unwritten == {} and guard.unguarded == set()
+    a, b = guard.log[3], guard.log[4]
+    b.raw[b.lo - 4:b.lo] = a.fill                                        # the neighbour's byte in a band is a hit ...
+    assert guard.band_hits() == [(4, b.site, tuple(b.view.shape), 4, 0)] and guard.band_hits(only=[3]) == []
+    with pytest.raises(AssertionError, match=r"guard band overwritten \(per-block bytes 0x3b..0x3f\)"):
+        guard.check({})
+    b.raw[b.lo - 4:b.lo] = b.fill                                        # ... the block's own is not
+    assert guard.band_hits() == []
+
+
+def test_allocations_are_tagged_with_the_innermost_function_of_a_proxied_module(monkeypatch):
+    mod = types.ModuleType("somepkg.fakeops")
+    exec("def outer(n):\n    return inner(n)\n\n\ndef inner(n):\n    return torch.empty(n), helper.op_full(torch.zeros(n))\n", mod.__dict__)
+    mod.torch, mod.helper = torch, _fake_module()                        # helper's functions live in this file: their frames are passed over
+    guard = GA.Guard(GA.PATTERN_A)
+    with guard.installed(monkeypatch, mod, mod.helper):
+        mod.outer(4)
+        guard.tensor(torch.ones(2))
+    assert [a.site for a in guard.log] == ["fakeops.inner", "fakeops.inner", "fakeops.inner", "Guard.tensor"]
+    guard.log[1].raw[0] = 0
+    assert guard.band_hits() == [(1, "fakeops.inner", (4,), 1, 0)]
+    with pytest.raises(AssertionError, match=r"guard band overwritten \(pattern 0xff\).*\(1, 'fakeops.inner', \(4,\), 1, 0\)"):
+        guard.check({})
+
+
+def _one_pass(monkeypatch, fake, pattern, run):
+    """run(guard) under one pattern alone -> the guard, after its own checks (a) and (c)."""
+    guard = GA.Guard(pattern)
+    with guard.installed(monkeypatch, fake):
+        outputs = run(guard)
+        assert guard.band_hits() == []
+        guard.check(outputs)
+    return guard
+
+
+@pytest.mark.parametrize("op", ["op_stray_sum", "op_stray_copy"])
+def test_a_store_fed_by_a_stray_load_passes_patterns_a_and_b_and_fails_the_third_pass(monkeypatch, op):
+    """The blind spot as a fact: both patterns absorb the addition (NaN + x is the same NaN, 3.39e38 + x rounds back), and a copy
+    carries the pattern over, so the element written past `out` holds the band's own bytes.  Per-block bytes tell the two bands
+    apart."""
+    fake, x = _fake_module(), seeded_randn(1, 6, 5)
+    for pattern in GA.PATTERNS:
+        guard = _one_pass(monkeypatch, fake, pattern, lambda g: {"y": getattr(fake, op)(g.tensor(x))})
+        out = guard.log[1]
+        assert bool((out.raw[out.hi:out.hi + 4] == pattern).all())       # the stray store happened, and wrote the pattern
+    with pytest.raises(AssertionError, match=rf"guard band overwritten \(per-block bytes.*\[\(1, 'op_full', \(6, 5\), 0, [1-4]\)\]"):
+        GA.run_both(monkeypatch, [fake], _body(fake, op, x))             # names the output's block: index 1, after the input's
+    guard = GA.Guard(GA.CYCLE)
+    with guard.installed(monkeypatch, fake):
+        getattr(fake, op)(guard.tensor(x))
+    (hit,) = guard.band_hits()
+    assert hit[0] == 1 and hit[3] == 0 and hit[4] >= 1 and guard.log[0].fill != guard.log[1].fill
+
+
+def test_the_old_dwconv5_db_reduce_bound_passes_patterns_a_and_b_and_fails_the_third_pass(monkeypatch):
+    """(n, cg) = (6, 32), the stage-1 launch of the model: with the column bound i < 26 c the reduce stores 32 floats past db, each a
+    sum whose last term comes from past the end of the partials.  Patterns A and B leave every band intact; the third pass names db.
+    With the kernel's bound (i < c) all three pass."""
+    fake, n, c = _fake_module(), 6, 32
+    part = seeded_randn(7, n, 26 * c)
+
+    def body(bound):
+        return lambda g: ({"db": fake.op_window_db_reduce(g.tensor(part), n, c, bound)}, (), None)
+    for pattern in GA.PATTERNS:
+        guard = _one_pass(monkeypatch, fake, pattern, lambda g: body("width")(g)[0])
+        db = guard.log[1]
+        assert db.view.shape == (c,) and bool((db.raw[db.hi:db.hi + 128] == pattern).all())
+        assert torch.allclose(db.view, part[:, 25 * c:].sum(0), rtol=1e-5, atol=1e-6)              # db itself is right all along
+    with pytest.raises(AssertionError, match=r"guard band overwritten \(per-block bytes.*\[\(1, 'op_window_db_reduce', \(32,\), 0, 128\)\]"):
+        GA.run_both(monkeypatch, [fake], body("width"))
+    runs, unguarded = GA.run_both(monkeypatch, [fake], body("count"))
+    assert unguarded == set() and all(GA.same_bits(r["db"], runs[0]["db"]) for r in runs)
 
 
 # ================================================================================================ GPU: the case table
@@ -520,14 +682,15 @@ for _b, _hs, _w, _c, _s in ((3, 7, 7, 32, 0), (2, 14, 14, 64, 3)):
 
 
 # ----------------------------------------------------------------------------------------------------- cross-view chain
-@case("deform_offsets/1x7x7x96")                                         # test_deform_offset_network_layernorm_offset_rows
-def _():
-    from models.modules.deformableAttention import SwinDAttention
-    sd = fill_module_(SwinDAttention(96, 3, 0.0, n_groups=3).eval(), "sda_r1/").state_dict()
-    i = {"q": seeded_randn(60, 1, 49, 96), "dw_w": sd["conv_offset.0.weight"], "dw_b": sd["conv_offset.0.bias"],
-         "ln_g": sd["conv_offset.1.norm.weight"], "ln_b": sd["conv_offset.1.norm.bias"], "pw_w": sd["conv_offset.3.weight"]}
-    i = {k: v.detach().clone() for k, v in i.items()}
-    return i, lambda ops, t: {"pos": ops.deform_offsets(t.q, t.dw_w, t.dw_b, t.ln_g, t.ln_b, t.pw_w, 1, 7, 7, 96)}
+for _c in (96, 384, 768):                                                # test_deform_offset_network_layernorm_offset_rows; 384, 768: the deep stages
+    @case(f"deform_offsets/1x7x7x{_c}")
+    def _(c=_c):
+        from models.modules.deformableAttention import SwinDAttention
+        sd = fill_module_(SwinDAttention(c, c // 32, 0.0, n_groups=3).eval(), "sda_r1/").state_dict()
+        i = {"q": seeded_randn(60, 1, 49, c), "dw_w": sd["conv_offset.0.weight"], "dw_b": sd["conv_offset.0.bias"],
+             "ln_g": sd["conv_offset.1.norm.weight"], "ln_b": sd["conv_offset.1.norm.bias"], "pw_w": sd["conv_offset.3.weight"]}
+        i = {k: v.detach().clone() for k, v in i.items()}
+        return i, lambda ops, t: {"pos": ops.deform_offsets(t.q, t.dw_w, t.dw_b, t.ln_g, t.ln_b, t.pw_w, 1, 7, 7, c)}
 
 
 @case("deform_sample/window-form-3x49x96")                                # test_deform_sampling_hits_zero_padding
@@ -536,7 +699,9 @@ def _():
     return i, lambda ops, t: {"y": ops.deform_sample(t.x2, t.pos, 3, 7, 7, 96, 3)}
 
 
-for _c, _side, _r in ((96, 14, 1), (192, 14, 3)):        # test_deform_fused_gemms_match_the_unfused_kernels + test_cva_bf16mm: b = 2, raster
+# test_deform_fused_gemms_match_the_unfused_kernels + test_cva_bf16mm: b = 2, raster; (384, 14, 3) and (768, 7, 3) are the side views'
+# stages 3 and 4 at their own map sizes, for the two fused GEMMs only
+for _c, _side, _r, _whole_chain in ((96, 14, 1, True), (192, 14, 3, True), (384, 14, 3, False), (768, 7, 3, False)):
     def _cva_inputs(c=_c, side=_side, r=_r):
         b = 2
         nq = b * (side // 7) ** 2
@@ -545,10 +710,11 @@ for _c, _side, _r in ((96, 14, 1), (192, 14, 3)):        # test_deform_fused_gem
                 "wkv": seeded_randn(52, 2 * c, c) / c ** 0.5, "bkv": seeded_randn(53, 2 * c), "o": seeded_randn(54 + c, nq, 49, c),
                 "x1": seeded_randn(55 + c, b, side * side, c), "wout": seeded_randn(56, c, c) / c ** 0.5, "bout": seeded_randn(57, c)}
 
-    @case(f"deform_sample/c{_c}-side{_side}-r{_r}")
-    def _(c=_c, side=_side, r=_r, inputs=_cva_inputs):
-        i = {k: v for k, v in inputs().items() if k in ("x2", "pos")}
-        return i, lambda ops, t: {"y": ops.deform_sample(t.x2, t.pos, 2, r * side, side, c, t.pos.shape[0])}
+    if _whole_chain:
+        @case(f"deform_sample/c{_c}-side{_side}-r{_r}")
+        def _(c=_c, side=_side, r=_r, inputs=_cva_inputs):
+            i = {k: v for k, v in inputs().items() if k in ("x2", "pos")}
+            return i, lambda ops, t: {"y": ops.deform_sample(t.x2, t.pos, 2, r * side, side, c, t.pos.shape[0])}
 
     for _math in ("fp32", "bf16"):
         @case(f"deform_sample_kv/c{_c}-side{_side}-r{_r}-{_math}")
@@ -561,11 +727,12 @@ for _c, _side, _r in ((96, 14, 1), (192, 14, 3)):        # test_deform_fused_gem
             i = {k: v for k, v in inputs().items() if k in ("o", "x1", "wout", "bout")}
             return i, lambda ops, t: {"y": ops.deform_out_combine(t.o, t.wout, t.bout, t.x1, 2, side, side, c, math=math)}
 
-    @case(f"deform_combine/c{_c}-side{_side}")
-    def _(c=_c, side=_side, inputs=_cva_inputs):
-        i = inputs()
-        i = {"x1": i["x1"], "yt": seeded_randn(58 + c, *i["o"].shape)}
-        return i, lambda ops, t: {"y": ops.deform_combine(t.x1, t.yt, 2, side, side, c)}
+    if _whole_chain:
+        @case(f"deform_combine/c{_c}-side{_side}")
+        def _(c=_c, side=_side, inputs=_cva_inputs):
+            i = inputs()
+            i = {"x1": i["x1"], "yt": seeded_randn(58 + c, *i["o"].shape)}
+            return i, lambda ops, t: {"y": ops.deform_combine(t.x1, t.yt, 2, side, side, c)}
 
 for _math in ("fp32", "bf16"):                                           # test_core_mm16_accuracy_...: (b, h, w, c, r) = (2, 14, 14, 96, 3)
     @case(f"deform_attention/2x14x14x96-r3-{_math}")
@@ -577,29 +744,44 @@ for _math in ("fp32", "bf16"):                                           # test_
         return i, lambda ops, t: {"y": ops.deform_attention(t.q, t.kv, t.pad, b, h, w, c, r, 32 ** -0.5, math=math)}
 
 
-@case("deform_sample_bwd/nq2-r3-c192")                                   # test_hip_deform_sample_bwd
-def _():
-    nq, r, c = 2, 3, 192
-    i = {"x2": seeded_randn(110, nq * r, 49, c), "pos": (seeded_randn(111, nq, 3, 49, 2) * 0.7).clamp(-1.3, 1.3), "ds": seeded_randn(112, nq * r, 49, c)}
+def _sample_bwd_case(nq, r, c, groups):
+    def build():
+        i = {"x2": seeded_randn(110, nq * r, 49, c), "pos": (seeded_randn(111, nq, 3, 49, 2) * 0.7).clamp(-1.3, 1.3), "ds": seeded_randn(112, nq * r, 49, c)}
 
-    def call(ops, t):
-        dx2, dpos = ops.deform_sample_bwd(t.x2, t.pos, t.ds)
-        return {"dx2": dx2, "dpos": dpos}
-    return i, call
-
-
-@case("deform_attention_bwd/b1-r5-c96")                                  # test_hip_deform_attention_bwd
-def _():
-    b1, r, c = 1, 5, 96
-    i = {"q": seeded_randn(120, b1, 49, c), "kv": seeded_randn(121, b1 * r, 49, 2 * c), "do": seeded_randn(122, b1, 49, c)}
-
-    def call(ops, t):
-        dq, dkv = ops.deform_attention_bwd(t.q, t.kv, t.do, r, 32 ** -0.5)
-        return {"dq": dq, "dkv": dkv}
-    return i, call
+        def call(ops, t):
+            dx2, dpos = ops.deform_sample_bwd(t.x2, t.pos, t.ds, groups=groups)
+            return {"dx2": dx2, "dpos": dpos}
+        return i, call
+    return build
 
 
-for _n, _c in ((3, 256), (6, 32)):                                       # test_hip_dwconv5_window_fwd_bwd
+def _attention_bwd_case(b1, r, c, math, groups):
+    def build():
+        i = {"q": seeded_randn(120, b1, 49, c), "kv": seeded_randn(121, b1 * r, 49, 2 * c), "do": seeded_randn(122, b1, 49, c)}
+
+        def call(ops, t):
+            dq, dkv = ops.deform_attention_bwd(t.q, t.kv, t.do, r, 32 ** -0.5, math=math, groups=groups)
+            return {"dq": dq, "dkv": dkv}
+        return i, call
+    return build
+
+
+case("deform_sample_bwd/nq2-r3-c192")(_sample_bwd_case(2, 3, 192, 1))               # test_hip_deform_sample_bwd
+case("deform_attention_bwd/b1-r5-c96")(_attention_bwd_case(1, 5, 96, "fp32", 1))    # test_hip_deform_attention_bwd
+# the four side-view widths (group width C / 3 = 32, 64, 128, 256) at (windows, r) = (2, 3), and per-clip pairing (groups = 2) at
+# (4, 3) for the narrowest and the widest: test_hip_deform_{sample,attention}_bwd_side_view_widths hold the values.
+# deform_sample_bwd has one arithmetic form; deform_attention_bwd runs both.
+for _c in (96, 192, 384, 768):
+    for _nq, _g in ((2, 1), (4, 2)) if _c in (96, 768) else ((2, 1),):
+        _tag = f"-groups{_g}" if _g > 1 else ""
+        if (_nq, _c) != (2, 192):
+            case(f"deform_sample_bwd/nq{_nq}-r3-c{_c}{_tag}")(_sample_bwd_case(_nq, 3, _c, _g))
+        for _math in ("fp32", "bf16"):
+            case(f"deform_attention_bwd/b{_nq}-r3-c{_c}-{_math}{_tag}")(_attention_bwd_case(_nq, 3, _c, _math, _g))
+
+
+for _n, _c in ((3, 256), (6, 32), (1, 32), (1, 64), (6, 64), (1, 128), (6, 128), (1, 256), (6, 256)):
+    # test_hip_dwconv5_window_fwd_bwd; (n, cg) with cg = C / 3 of the four side-view widths at one window and at six
     @case(f"dwconv5_window/{_n}x{_c}")
     def _(n=_n, c=_c):
         i = {"x": seeded_randn(100, n, 49, c), "w": (seeded_randn(101, c, 1, 5, 5) / 5).reshape(c, 25), "b": seeded_randn(102, c)}
@@ -910,7 +1092,7 @@ for _n in (1, 3, 1023):          # test_hip_adamw_matches_torch / test_hip_sgd_m
 
 # ================================================================================================ GPU: the one test
 # results that a tensor method allocated, not the proxy: compared bitwise, invisible to check (b) (see the docstring)
-UNGUARDED_RESULTS = {"deform_sample_bwd/nq2-r3-c192": {"dpos"}}
+UNGUARDED_RESULTS = {c.id: {"dpos"} for c in CASES if c.id.startswith("deform_sample_bwd/")}
 _HIP_ERROR = []          # the first case whose run raised inside the library: nothing more is launched in this process after it
 
 
@@ -951,7 +1133,8 @@ def test_memory_discipline(case_, monkeypatch):
             _HIP_ERROR.append(case_.id)
         raise
     assert unguarded == UNGUARDED_RESULTS.get(case_.id, set())                        # every other output was seen by check (b)
-    for pattern, outs in zip(GA.PATTERNS, runs):                                      # placement independence, bit for bit
+    assert len(runs) == len(GA.PASSES)
+    for pattern, outs in zip(GA.PASSES, runs):                                        # placement independence, bit for bit
         assert set(outs) == set(plain)
         for name, out in outs.items():
             got, want = GA._bytes(out.cpu()), GA._bytes(plain[name])
@@ -961,4 +1144,185 @@ def test_memory_discipline(case_, monkeypatch):
             assert got.shape == want.shape
             diff = (got != want).any(-1)
             assert not bool(diff.any()), (f"{name}: {int(diff.sum())} of {diff.numel()} elements differ from the unguarded run under "
-                                          f"pattern {pattern:#x}; first at {diff.nonzero()[0].tolist()}")
+                                          f"{GA.pass_name(pattern)}; first at {diff.nonzero()[0].tolist()}")
+
+
+# ================================================================================================ GPU: the whole model
+# (id, training tape?, batch, switches).  T = 3 throughout: the smallest clip that launches every kernel of its mode.
+ModelConfig = namedtuple("ModelConfig", "id train batch storage attn cva mlp coupling")
+MODEL_CONFIGS = [
+    ModelConfig("eval-fp32-b1", False, 1, "fp32", "fp32", "fp32", False, "batch"),
+    ModelConfig("eval-bf16-storage-b1", False, 1, "bf16", "bf16", "bf16", False, "batch"),
+    ModelConfig("train-fp32-b1", True, 1, "fp32", "fp32", "fp32", False, "batch"),
+    ModelConfig("train-bf16-attention-fused-mlp-clip-b2", True, 2, "fp32", "bf16", "bf16", True, "clip"),
+]
+MODEL_T = 3
+MODEL_MODULES = ("mumpy_hip.ops", "mumpy_hip.autograd", "models.modules.swinTransformer", "models.modules.blocks",
+                 "models.encoder.multiTemporalViewEncoder")
+
+
+@functools.lru_cache(maxsize=None)
+def _three_view_model():
+    """Encoder and Decoder as tests/test_swin_backward._hip_full_backward builds them, once for the four configurations."""
+    from models.decoder.decoder import Decoder
+    from models.encoder.encoder import Encoder
+    enc = fill_module_(Encoder(num_frames=MODEL_T)).eval().cuda()
+    dec = fill_module_(Decoder(input_token_temporal_dims=[1, 1, MODEL_T])).eval().cuda()
+    return enc, dec
+
+
+@contextlib.contextmanager
+def _model_switches(cfg):
+    """The process-wide switches of one configuration; every one of them is put back on the way out, also on failure."""
+    from mumpy_hip import ops
+    before = (ops.storage(), ops.matrix_math(), ops.attention_math(), ops.cva_math(), ops.mlp_fusion(), ops.clip_coupling())
+    try:
+        ops.set_storage(cfg.storage)
+        ops.set_attention_math(cfg.attn)
+        ops.set_cva_math(cfg.cva)
+        ops.set_mlp_fusion(cfg.mlp)
+        ops.set_clip_coupling(cfg.coupling)
+        yield
+    finally:
+        ops.set_storage(before[0])
+        ops.set_matrix_math(before[1])
+        ops.set_attention_math(before[2])
+        ops.set_cva_math(before[3])
+        ops.set_mlp_fusion(before[4])
+        ops.set_clip_coupling(before[5])
+
+
+def _scalars(args):
+    """The scalar arguments of a launch: everything that is not an address (tensor, workspace and stream handles are 64-bit values)."""
+    return tuple(a for a in args if isinstance(a, float) or (isinstance(a, int) and abs(a) < 1 << 32))
+
+
+def _watching_call(real_call, launches, first, guard=None, watch=None, sync=lambda: None):
+    """ops._call, counted in launches[0].  With watch (indices of guarded blocks): after every launch the device is synchronised and
+    the bands of those blocks -- the ones that exist by then; allocation order is deterministic, so the indices of an earlier run
+    carry over -- are looked at, until one has changed: first[0] = (entry point, its scalar arguments, band_hits)."""
+    def call(name, *args, work=0.0):
+        real_call(name, *args, work=work)
+        launches[0] += 1
+        if watch and not first:
+            sync()
+            hits = guard.band_hits(only=[i for i in watch if i < len(guard.log)])
+            if hits:
+                first.append((name, _scalars(args), hits))
+    return call
+
+
+def test_the_watching_call_names_the_first_launch_that_damaged_a_band():
+    """CPU: the report path of test_whole_model_under_the_guard, on a fake launch that writes past its output on its third call."""
+    guard, launches, first, bufs = GA.Guard(GA.CYCLE), [0], [], []
+
+    def fake_launch(name, address, n, scale, table, stream, work=0.0):
+        out = guard.torch.empty(n, dtype=torch.float32)
+        bufs.append(out)
+        out.fill_(scale)
+        if len(bufs) == 3:
+            out.as_strided((1,), (1,), out.storage_offset() + n).fill_(scale)         # one element too far
+    call = _watching_call(fake_launch, launches, first, guard, watch=[2, 3])
+    for i in range(5):
+        call(f"entry{i}", 0x7F0000001000 + i, 4 + i, 0.5, None, 0x55550000AAAA, work=1.0)
+    assert launches == [5] and len(guard.log) == 5
+    assert first == [("entry2", (6, 0.5), [(2, "fake_launch", (6,), 0, 4)])]                # addresses and handles are left out
+    quiet = []
+    call = _watching_call(lambda name, *a, work=0.0: None, launches, quiet, guard, watch=[0, 1])
+    call("entry5", 1, 2)
+    assert quiet == [] and launches == [6]                                                   # undamaged blocks report nothing
+
+
+def _model_run(monkeypatch, cfg, x, target, guard=None, watch=None):
+    """One forward (and backward) of the configuration -> ({"logits": ..., "grad/<name>": ...} as copies, launches, first damaging
+    launch or None).  guard: run with its proxy installed in MODEL_MODULES, x and target in guarded blocks.  watch: indices of
+    guarded blocks; after every launch the device is synchronised and their bands are looked at, and the first launch after which
+    one changed is returned as (entry point, scalar arguments, band_hits)."""
+    import importlib
+    from mumpy_hip import ops, state
+    from mumpy_hip.autograd import decoder_train, encoder_train
+    enc, dec = _three_view_model()
+    params = [(f"{which}.{n}", p) for which, mod in (("enc", enc), ("dec", dec)) for n, p in mod.named_parameters()]
+    for _, p in params:
+        p.grad = None
+    state.bump_weights_epoch()                                           # derived weights are rebuilt inside this run's allocations
+    launches, first = [0], []
+    counting_call = _watching_call(ops._call, launches, first, guard, watch, torch.cuda.synchronize)
+
+    def run(xd, td):
+        if cfg.train:
+            fx, vx, dx = encoder_train(enc, xd, coupling="clip" if cfg.coupling == "clip" else None)
+            lg, _ = decoder_train(dec, fx, vx, dx)
+            lg.backward(ops.mask_loss(lg.detach(), td)[1])
+        else:
+            with torch.no_grad():
+                lg, _ = dec(*enc(xd))
+        torch.cuda.synchronize()                                         # side streams included
+        out = {"logits": lg.detach().clone()}                            # copies outside the guard, compared on the device
+        if cfg.train:
+            assert all(p.grad is not None for _, p in params)
+            out.update({f"grad/{n}": p.grad.detach().clone() for n, p in params})
+        return out
+    try:
+        with monkeypatch.context() as m, _model_switches(cfg):
+            m.setattr(ops, "_call", counting_call)
+            if guard is None:
+                out = run(x.cuda(), target.cuda())
+            else:
+                with guard.installed(monkeypatch, *(importlib.import_module(n) for n in MODEL_MODULES)):
+                    out = run(guard.tensor(x), guard.tensor(target))
+    finally:
+        for _, p in params:
+            p.grad = None
+        state.bump_weights_epoch()                                       # nothing derived inside a guard outlives it in use
+    return out, launches[0], first[0] if first else None
+
+
+def _first_difference(a, b):
+    assert list(a) == list(b)
+    return next((n for n in a if not GA.same_bits(a[n], b[n])), None)
+
+
+MODEL_COUNTS = {}        # id -> (launches, [guarded blocks per pass]); printed by the test, quoted in the module docstring
+
+
+@gpu
+@pytest.mark.parametrize("cfg", MODEL_CONFIGS, ids=[c.id for c in MODEL_CONFIGS])
+def test_whole_model_under_the_guard(cfg, monkeypatch):
+    """The three-view model's own forward and training tape, every allocation of MODEL_MODULES in a guarded block: after each of the
+    three passes every band of every block is intact (kept GEMM workspaces and side-stream allocations included; the device is
+    synchronised first), the clip and the target are unchanged, and the logits -- on the tape also every parameter gradient -- are
+    bitwise those of the unguarded run.  Precondition: two unguarded runs are bitwise equal.  Check (b) is not applied:
+    intermediates are not outputs.  On a band failure the configuration runs once more with the damaged blocks watched after every
+    launch, and the failure names the first entry point after which a band changed."""
+    if _HIP_ERROR:
+        pytest.fail(f"not run: the case {_HIP_ERROR[0]} hit an error inside a launch earlier in this process")
+    dev = torch.device("cuda:0")
+    x = seeded_randn(990, cfg.batch, MODEL_T, 3, 224, 224)
+    target = (torch.rand(cfg.batch, 1, 224, 224, generator=torch.Generator().manual_seed(7)) < 0.1).float()
+    try:
+        plain, launches, _ = _model_run(monkeypatch, cfg, x, target)
+        again, launches2, _ = _model_run(monkeypatch, cfg, x, target)
+        assert launches == launches2 and _first_difference(plain, again) is None, \
+            f"two unguarded runs differ; first at {_first_difference(plain, again)}"
+        blocks = []
+        for pattern in GA.PASSES:
+            guard = GA.Guard(pattern, dev)
+            out, n, _ = _model_run(monkeypatch, cfg, x, target, guard=guard)
+            blocks.append(len(guard.log))
+            hits = guard.band_hits()
+            if hits:
+                _, _, first = _model_run(monkeypatch, cfg, x, target, guard=GA.Guard(pattern, dev), watch=[h[0] for h in hits])
+                pytest.fail(f"guard band overwritten ({GA.pass_name(pattern)}): [(block, site, shape, bytes in front, bytes behind)] = "
+                            f"{hits[:8]}{' ...' if len(hits) > 8 else ''}; first launch after which one of them changed: {first}")
+            guard.check({})                                              # (a) again, and (c): the clip and the target are unchanged
+            assert n == launches, f"{n} launches under the guard, {launches} without"
+            differs = _first_difference(plain, out)
+            assert differs is None, f"{differs} differs from the unguarded run under {GA.pass_name(pattern)}"
+            del guard, out
+    except RuntimeError as e:
+        if any(s in str(e) for s in ("HIP", "hip", "rc=")):
+            _HIP_ERROR.append(f"whole model/{cfg.id}")
+        raise
+    MODEL_COUNTS[cfg.id] = (launches, blocks)
+    print(f"whole model {cfg.id}: {launches} launches, guarded blocks per pass {blocks}, {len(plain)} tensors compared")

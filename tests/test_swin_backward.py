@@ -714,6 +714,56 @@ def test_hip_deform_attention_bwd(b1, r, c):
     assert rel_err(qg.grad.cpu(), qr.grad) < 2e-5 and rel_err(kvg.grad.cpu(), kvr.grad) < 2e-5
 
 
+SIDE_VIEW_WIDTHS = [96, 192, 384, 768]          # the side views' four stages: group width C / 3 = 32, 64, 128, 256
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", SIDE_VIEW_WIDTHS)
+def test_hip_deform_sample_bwd_side_view_widths(c):
+    """test_hip_deform_sample_bwd at (nq, r) = (2, 3) for every side-view width, against autograd of the same expression in fp64,
+    under that test's bars (tests/test_memory_discipline.py runs these launches inside guard bands)."""
+    from mumpy_hip.autograd import DeformSampleFn
+    nq, r = 2, 3
+    b2 = nq * r
+    x2 = seeded_randn(110, b2, 49, c)
+    pos = (seeded_randn(111, nq, 3, 49, 2) * 0.7).clamp(-1.3, 1.3)
+    ds = seeded_randn(112, b2, 49, c)
+    xr, pr = x2.double().requires_grad_(True), pos.double().requires_grad_(True)
+    ref = O.bilinear_sample_window(xr, pr[torch.arange(b2) % nq])
+    ref.backward(ds.double())
+    xg, pg = x2.cuda().requires_grad_(True), pos.cuda().requires_grad_(True)
+    out = DeformSampleFn.apply(xg, pg)
+    out.backward(ds.cuda())
+    errs = rel_err(out.detach().cpu(), ref.detach()), rel_err(xg.grad.cpu(), xr.grad), rel_err(pg.grad.cpu(), pr.grad)
+    print(f"deform_sample_bwd C={c} vs fp64: out {errs[0]:.2e}, dx2 {errs[1]:.2e}, dpos {errs[2]:.2e}")
+    assert errs[0] < 1e-5 and errs[1] < 2e-5 and errs[2] < 5e-5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c", SIDE_VIEW_WIDTHS)
+def test_hip_deform_attention_bwd_side_view_widths(c):
+    """test_hip_deform_attention_bwd at (b1, r) = (2, 3) for every side-view width, against autograd of the same expression in fp64,
+    under that test's bars."""
+    from mumpy_hip.autograd import DeformAttentionFn
+    b1, r = 2, 3
+    b2, nh = b1 * r, c // 32
+    q, kv, do = seeded_randn(120, b1, 49, c), seeded_randn(121, b2, 49, 2 * c), seeded_randn(122, b1, 49, c)
+    qr, kvr = q.double().requires_grad_(True), kv.double().requires_grad_(True)
+    sel = torch.arange(b2) % b1
+    qh = qr[sel].reshape(b2, 49, nh, 32).transpose(1, 2)
+    k = kvr[..., :c].reshape(b2, 49, nh, 32).transpose(1, 2)
+    v = kvr[..., c:].reshape(b2, 49, nh, 32).transpose(1, 2)
+    attn = ((qh @ k.transpose(-2, -1)) * 32 ** -0.5).softmax(-1)
+    ref = (attn @ v).transpose(1, 2).reshape(b2, 49, c).reshape(b1, r, 49, c).sum(1)
+    ref.backward(do.double())
+    qg, kvg = q.cuda().requires_grad_(True), kv.cuda().requires_grad_(True)
+    out = DeformAttentionFn.apply(qg, kvg, 32 ** -0.5)
+    out.backward(do.cuda())
+    errs = rel_err(out.detach().cpu(), ref.detach()), rel_err(qg.grad.cpu(), qr.grad), rel_err(kvg.grad.cpu(), kvr.grad)
+    print(f"deform_attention_bwd C={c} vs fp64: out {errs[0]:.2e}, dq {errs[1]:.2e}, dkv {errs[2]:.2e}")
+    assert errs[0] < 1e-5 and errs[1] < 2e-5 and errs[2] < 2e-5
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("b1,r,c", [(4, 1, 96), (2, 3, 192), (2, 5, 96)])
 def test_hip_swin_dattention_backward_vs_oracle(b1, r, c):
