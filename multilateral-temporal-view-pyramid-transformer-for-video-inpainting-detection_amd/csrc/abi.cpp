@@ -14,6 +14,7 @@
 #include "../../include/mumpy_hip_ext9.h"
 #include "../../include/mumpy_hip_ext10.h"
 #include "../../include/mumpy_perturb.h"
+#include "../../include/mumpy_photometric.h"
 
 namespace mumpy {
 static thread_local char g_err[512] = "";
@@ -87,5 +88,6 @@ extern "C" int mumpy_ext8_version(void) { return MUMPY_EXT8_VERSION; }
 extern "C" int mumpy_ext9_version(void) { return MUMPY_EXT9_VERSION; }
 extern "C" int mumpy_ext10_version(void) { return MUMPY_EXT10_VERSION; }
 extern "C" int mumpy_perturb_version(void) { return MUMPY_PERTURB_VERSION; }
+extern "C" int mumpy_photometric_version(void) { return MUMPY_PHOTOMETRIC_VERSION; }
 extern "C" const char* mumpy_last_error(void) { return mumpy::g_err; }
 extern "C" const char* mumpy_last_route(void) { return mumpy::format_route(); }

@@ -408,9 +408,13 @@ class AugmentedInput:
     then the stage above reading the canvas: all of it capturable.  The per-clip tables are then CANVAS-relative --
     clip_tables((L, L), L, op, box), clip_warp_params((L, L), L, draw) -- because the object does the source -> canvas resize itself.
     load(..., perturb=[None | ("jpeg", q) | ("blur", r) per clip]): all T frames of a clip share the clip's setting; masks are never
-    perturbed.  perturb=False (the default) is the object as it was: the same buffers, the same single launch."""
+    perturbed.  perturb=False (the default) is the object as it was: the same buffers, the same single launch.
+    photometric=True (needs perturb=True): the nine photometric kinds of mumpy_hip.photometric as well -- one {kind, value, 0, 0} row
+    per frame more in the parameter block (still one upload) and one more in-place launch on the canvas after the blur
+    (ops.photometric_u8); load(perturb=[...]) then also takes ("contrast", 1.4), ("equalize", None), ... per clip.  Statistics are per
+    frame, as Pillow's are per image.  photometric=False (the default) is the object as it was: the same block, the same launches."""
 
-    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None, warp=False, perturb=False):
+    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None, warp=False, perturb=False, photometric=False):
         import torch
         from . import ops
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5 or x.shape[2] != 3 or x.shape[3] != x.shape[4] or not x.is_contiguous():
@@ -434,13 +438,19 @@ class AugmentedInput:
         shapes = dict(tab_a=(b, L), tab_b=(b, L), pos_y=(b, L), pos_x=(b, L), coef_y=(b, L, 4), coef_x=(b, L, 4), affine=(b, 8), swap=(b,),
                       mode=(b,))
         self._fields = tuple(shapes) if self.warp else ("tab_a", "tab_b", "swap")
-        self.perturb = bool(perturb)
+        self.perturb, self.photometric = bool(perturb), bool(photometric)
+        if self.photometric and not self.perturb:
+            raise ValueError("AugmentedInput: photometric=True needs perturb=True (the operations act on the canvas)")
         if self.perturb:
             # qtab: (b, 2, 64) uint16 = 64 words per clip; blur: {r, ww, fw, on} per frame; sel: the clip's table or -1 per frame.
             # qtab and blur are loaded 16 bytes at a time: they go in front of the first one-word-per-clip array
             shapes.update(qtab=(b, 64), blur=(b * t, 4), sel=(b * t,))
             at = self._fields.index("swap")
             self._fields = self._fields[:at] + ("qtab", "blur") + self._fields[at:] + ("sel",)
+        if self.photometric:                                          # {kind, value, 0, 0} per frame, loaded 16 bytes at a time too
+            shapes.update(photo=(b * t, 4))
+            at = self._fields.index("swap")
+            self._fields = self._fields[:at] + ("photo",) + self._fields[at:]
         self._where, n = {}, 0
         for name in self._fields:
             self._where[name] = (n, n + int(np.prod(shapes[name])), shapes[name])
@@ -459,6 +469,8 @@ class AugmentedInput:
             self.mask_canvas = torch.empty(self.nmasks, L, L, dtype=u8, device=dev) if target is not None else None
             lib = ops._lib()
             need = [int(lib.mumpy_jpeg_roundtrip_workspace_bytes(b * t, L, L)), int(lib.mumpy_gaussian_blur_workspace_bytes(b * t, L, L))]
+            if self.photometric:
+                need.append(int(lib.mumpy_photometric_workspace_bytes(b * t, L, L)))
             if min(need) < 0:
                 raise RuntimeError(f"AugmentedInput: a canvas of {L}x{L} is refused: {lib.mumpy_last_error().decode()}")
             self._perturb_ws = torch.empty(max(need), dtype=u8, device=dev)
@@ -476,8 +488,10 @@ class AugmentedInput:
             dst.copy_(pinned, non_blocking=True)
 
     def _perturb_rows(self, perturb):
-        """-> (qtab (b, 64) words, blur (b * T, 4), sel (b * T,)) int32 of one setting per clip (None: the clip passes through)."""
+        """-> (qtab (b, 64) words, blur (b * T, 4), sel (b * T,), photo (b * T, 4)) int32 of one setting per clip (None: the clip passes
+        through)."""
         from .perturb import box_params, check_spec, jpeg_tables
+        from .photometric import params_row
         b, t = self.nclips, self.T
         perturb = [None] * b if perturb is None else list(perturb)
         if len(perturb) != b:
@@ -485,6 +499,7 @@ class AugmentedInput:
         qtab = np.ones((b, 2, 64), np.uint16)
         blur = np.tile(np.array([0, 1 << 24, 0, 0], np.int64), (b, t, 1))
         sel = np.full((b, t), -1, np.int32)
+        photo = np.zeros((b, t, 4), np.int32)
         for c, spec in enumerate(perturb):
             steps = check_spec(spec, "AugmentedInput.load: perturb")
             if len(steps) > 1:
@@ -492,16 +507,22 @@ class AugmentedInput:
             for kind, value in steps:
                 if kind == "jpeg":
                     qtab[c], sel[c] = jpeg_tables(value), c
-                else:
+                elif kind == "blur":
                     blur[c] = box_params(value)
-        return qtab.reshape(b, 128).view(np.int32), blur.astype(np.int32).reshape(b * t, 4), sel.reshape(b * t)
+                elif not self.photometric:
+                    raise ValueError(f"AugmentedInput.load: perturb: ({kind!r}, ...) needs an input built with photometric=True")
+                else:
+                    photo[c] = params_row(kind, value)
+        return qtab.reshape(b, 128).view(np.int32), blur.astype(np.int32).reshape(b * t, 4), sel.reshape(b * t), photo.reshape(b * t, 4)
 
     def load(self, frames_u8, masks_u8, params, perturb=None):
         import torch
         b, L = self.nclips, self.L
         if perturb is not None and not self.perturb:
             raise RuntimeError("AugmentedInput.load: perturb= needs an input built with perturb=True")
-        extra = dict(zip(("qtab", "blur", "sel"), self._perturb_rows(perturb))) if self.perturb else {}
+        extra = dict(zip(("qtab", "blur", "sel", "photo"), self._perturb_rows(perturb))) if self.perturb else {}
+        if not self.photometric:
+            extra.pop("photo", None)
         st = self._stage[self._turn]
         self._turn ^= 1
         st["done"].synchronize()                 # host-side only: the upload of two loads ago has left this staging set
@@ -550,6 +571,8 @@ class AugmentedInput:
                 ops.resize_nearest_u8(self.masks, side, out=masks, channels=1)
             ops.jpeg_roundtrip_u8(frames, self.qtab, sel=self.sel, out=frames, workspace=self._perturb_ws)
             ops.gaussian_blur_u8(frames, self.blur, out=frames, workspace=self._perturb_ws)
+            if self.photometric:
+                ops.photometric_u8(frames, self.photo, out=frames, workspace=self._perturb_ws)
         if self.warp:
             ops.augment_warp_u8(frames, self.tab_a, self.tab_b, self.swap, self.mode, self.pos_y, self.pos_x, self.coef_y, self.coef_x,
                                 self.affine, masks=masks, out=self.x, target=target, mean=self.mean, std=self.std)

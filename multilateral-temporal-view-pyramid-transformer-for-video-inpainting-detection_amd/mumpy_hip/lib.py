@@ -201,6 +201,13 @@ PERTURB = Surface("mumpy_perturb.h", "mumpy_perturb_version", 1, {
     "mumpy_resize_nearest_u8_fwd": [c_f, c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_i, c_i, c_f],
 })
 
+# include/mumpy_photometric.h: the photometric operations of uint8 frames, a surface of its own for the same reason
+# (tests/test_perturb_host.py pins the names of mumpy_perturb.h); tests/test_photometric_host.py holds it to its header and exports.
+PHOTOMETRIC = Surface("mumpy_photometric.h", "mumpy_photometric_version", 1, {
+    "mumpy_photometric_workspace_bytes": [c_l, c_i, c_i],
+    "mumpy_photometric_u8_fwd": [c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_f],
+})
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -240,7 +247,7 @@ def load_library():
     lib.mumpy_last_error.restype = ctypes.c_char_p
     lib.mumpy_last_route.restype = ctypes.c_char_p      # (AttributeError here or below = the library is stale: fail loudly)
     lib.mumpy_last_route.argtypes = []
-    for s in SURFACES + [PERTURB]:
+    for s in SURFACES + [PERTURB, PHOTOMETRIC]:
         version = getattr(lib, s.version_fn)
         version.restype, version.argtypes = c_i, []
         if version() != s.version:

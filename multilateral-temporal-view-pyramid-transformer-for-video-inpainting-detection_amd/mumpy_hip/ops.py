@@ -1511,6 +1511,42 @@ def gaussian_blur_u8(frames, radius_or_params, out=None, workspace=None):
     return out
 
 
+def photometric_params(spec_or_rows, nimg, device):
+    """(nimg, 4) int32 on the device, {kind, value, 0, 0} per image: one (kind, value) for every image, or one per image (a sequence
+    of nimg pairs; None means pass through) -- encoded by mumpy_hip.photometric.params_row and uploaded."""
+    import numpy as np
+    from .photometric import params_row
+    if spec_or_rows is None or (isinstance(spec_or_rows, tuple) and len(spec_or_rows) == 2 and isinstance(spec_or_rows[0], str)):
+        rows = [params_row(*(spec_or_rows or ("none", None)))] * nimg
+    else:
+        rows = [params_row(*(s or ("none", None))) for s in spec_or_rows]
+        if len(rows) != nimg:
+            raise RuntimeError(f"mumpy_hip: photometric_params: {len(rows)} settings for {nimg} images")
+    return torch.from_numpy(np.asarray(rows, dtype=np.int32).reshape(nimg, 4)).to(device)
+
+
+def photometric_u8(frames, spec_or_params, out=None, workspace=None):
+    """One photometric operation of Pillow per image on the GPU (mumpy_photometric_u8_fwd, include/mumpy_photometric.h): frames
+    (..., H, W, 3) uint8 -> the same shape, bit for bit ImageOps.autocontrast / invert / equalize / solarize / posterize or
+    ImageEnhance.Contrast / Color / Brightness / Sharpness (mumpy_hip.photometric.apply is the numpy statement; statistics are per
+    image).  spec_or_params: a (kind, value) for every image (its rows are uploaded by this call: pass a tensor inside a graph
+    capture), or a device tensor (nimg, 4) int32 of mumpy_hip.photometric.params_row rows (`photometric_params`), read when the
+    kernels run; kind 0 copies that image through.  out= and workspace= as in jpeg_roundtrip_u8
+    (mumpy_photometric_workspace_bytes); out may be frames itself for every kind."""
+    who = "photometric_u8"
+    nimg, h, w = _frames_u8(frames, who)
+    params = spec_or_params if isinstance(spec_or_params, torch.Tensor) else photometric_params(spec_or_params, nimg, frames.device)
+    _chk_exact(params, "params", torch.int32, (nimg, 4), who)
+    out = _perturb_out(frames, out, who)
+    ws, step = _perturb_chunks("mumpy_photometric_workspace_bytes", nimg, h, w, workspace, who, frames.device)
+    src, dst = frames.view(nimg, h, w, 3), out.view(nimg, h, w, 3)
+    for i in range(0, nimg, step):
+        m = min(step, nimg - i)
+        _call("mumpy_photometric_u8_fwd", _p(src[i:i + m]), _p(dst[i:i + m]), _p(params[i:i + m]), _p(ws), ws.numel(), m, h, w,
+              _stream(), work=float(6 * m * h * w))
+    return out
+
+
 def resize_nearest_u8(frames, size, out=None, channels=3):
     """Image.resize((W, H), Image.NEAREST) of RGB frames on the GPU (mumpy_resize_nearest_u8_fwd, include/mumpy_perturb.h): frames
     (..., Hs, Ws, 3) uint8 -> (..., H, W, 3) uint8, size = (H, W), through the tables of mumpy_resize_nearest_table (cached per

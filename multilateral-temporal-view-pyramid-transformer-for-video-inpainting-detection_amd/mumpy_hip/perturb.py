@@ -203,32 +203,41 @@ BLUR_RADIUS = (0.0, 5.0)          # randaugment.py:555, 588: (RandomGaussianBlur
 
 
 def draw(rng, kinds=("jpeg", "blur")):
-    """One condition, ("jpeg", q) or ("blur", r), the kind uniform over `kinds`: the reference's ranges, not its RNG stream."""
+    """One condition, ("jpeg", q), ("blur", r) or a photometric (kind, value) when `kinds` names one (mumpy_hip.photometric.draw), the
+    kind uniform over `kinds`: the reference's ranges, not its RNG stream."""
+    from . import photometric
     kinds = tuple(kinds)
-    if not kinds or any(k not in ("jpeg", "blur") for k in kinds):
-        raise ValueError(f"draw: kinds={kinds!r} must be a non-empty choice of \"jpeg\" and \"blur\"")
+    if not kinds or any(k not in ("jpeg", "blur") and (k == "none" or k not in photometric.KINDS) for k in kinds):
+        raise ValueError(f"draw: kinds={kinds!r} must be a non-empty choice of \"jpeg\", \"blur\" and the photometric kinds")
     kind = kinds[int(rng.integers(0, len(kinds)))]
     if kind == "jpeg":
         return "jpeg", int(rng.integers(*JPEG_QUALITY))
-    return "blur", float(rng.uniform(*BLUR_RADIUS))
+    if kind == "blur":
+        return "blur", float(rng.uniform(*BLUR_RADIUS))
+    return photometric.draw(rng, (kind,))
 
 
 def check_spec(spec, who="perturb"):
-    """None | ("jpeg", q) | ("blur", r) | a list of those -> the list [(kind, value), ...], refused unless every entry is one of the
-    two kinds with a quality in 1 .. 100 / a finite radius >= 0."""
+    """None | ("jpeg", q) | ("blur", r) | (a photometric kind, its value) | a list of those -> the list [(kind, value), ...], refused
+    unless every entry is a two-tuple of a known kind with a quality in 1 .. 100 / a finite radius >= 0 / the value
+    mumpy_hip.photometric.check_kind takes for that kind (None for autocontrast, equalize and invert)."""
+    from . import photometric
     if spec is None:
         return []
     items = [spec] if isinstance(spec, tuple) and len(spec) == 2 and isinstance(spec[0], str) else spec
     if isinstance(items, (str, bytes)) or not hasattr(items, "__iter__"):
-        raise ValueError(f"{who}: {spec!r} must be None, (\"jpeg\", q), (\"blur\", r) or a list of those")
+        raise ValueError(f"{who}: {spec!r} must be None, (\"jpeg\", q), (\"blur\", r), a photometric (kind, value) or a list of those")
     out = []
     for it in items:
-        if not (isinstance(it, (tuple, list)) and len(it) == 2 and it[0] in ("jpeg", "blur")):
-            raise ValueError(f"{who}: {it!r} must be (\"jpeg\", quality) or (\"blur\", radius)")
+        if not (isinstance(it, (tuple, list)) and len(it) == 2 and isinstance(it[0], str)
+                and (it[0] in ("jpeg", "blur") or (it[0] in photometric.KINDS and it[0] != "none"))):
+            raise ValueError(f"{who}: {it!r} must be (\"jpeg\", quality), (\"blur\", radius) or a photometric (kind, value)")
         if it[0] == "jpeg":
             jpeg_tables(it[1])
             out.append(("jpeg", int(it[1])))
-        else:
+        elif it[0] == "blur":
             box_params(it[1])
             out.append(("blur", float(it[1])))
+        else:
+            out.append(photometric.check_kind(it[0], it[1], who))
     return out

@@ -201,7 +201,9 @@ class VideoPredictor(GraphedForward):
     place, on the uploaded video at its own size (ops.jpeg_roundtrip_u8 / ops.gaussian_blur_u8: Pillow's save(format="JPEG",
     quality=q) + re-open and ImageFilter.GaussianBlur(r), bit for bit), before the first batch -- what an unperturbed predictor
     computes when it is fed the frames Pillow processed on the host.  A robustness table is
-    `for q in (90, 70, 50): VideoPredictor(..., perturb=("jpeg", q)).predict(frames, gt)`.  The predictor owns the tables and a
+    `for q in (90, 70, 50): VideoPredictor(..., perturb=("jpeg", q)).predict(frames, gt)`.  The nine photometric kinds of
+    mumpy_hip.photometric -- ("contrast", 1.4), ("equalize", None), ... -- may stand anywhere in the list, mixed with the two
+    (ops.photometric_u8: Pillow's ImageOps / ImageEnhance, bit for bit, statistics per frame).  The predictor owns the tables and a
     workspace of perturb_chunk frames; a bad spec is refused here.  perturb=None (the default) allocates nothing and launches
     nothing: the captured graph, the masks, the bank, the counts and the metric vector are what they were without the option."""
 
@@ -272,9 +274,12 @@ class VideoPredictor(GraphedForward):
                     need.append(int(lib.mumpy_jpeg_roundtrip_workspace_bytes(chunk, hs, ws)))
                     self.perturb.append((kind, value, ops.jpeg_tables_u16(jpeg_tables(value)[None], dev),
                                          torch.zeros(chunk, device=dev, dtype=torch.int32)))
-                else:
+                elif kind == "blur":
                     need.append(int(lib.mumpy_gaussian_blur_workspace_bytes(chunk, hs, ws)))
                     self.perturb.append((kind, value, ops.blur_params(value, chunk, dev), None))
+                else:                                                # a photometric kind: one row per frame of a chunk
+                    need.append(int(lib.mumpy_photometric_workspace_bytes(chunk, hs, ws)))
+                    self.perturb.append((kind, value, ops.photometric_params((kind, value), chunk, dev), None))
             if min(need) < 0:
                 raise ValueError(f"VideoPredictor: perturb: frames of {hs}x{ws} are refused: {lib.mumpy_last_error().decode()}")
             self._perturb_ws = torch.empty(max(need), device=dev, dtype=torch.uint8)
@@ -375,8 +380,10 @@ class VideoPredictor(GraphedForward):
                 m = part.shape[0]
                 if kind == "jpeg":
                     ops.jpeg_roundtrip_u8(part, setting, sel=sel[:m], out=part, workspace=self._perturb_ws)
-                else:
+                elif kind == "blur":
                     ops.gaussian_blur_u8(part, setting[:m], out=part, workspace=self._perturb_ws)
+                else:
+                    ops.photometric_u8(part, setting[:m], out=part, workspace=self._perturb_ws)
 
     def _resize_gt(self, gt_u8, n):
         """gt[:n] = Image.resize((224, 224), BILINEAR) of the annotations (ops.resize_bilinear_u8), issued on the current stream ahead
