@@ -15,6 +15,7 @@
 #include "../../include/mumpy_hip_ext10.h"
 #include "../../include/mumpy_perturb.h"
 #include "../../include/mumpy_photometric.h"
+#include "../../include/mumpy_geometric.h"
 
 namespace mumpy {
 static thread_local char g_err[512] = "";
@@ -89,5 +90,6 @@ extern "C" int mumpy_ext9_version(void) { return MUMPY_EXT9_VERSION; }
 extern "C" int mumpy_ext10_version(void) { return MUMPY_EXT10_VERSION; }
 extern "C" int mumpy_perturb_version(void) { return MUMPY_PERTURB_VERSION; }
 extern "C" int mumpy_photometric_version(void) { return MUMPY_PHOTOMETRIC_VERSION; }
+extern "C" int mumpy_geometric_version(void) { return MUMPY_GEOMETRIC_VERSION; }
 extern "C" const char* mumpy_last_error(void) { return mumpy::g_err; }
 extern "C" const char* mumpy_last_route(void) { return mumpy::format_route(); }

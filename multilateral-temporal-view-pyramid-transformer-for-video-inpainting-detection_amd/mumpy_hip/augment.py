@@ -18,6 +18,11 @@ interpolates on the canvas those tables describe (`ops.augment_warp_u8`, mumpy_a
 RandomScaleCrop is Pillow's 8-bit BICUBIC restated in integers, bit for bit; RandomRotate is a plain fp32 bilinear warp, not
 cv2.warpAffine's fixed-point one -- how far the two differ is not measured.
 
+The affine group of the same file (ShearX .. Rotate) and Cutout, which the reference lists beside those and keeps commented out, move
+the mask with the frames and are not index tables of this kind either (a shear has no per-axis table, a rotation by 17 degrees no
+swap bit): they run before this stage, on the canvas, as mumpy_hip.geometric / ops.geometric_u8 (include/mumpy_geometric.h) behind
+AugmentedInput(perturb=True, geometric=True), bit for bit Pillow's fixed-point walk.
+
 This module is host code (numpy + the library's host helper mumpy_resize_nearest_table) and imports without a GPU; only
 AugmentedInput touches the device.  The samplers follow the reference's distributions, not its RNG stream."""
 import collections
@@ -412,9 +417,19 @@ class AugmentedInput:
     photometric=True (needs perturb=True): the nine photometric kinds of mumpy_hip.photometric as well -- one {kind, value, 0, 0} row
     per frame more in the parameter block (still one upload) and one more in-place launch on the canvas after the blur
     (ops.photometric_u8); load(perturb=[...]) then also takes ("contrast", 1.4), ("equalize", None), ... per clip.  Statistics are per
-    frame, as Pillow's are per image.  photometric=False (the default) is the object as it was: the same block, the same launches."""
+    frame, as Pillow's are per image.  photometric=False (the default) is the object as it was: the same block, the same launches.
+    geometric=True (needs perturb=True): the affine kinds and Cutout of mumpy_hip.geometric as well, the first operations that move
+    the MASK with the frames.  The object additionally owns a second frame canvas and a second mask canvas (a gather cannot run in
+    place), one {mode, a0 .. a5, 0} row per frame and one per mask more in the parameter block (still one upload); after the
+    photometric launch (after the blur without one) launch() runs ops.geometric_u8 canvas -> second canvas, the same on the mask canvas
+    with channels=1, and the final stage reads the second canvases.  load(perturb=[...]) then also takes ("shear_x", 0.2),
+    ("rotate", -30), ... per clip: all T frames and the clip's mask share the clip's matrix, so clips that share a mask (b % nmasks)
+    must carry the same affine setting.  ("cutout", v) fills the rectangles of mumpy_hip.geometric.cutout_rects in the frames and
+    leaves the mask alone; their placement reads the canvas mask on the host (`canvas_mask`), so the masks must arrive on the host,
+    and load(..., rng=) supplies the generator.  geometric=False (the default) is the object as it was."""
 
-    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None, warp=False, perturb=False, photometric=False):
+    def __init__(self, x, target, src_hw, nmasks=None, mean=None, std=None, warp=False, perturb=False, photometric=False,
+                 geometric=False):
         import torch
         from . import ops
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 5 or x.shape[2] != 3 or x.shape[3] != x.shape[4] or not x.is_contiguous():
@@ -438,9 +453,11 @@ class AugmentedInput:
         shapes = dict(tab_a=(b, L), tab_b=(b, L), pos_y=(b, L), pos_x=(b, L), coef_y=(b, L, 4), coef_x=(b, L, 4), affine=(b, 8), swap=(b,),
                       mode=(b,))
         self._fields = tuple(shapes) if self.warp else ("tab_a", "tab_b", "swap")
-        self.perturb, self.photometric = bool(perturb), bool(photometric)
+        self.perturb, self.photometric, self.geometric = bool(perturb), bool(photometric), bool(geometric)
         if self.photometric and not self.perturb:
             raise ValueError("AugmentedInput: photometric=True needs perturb=True (the operations act on the canvas)")
+        if self.geometric and not self.perturb:
+            raise ValueError("AugmentedInput: geometric=True needs perturb=True (the operations act on the canvas)")
         if self.perturb:
             # qtab: (b, 2, 64) uint16 = 64 words per clip; blur: {r, ww, fw, on} per frame; sel: the clip's table or -1 per frame.
             # qtab and blur are loaded 16 bytes at a time: they go in front of the first one-word-per-clip array
@@ -451,6 +468,10 @@ class AugmentedInput:
             shapes.update(photo=(b * t, 4))
             at = self._fields.index("swap")
             self._fields = self._fields[:at] + ("photo",) + self._fields[at:]
+        if self.geometric:                                            # {mode, a0 .. a5, 0} per frame and per mask, 16 bytes at a time
+            shapes.update(geo=(b * t, 8), geo_mask=(self.nmasks, 8))
+            at = self._fields.index("swap")
+            self._fields = self._fields[:at] + ("geo", "geo_mask") + self._fields[at:]
         self._where, n = {}, 0
         for name in self._fields:
             self._where[name] = (n, n + int(np.prod(shapes[name])), shapes[name])
@@ -474,6 +495,9 @@ class AugmentedInput:
             if min(need) < 0:
                 raise RuntimeError(f"AugmentedInput: a canvas of {L}x{L} is refused: {lib.mumpy_last_error().decode()}")
             self._perturb_ws = torch.empty(max(need), dtype=u8, device=dev)
+            if self.geometric:
+                self.canvas2 = torch.empty_like(self.canvas)
+                self.mask_canvas2 = torch.empty_like(self.mask_canvas) if target is not None else None
             ops._nearest_table(hs, L, dev), ops._nearest_table(ws, L, dev)  # uploaded here, not inside a capture
 
     def _upload(self, dst, src, pinned, what):
@@ -487,9 +511,10 @@ class AugmentedInput:
             pinned.copy_(src)
             dst.copy_(pinned, non_blocking=True)
 
-    def _perturb_rows(self, perturb):
-        """-> (qtab (b, 64) words, blur (b * T, 4), sel (b * T,), photo (b * T, 4)) int32 of one setting per clip (None: the clip passes
-        through)."""
+    def _perturb_rows(self, perturb, masks_u8=None, rng=None):
+        """-> (qtab (b, 64) words, blur (b * T, 4), sel (b * T,), photo (b * T, 4), geo (b * T, 8), geo_mask (nmasks, 8)) int32 of one
+        setting per clip (None: the clip passes through)."""
+        from . import geometric as G
         from .perturb import box_params, check_spec, jpeg_tables
         from .photometric import params_row
         b, t = self.nclips, self.T
@@ -500,8 +525,10 @@ class AugmentedInput:
         blur = np.tile(np.array([0, 1 << 24, 0, 0], np.int64), (b, t, 1))
         sel = np.full((b, t), -1, np.int32)
         photo = np.zeros((b, t, 4), np.int32)
+        geo, geo_mask = np.zeros((b, t, 8), np.int32), np.zeros((self.nmasks, 8), np.int32)
+        moved = {}                                                    # mask -> (the first clip that reads it, its affine setting)
         for c, spec in enumerate(perturb):
-            steps = check_spec(spec, "AugmentedInput.load: perturb")
+            steps = check_spec(spec, "AugmentedInput.load: perturb", geometric=self.geometric)
             if len(steps) > 1:
                 raise ValueError("AugmentedInput.load: one setting per clip, (\"jpeg\", q) or (\"blur\", r), not a list")
             for kind, value in steps:
@@ -509,20 +536,58 @@ class AugmentedInput:
                     qtab[c], sel[c] = jpeg_tables(value), c
                 elif kind == "blur":
                     blur[c] = box_params(value)
+                elif kind == "cutout":
+                    geo[c] = self._cutout_rows(c, value, masks_u8, rng)
+                elif kind in G.AFFINE_KINDS:
+                    geo[c] = G.params_row(kind, value, (self.L, self.L))
                 elif not self.photometric:
                     raise ValueError(f"AugmentedInput.load: perturb: ({kind!r}, ...) needs an input built with photometric=True")
                 else:
                     photo[c] = params_row(kind, value)
-        return qtab.reshape(b, 128).view(np.int32), blur.astype(np.int32).reshape(b * t, 4), sel.reshape(b * t), photo.reshape(b * t, 4)
+            if self.geometric and self.nmasks:                        # the mask moves with the frames: one matrix per mask
+                affine = steps[0] if steps and steps[0][0] in G.AFFINE_KINDS else None
+                first, other = moved.setdefault(c % self.nmasks, (c, affine))
+                if other != affine:
+                    raise ValueError(f"AugmentedInput.load: perturb: clips {first} and {c} share mask {c % self.nmasks} and must carry the "
+                                     f"same affine setting, got {other!r} and {affine!r}")
+                geo_mask[c % self.nmasks] = geo[c, 0] if affine else 0
+        return (qtab.reshape(b, 128).view(np.int32), blur.astype(np.int32).reshape(b * t, 4), sel.reshape(b * t), photo.reshape(b * t, 4),
+                geo.reshape(b * t, 8), geo_mask)
 
-    def load(self, frames_u8, masks_u8, params, perturb=None):
+    def _cutout_rows(self, c, v, masks_u8, rng):
+        """The T rows of clip c for ("cutout", v): the reference's rectangles on the canvas, placed against the clip's canvas mask."""
+        import torch
+        from . import geometric as G
+        if self.target is None or masks_u8 is None:
+            raise ValueError("AugmentedInput.load: perturb: (\"cutout\", v) places its rectangles against the mask and needs an input "
+                             "built with a target")
+        if isinstance(masks_u8, torch.Tensor) and masks_u8.is_cuda:
+            raise ValueError("AugmentedInput.load: perturb: (\"cutout\", v) reads the mask on the host to place its rectangles; pass "
+                             "masks_u8 as a host array, not a device tensor")
+        if rng is None:
+            raise ValueError("AugmentedInput.load: perturb: (\"cutout\", v) draws its rectangles and needs rng= (a numpy Generator)")
+        mask = np.asarray(masks_u8)[c % self.nmasks]
+        if mask.shape != self.src_hw:
+            raise RuntimeError(f"AugmentedInput.load: masks must be ({self.nmasks}, {self.src_hw[0]}, {self.src_hw[1]}), got "
+                               f"{np.asarray(masks_u8).shape}")
+        L = self.L
+        cmask = canvas_mask(mask, nearest_table(self.src_hw[0], L), nearest_table(self.src_hw[1], L), 0)
+        rects = G.cutout_rects(cmask, v, self.T, rng)
+        rows = np.zeros((self.T, 8), np.int32)
+        for k, r in enumerate(rects):
+            rows[k] = G.params_row("cutout", r, (L, L))
+        return rows
+
+    def load(self, frames_u8, masks_u8, params, perturb=None, rng=None):
         import torch
         b, L = self.nclips, self.L
         if perturb is not None and not self.perturb:
             raise RuntimeError("AugmentedInput.load: perturb= needs an input built with perturb=True")
-        extra = dict(zip(("qtab", "blur", "sel", "photo"), self._perturb_rows(perturb))) if self.perturb else {}
+        extra = dict(zip(("qtab", "blur", "sel", "photo", "geo", "geo_mask"), self._perturb_rows(perturb, masks_u8, rng))) if self.perturb else {}
         if not self.photometric:
             extra.pop("photo", None)
+        if not self.geometric:
+            extra.pop("geo", None), extra.pop("geo_mask", None)
         st = self._stage[self._turn]
         self._turn ^= 1
         st["done"].synchronize()                 # host-side only: the upload of two loads ago has left this staging set
@@ -573,6 +638,10 @@ class AugmentedInput:
             ops.gaussian_blur_u8(frames, self.blur, out=frames, workspace=self._perturb_ws)
             if self.photometric:
                 ops.photometric_u8(frames, self.photo, out=frames, workspace=self._perturb_ws)
+            if self.geometric:
+                frames = ops.geometric_u8(frames, self.geo, out=self.canvas2)
+                if masks is not None:
+                    masks = ops.geometric_u8(masks, self.geo_mask, out=self.mask_canvas2, channels=1)
         if self.warp:
             ops.augment_warp_u8(frames, self.tab_a, self.tab_b, self.swap, self.mode, self.pos_y, self.pos_x, self.coef_y, self.coef_x,
                                 self.affine, masks=masks, out=self.x, target=target, mean=self.mean, std=self.std)

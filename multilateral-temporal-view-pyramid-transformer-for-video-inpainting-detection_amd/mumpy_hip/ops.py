@@ -1547,6 +1547,36 @@ def photometric_u8(frames, spec_or_params, out=None, workspace=None):
     return out
 
 
+def geometric_u8(src, params, out=None, channels=3):
+    """One geometric operation per image on the GPU (mumpy_geometric_u8_fwd, include/mumpy_geometric.h): src (..., H, W, 3) uint8,
+    or with channels=1 single-channel images (masks) (..., H, W), -> the same shape, bit for bit Pillow's Image.transform(size,
+    AFFINE, m, NEAREST, fillcolor=0) / Image.rotate / ImageDraw.rectangle(xy, 0) (mumpy_hip.geometric.apply_row is the numpy
+    statement).  params: a device tensor (nimg, 8) int32 of mumpy_hip.geometric.params_row rows, read when the kernel runs, or such
+    rows on the host (a numpy array / list, uploaded by this call: pass a tensor inside a graph capture); mode 0 copies that image
+    through.  One launch, no workspace.  out= is written in place and must be contiguous uint8 of src's shape; it must not overlap
+    src, src itself included (a gather cannot run in place)."""
+    who = "geometric_u8"
+    if channels not in (1, 3):
+        raise RuntimeError(f"mumpy_hip: geometric_u8: channels={channels} must be 1 or 3")
+    if channels == 1 and isinstance(src, torch.Tensor) and src.dim() < 2:
+        raise RuntimeError(f"mumpy_hip: geometric_u8 needs images (..., H, W) with channels=1, got {tuple(src.shape)}")
+    img = src.unsqueeze(-1) if channels == 1 and isinstance(src, torch.Tensor) and src.is_contiguous() else src
+    nimg, h, w = _frames_u8(img, who, channels)
+    if not isinstance(params, torch.Tensor):
+        import numpy as np
+        rows = np.asarray(params)
+        if rows.dtype != np.int32 or rows.shape != (nimg, 8):
+            raise RuntimeError(f"mumpy_hip: geometric_u8 needs params as int32 rows of shape ({nimg}, 8), got {rows.dtype} {rows.shape}")
+        params = torch.from_numpy(np.ascontiguousarray(rows)).to(src.device)
+    _chk_exact(params, "params", torch.int32, (nimg, 8), who)
+    out = torch.empty_like(src) if out is None else _chk_exact(out, "out", torch.uint8, src.shape, who)
+    lo, hi = sorted(((src.data_ptr(), src.numel()), (out.data_ptr(), out.numel())))
+    if nimg and lo[0] + lo[1] > hi[0]:
+        raise RuntimeError(f"mumpy_hip: geometric_u8: out {tuple(out.shape)} overlaps src (a gather cannot run in place)")
+    _call("mumpy_geometric_u8_fwd", _p(src), _p(out), _p(params), nimg, h, w, channels, _stream(), work=float(2 * out.numel()))
+    return out
+
+
 def resize_nearest_u8(frames, size, out=None, channels=3):
     """Image.resize((W, H), Image.NEAREST) of RGB frames on the GPU (mumpy_resize_nearest_u8_fwd, include/mumpy_perturb.h): frames
     (..., Hs, Ws, 3) uint8 -> (..., H, W, 3) uint8, size = (H, W), through the tables of mumpy_resize_nearest_table (cached per

@@ -217,10 +217,14 @@ def draw(rng, kinds=("jpeg", "blur")):
     return photometric.draw(rng, (kind,))
 
 
-def check_spec(spec, who="perturb"):
+def check_spec(spec, who="perturb", geometric=False):
     """None | ("jpeg", q) | ("blur", r) | (a photometric kind, its value) | a list of those -> the list [(kind, value), ...], refused
     unless every entry is a two-tuple of a known kind with a quality in 1 .. 100 / a finite radius >= 0 / the value
-    mumpy_hip.photometric.check_kind takes for that kind (None for autocontrast, equalize and invert)."""
+    mumpy_hip.photometric.check_kind takes for that kind (None for autocontrast, equalize and invert).
+    geometric=True: the kinds of mumpy_hip.geometric as well -- ("shear_x", 0.2), ("rotate", -30), ("cutout", 0.1), ... with the value
+    its check_kind takes.  They move the mask, so only a caller that moves it too passes True (AugmentedInput(geometric=True)); with
+    the default they are refused as any unknown kind is."""
+    from . import geometric as geo
     from . import photometric
     if spec is None:
         return []
@@ -230,14 +234,17 @@ def check_spec(spec, who="perturb"):
     out = []
     for it in items:
         if not (isinstance(it, (tuple, list)) and len(it) == 2 and isinstance(it[0], str)
-                and (it[0] in ("jpeg", "blur") or (it[0] in photometric.KINDS and it[0] != "none"))):
-            raise ValueError(f"{who}: {it!r} must be (\"jpeg\", quality), (\"blur\", radius) or a photometric (kind, value)")
+                and (it[0] in ("jpeg", "blur") or (it[0] in photometric.KINDS and it[0] != "none") or (geometric and it[0] in geo.KINDS))):
+            raise ValueError(f"{who}: {it!r} must be (\"jpeg\", quality), (\"blur\", radius) or a photometric (kind, value)"
+                             + (" or a geometric (kind, value)" if geometric else ""))
         if it[0] == "jpeg":
             jpeg_tables(it[1])
             out.append(("jpeg", int(it[1])))
         elif it[0] == "blur":
             box_params(it[1])
             out.append(("blur", float(it[1])))
+        elif it[0] in geo.KINDS:
+            out.append(geo.check_kind(it[0], it[1], who))
         else:
             out.append(photometric.check_kind(it[0], it[1], who))
     return out
