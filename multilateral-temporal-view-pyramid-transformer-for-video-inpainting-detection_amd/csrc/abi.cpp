@@ -16,6 +16,7 @@
 #include "../../include/mumpy_perturb.h"
 #include "../../include/mumpy_photometric.h"
 #include "../../include/mumpy_geometric.h"
+#include "../../include/mumpy_postprocess.h"
 
 namespace mumpy {
 static thread_local char g_err[512] = "";
@@ -91,5 +92,6 @@ extern "C" int mumpy_ext10_version(void) { return MUMPY_EXT10_VERSION; }
 extern "C" int mumpy_perturb_version(void) { return MUMPY_PERTURB_VERSION; }
 extern "C" int mumpy_photometric_version(void) { return MUMPY_PHOTOMETRIC_VERSION; }
 extern "C" int mumpy_geometric_version(void) { return MUMPY_GEOMETRIC_VERSION; }
+extern "C" int mumpy_postprocess_version(void) { return MUMPY_POSTPROCESS_VERSION; }
 extern "C" const char* mumpy_last_error(void) { return mumpy::g_err; }
 extern "C" const char* mumpy_last_route(void) { return mumpy::format_route(); }

@@ -214,6 +214,13 @@ GEOMETRIC = Surface("mumpy_geometric.h", "mumpy_geometric_version", 1, {
     "mumpy_geometric_u8_fwd": [c_f, c_f, c_f, c_l, c_i, c_i, c_i, c_f],
 })
 
+# include/mumpy_postprocess.h: cleaning predicted masks (small components out, small holes filled), a surface of its own for the same
+# reason; tests/test_postprocess_host.py holds it to its header and exports.
+POSTPROCESS = Surface("mumpy_postprocess.h", "mumpy_postprocess_version", 1, {
+    "mumpy_mask_clean_workspace_bytes": [c_l, c_i, c_i],
+    "mumpy_mask_clean_u8_fwd": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_l, c_l, c_i, c_i, c_f],
+})
+
 
 def library_path() -> str:
     """MUMPY_HIP_LIB=<file> overrides; MUMPY_TUNING=1 selects the diagnostics build (tools/gemm_shapes.py & co: the only build
@@ -253,7 +260,7 @@ def load_library():
     lib.mumpy_last_error.restype = ctypes.c_char_p
     lib.mumpy_last_route.restype = ctypes.c_char_p      # (AttributeError here or below = the library is stale: fail loudly)
     lib.mumpy_last_route.argtypes = []
-    for s in SURFACES + [PERTURB, PHOTOMETRIC, GEOMETRIC]:
+    for s in SURFACES + [PERTURB, PHOTOMETRIC, GEOMETRIC, POSTPROCESS]:
         version = getattr(lib, s.version_fn)
         version.restype, version.argtypes = c_i, []
         if version() != s.version:

@@ -1577,6 +1577,85 @@ def geometric_u8(src, params, out=None, channels=3):
     return out
 
 
+def mask_clean_params(spec, nimg, device):
+    """(nimg, 4) int32 on the device, {min_area, max_hole, connectivity, 0} per image: one setting for every image (a dict as
+    VideoPredictor(clean=...) takes it, or a (min_area, max_hole[, connectivity]) tuple), or one such setting per image (a list of
+    nimg of them) -- encoded by mumpy_hip.postprocess.params_row and uploaded."""
+    import numpy as np
+    from .postprocess import params_row
+
+    def row(s):
+        if isinstance(s, dict):
+            return params_row(s["min_area"], s["max_hole"], s.get("connectivity", 8))
+        return params_row(*s)
+    if isinstance(spec, dict) or (isinstance(spec, tuple) and len(spec) in (2, 3) and not isinstance(spec[0], (dict, tuple, list))):
+        rows = [row(spec)] * nimg
+    else:
+        rows = [row(s) for s in spec]
+        if len(rows) != nimg:
+            raise RuntimeError(f"mumpy_hip: mask_clean_params: {len(rows)} settings for {nimg} images")
+    return torch.from_numpy(np.asarray(rows, dtype=np.int32).reshape(nimg, 4)).to(device)
+
+
+def mask_clean_workspace(nimg, h, w, device):
+    """The workspace of one mask_clean_u8 call on nimg masks of h x w (mumpy_mask_clean_workspace_bytes); a refused shape raises."""
+    need = int(_lib().mumpy_mask_clean_workspace_bytes(nimg, h, w))
+    if need < 0:
+        raise RuntimeError(f"mumpy_hip: mask_clean_u8 (rc={need}): {_lib().mumpy_last_error().decode()}")
+    return torch.empty(max(need, 16), device=device, dtype=torch.uint8)
+
+
+def mask_clean_u8(mask, params, out=None, gt=None, counts=None, stats=None, workspace=None, hw=None):
+    """Small components out, small holes filled, per mask, on the GPU (mumpy_mask_clean_u8_fwd, include/mumpy_postprocess.h;
+    mumpy_hip.postprocess.clean is the numpy statement): mask (nimg, H, W) uint8 -- or (nimg, H * W) with hw=(H, W), the layout of
+    the predictor's bank --, non-zero is foreground -> out of the same shape, bytes 0 / 255.  params: a device tensor (nimg, 4) int32
+    of mumpy_hip.postprocess.params_row rows {min_area, max_hole, connectivity, 0}, read when the kernel runs, or such rows on the
+    host (a numpy array / list, uploaded by this call: pass a tensor inside a graph capture).  out= may be mask itself (in place) and
+    must not overlap it otherwise.  gt (the shape of mask, > 0 is forged): also counts (nimg, 4) int32 = [sum p & g, sum p, sum g,
+    sum p | g] of the cleaned masks, written, in the layout of mask_score_u8 (frame_metrics takes it).  stats (nimg, 8) int32:
+    mumpy_hip.postprocess.STATS; allocated when not given.  workspace= a uint8 tensor of mumpy_mask_clean_workspace_bytes(nimg, H, W)
+    bytes (`mask_clean_workspace`), allocated when not given.  One launch.  Returns (out, stats), or (out, counts, stats) with gt."""
+    who = "mask_clean_u8"
+    if not isinstance(mask, torch.Tensor) or not mask.is_cuda or mask.dtype != torch.uint8 or not mask.is_contiguous() or \
+            mask.dim() != (3 if hw is None else 2):
+        raise RuntimeError(f"mumpy_hip: {who} needs mask as a contiguous uint8 GPU tensor (nimg, H, W), or (nimg, H * W) with hw=, got "
+                           f"{getattr(mask, 'dtype', type(mask))} {tuple(getattr(mask, 'shape', ()))}")
+    nimg = mask.shape[0]
+    h, w = (int(v) for v in (mask.shape[1:] if hw is None else hw))
+    if hw is not None and (h < 1 or w < 1 or h * w != mask.shape[1]):
+        raise RuntimeError(f"mumpy_hip: {who}: hw={hw} does not give the {mask.shape[1]} pixels of a row of mask")
+    if not isinstance(params, torch.Tensor):
+        import numpy as np
+        rows = np.asarray(params)
+        if rows.dtype != np.int32 or rows.shape != (nimg, 4):
+            raise RuntimeError(f"mumpy_hip: {who} needs params as int32 rows of shape ({nimg}, 4), got {rows.dtype} {rows.shape}")
+        params = torch.from_numpy(np.ascontiguousarray(rows)).to(mask.device)
+    _chk_exact(params, "params", torch.int32, (nimg, 4), who)
+    out = torch.empty_like(mask) if out is None else _chk_exact(out, "out", torch.uint8, mask.shape, who)
+    if counts is not None and gt is None:
+        raise RuntimeError(f"mumpy_hip: {who}: counts= needs gt")
+    if gt is not None:
+        _chk_exact(gt, "gt", torch.uint8, mask.shape, who)
+        counts = torch.empty(nimg, 4, device=mask.device, dtype=torch.int32) if counts is None else \
+            _chk_exact(counts, "counts", torch.int32, (nimg, 4), who)
+    stats = torch.empty(nimg, 8, device=mask.device, dtype=torch.int32) if stats is None else \
+        _chk_exact(stats, "stats", torch.int32, (nimg, 8), who)
+    lo, hi = sorted(((mask.data_ptr(), mask.numel()), (out.data_ptr(), out.numel())))
+    if nimg and out.data_ptr() != mask.data_ptr() and lo[0] + lo[1] > hi[0]:
+        raise RuntimeError(f"mumpy_hip: {who}: out {tuple(out.shape)} overlaps mask without being mask")
+    need = int(_lib().mumpy_mask_clean_workspace_bytes(nimg, h, w))
+    if need < 0:
+        raise RuntimeError(f"mumpy_hip: {who} (rc={need}): {_lib().mumpy_last_error().decode()}")
+    if workspace is None:
+        workspace = torch.empty(max(need, 16), device=mask.device, dtype=torch.uint8)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or not workspace.is_contiguous() or workspace.numel() < need:
+        raise RuntimeError(f"mumpy_hip: {who} needs workspace as a contiguous uint8 GPU tensor of at least {need} bytes, got "
+                           f"{workspace.dtype} {tuple(workspace.shape)} on {workspace.device}")
+    _call("mumpy_mask_clean_u8_fwd", _p(mask), _p(out), _p(gt), _p(counts), _p(stats), _p(params), _p(workspace), workspace.numel(),
+          nimg, h, w, _stream(), work=float(2 * mask.numel()))
+    return (out, stats) if gt is None else (out, counts, stats)
+
+
 def resize_nearest_u8(frames, size, out=None, channels=3):
     """Image.resize((W, H), Image.NEAREST) of RGB frames on the GPU (mumpy_resize_nearest_u8_fwd, include/mumpy_perturb.h): frames
     (..., Hs, Ws, 3) uint8 -> (..., H, W, 3) uint8, size = (H, W), through the tables of mumpy_resize_nearest_table (cached per

@@ -205,11 +205,23 @@ class VideoPredictor(GraphedForward):
     mumpy_hip.photometric -- ("contrast", 1.4), ("equalize", None), ... -- may stand anywhere in the list, mixed with the two
     (ops.photometric_u8: Pillow's ImageOps / ImageEnhance, bit for bit, statistics per frame).  The predictor owns the tables and a
     workspace of perturb_chunk frames; a bad spec is refused here.  perturb=None (the default) allocates nothing and launches
-    nothing: the captured graph, the masks, the bank, the counts and the metric vector are what they were without the option."""
+    nothing: the captured graph, the masks, the bank, the counts and the metric vector are what they were without the option.
+
+    clean=dict(min_area=..., max_hole=..., connectivity=8): after the last batch of a predict, ONE launch (ops.mask_clean_u8,
+    include/mumpy_postprocess.h) removes every connected component below min_area pixels from each frame's mask and then fills every
+    hole of up to max_hole pixels (max_hole < 0: every hole; mumpy_hip.postprocess.clean is the numpy statement), bank[:n] ->
+    clean_bank[:n], and predict returns the cleaned masks.  The predictor then also owns clean_bank (max_frames, 224 * 224) uint8,
+    clean_counts (max_frames, 4), clean_stats (max_frames, 8), clean_acc (3,) float64, the parameter rows and the workspace; with
+    annotations one more ops.frame_metrics sums the cleaned masks' F1 / IoU into clean_acc (`metric_vector(clean=True)`), and
+    `clean_statistics()` is the (n, 8) table of mumpy_hip.postprocess.STATS.  bank, counts, metric_vector() and the sweep stay the
+    raw ones, bit for bit.  A bad setting is refused here; clean=None (the default) allocates nothing and launches nothing.  Not
+    covered: cleaned masks per threshold of a sweep, filtering across frames."""
 
     def __init__(self, encoder, decoder, T, src_hw, batch=8, max_frames=1024, thr=0.5, graph=True, gt_hw=None, gt_chunk=64,
-                 sweep=None, coupling="batch", perturb=None, perturb_chunk=64):
+                 sweep=None, coupling="batch", perturb=None, perturb_chunk=64, clean=None):
         from .perturb import check_spec, jpeg_tables
+        from .postprocess import check_spec as check_clean
+        clean = check_clean(clean, "VideoPredictor: clean", (SIDE, SIDE))      # refuses a bad setting
         if coupling not in ("batch", "clip"):
             raise ValueError(f"VideoPredictor: coupling must be \"batch\" or \"clip\", got {coupling!r}")
         steps = check_spec(perturb, "VideoPredictor: perturb")      # refuses a bad spec
@@ -284,6 +296,17 @@ class VideoPredictor(GraphedForward):
                 raise ValueError(f"VideoPredictor: perturb: frames of {hs}x{ws} are refused: {lib.mumpy_last_error().decode()}")
             self._perturb_ws = torch.empty(max(need), device=dev, dtype=torch.uint8)
             self._perturb_chunk = chunk
+        # clean: the cleaned bank with its counts, statistics and accumulator, the rows and the workspace; nothing of it exists without
+        self.clean = clean
+        if clean is not None:
+            from . import ops
+            self.clean_bank = torch.zeros(max_frames, npix, device=dev, dtype=torch.uint8)
+            self.clean_counts = torch.zeros(max_frames, 4, device=dev, dtype=torch.int32)
+            self.clean_stats = torch.zeros(max_frames, 8, device=dev, dtype=torch.int32)
+            self.clean_acc = torch.zeros(3, device=dev, dtype=torch.float64)
+            self._clean_params = ops.mask_clean_params(clean, max_frames, dev)
+            self._clean_ws = ops.mask_clean_workspace(max_frames, SIDE, SIDE, dev)
+            self._clean_n = 0
         clips = torch.zeros(batch, T, 3, SIDE, SIDE, device=dev, dtype=torch.float32)
         if self.graphed:
             super().__init__(encoder, decoder, clips, with_mask=True, coupling=coupling)     # static_x is the clip batch
@@ -322,7 +345,8 @@ class VideoPredictor(GraphedForward):
 
     def predict(self, frames_u8, gt_u8=None, on_batch=None):
         """frames_u8 (N, Hs, Ws, 3) uint8, on the host or the device, 1 <= N <= max_frames (N need not be a multiple of `batch`)
-        -> masks (N, 224, 224) uint8 with values 0 / 255 on the device: a view of the bank, valid until the next call.
+        -> masks (N, 224, 224) uint8 with values 0 / 255 on the device: a view of the bank (of clean_bank in a predictor built with
+        clean=: the cleaned masks), valid until the next call.
         gt_u8 (N, 224, 224) uint8 (> 0 counts as forged), already resized by the caller -- or, in a predictor built with
         gt_hw=(Hg, Wg), (N, Hg, Wg) uint8 at the annotations' own size, on the host or the device, holding the bytes
         Image.open(...).convert('L') gives: measure.py's Image.resize((224, 224), BILINEAR) then runs on the device, bit for bit
@@ -368,6 +392,15 @@ class VideoPredictor(GraphedForward):
             ops.frame_metrics(self.counts, n, SIDE * SIDE, acc=self.acc, accumulate=True)
             if self.table is not None:
                 ops.sweep_metrics(self.exceed, n, SIDE * SIDE, acc=self.sweep_acc, pooled=self.sweep_pooled, accumulate=True)
+        if self.clean is not None:
+            scored = gt_u8 is not None
+            ops.mask_clean_u8(self.bank[:n], self._clean_params[:n], out=self.clean_bank[:n], gt=self.gt[:n] if scored else None,
+                              counts=self.clean_counts[:n] if scored else None, stats=self.clean_stats[:n], workspace=self._clean_ws,
+                              hw=(SIDE, SIDE))
+            if scored:
+                ops.frame_metrics(self.clean_counts, n, SIDE * SIDE, acc=self.clean_acc, accumulate=True)
+            self._clean_n = n
+            return self.clean_bank[:n].view(n, SIDE, SIDE)
         return self.bank[:n].view(n, SIDE, SIDE)
 
     def _perturb_frames(self, n):
@@ -400,9 +433,19 @@ class VideoPredictor(GraphedForward):
             self._gt_stage[:m].copy_(gt_u8[i:i + m], non_blocking=True)
             ops.resize_bilinear_u8(self._gt_stage[:m], (SIDE, SIDE), out=bank[i:i + m])
 
-    def metric_vector(self) -> torch.Tensor:
-        """The device [sum F1, sum IoU, n] over every frame scored since the last reset: what evaluate.finalize_metrics takes."""
-        return self.acc
+    def metric_vector(self, clean=False) -> torch.Tensor:
+        """The device [sum F1, sum IoU, n] over every frame scored since the last reset: what evaluate.finalize_metrics takes.
+        clean=True: the same sums of the cleaned masks (only in a predictor built with clean=)."""
+        if clean and self.clean is None:
+            raise RuntimeError("VideoPredictor.metric_vector: this predictor was built without clean=")
+        return self.clean_acc if clean else self.acc
+
+    def clean_statistics(self) -> torch.Tensor:
+        """(n, 8) int32 on the device, a view: per frame of the last predict the columns of mumpy_hip.postprocess.STATS -- components
+        found, kept, pixels removed, holes filled, pixels filled, the largest kept component, 0, status (0).  Only with clean=."""
+        if self.clean is None:
+            raise RuntimeError("VideoPredictor.clean_statistics: this predictor was built without clean=")
+        return self.clean_stats[:self._clean_n]
 
     def sweep_vector(self):
         """(table (K,) float32, sweep_acc (K, 3) float64, sweep_pooled (2, K + 1) int64) on the device: the thresholds, per threshold
@@ -414,18 +457,24 @@ class VideoPredictor(GraphedForward):
 
     def reset_metrics(self) -> None:
         self.acc.zero_()
+        if self.clean is not None:
+            self.clean_acc.zero_()
         if self.table is not None:
             self.sweep_acc.zero_()
             self.sweep_pooled.zero_()
 
-    def write_masks(self, dirname, frame_numbers) -> None:
+    def write_masks(self, dirname, frame_numbers, clean=None) -> None:
         """Saves the masks of the last predict as '%04d_instance_%02d.png' % (frame_number, 0) (test.py:109-111), one per entry of
-        frame_numbers.  The one place that copies masks to the host."""
+        frame_numbers.  The one place that copies masks to the host.  clean=None saves the cleaned masks when the predictor was built
+        with clean= and the raw ones otherwise; clean=False the raw ones; clean=True needs a predictor built with clean=."""
+        if clean and self.clean is None:
+            raise RuntimeError("VideoPredictor.write_masks: this predictor was built without clean=")
+        bank = self.clean_bank if (self.clean is not None and clean is not False) else self.bank
         from PIL import Image
         frame_numbers = [int(f) for f in frame_numbers]
         if not 1 <= len(frame_numbers) <= self.max_frames:
             raise ValueError(f"VideoPredictor.write_masks: {len(frame_numbers)} frame numbers for banks of {self.max_frames} frames")
-        masks = self.bank[:len(frame_numbers)].view(-1, SIDE, SIDE).cpu().numpy()
+        masks = bank[:len(frame_numbers)].view(-1, SIDE, SIDE).cpu().numpy()
         os.makedirs(dirname, exist_ok=True)
         for f, m in zip(frame_numbers, masks):
             Image.fromarray(m).save(os.path.join(dirname, "%04d_instance_%02d.png" % (f, 0)))
